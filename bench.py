@@ -8,13 +8,19 @@ reference blocks; the 1,024-byte tail is dropped like the reference drops partia
 Multi-GPU: one process per GPU (torch.distributed.run); every rank receives its own
 independent stream (weak scaling, no data-path collective); timing is the max over ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 Prints ONE JSON line on rank 0.  `roofline` prices the fused kernel against HBM (SURVEY
 §8d algorithmic bytes: 2 B/IQ in + 2 B per mono audio frame out) from HIP-event kernel
 times on the context stream; `compute` gives the same kernel against the FP32 VALU roof.
-`cpu_baseline` times the reference's own src/filter.cpp mono path (oracle/_ref, 1 core) on
-the same bytes and reports whether its PCM equals the GPU's bit for bit.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, the
+result line.  --dump-outputs DIR writes the PCM of the last timed step to DIR/pcm_mono.npy
+(float32; the input is seeded, so two builds can be compared sample for sample).  --full adds
+every leg that takes runs of its own: the attainable HBM bandwidth (a device copy), the CPU
+baselines (`cpu_baseline` times the reference's own src/filter.cpp mono path, oracle/_ref,
+1 core, on the same bytes and reports whether its PCM equals the GPU's bit for bit) and the
+other BASELINE configs with their parity checks, baselines and stage latencies.
 """
 from __future__ import annotations
 
@@ -144,6 +150,11 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--min-warmup-seconds", type=float, default=1.0,
                     help="untimed warm-up runs at least this long (clock ramp), besides the W steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every leg that takes runs of its own: the HBM copy bandwidth, the CPU "
+                         "baselines, the other BASELINE configs (the options below trim these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the PCM of the last timed step to DIR/pcm_mono.npy (float32, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-bytes", type=int, default=STREAM_BYTES)
     ap.add_argument("--no-other-configs", action="store_true",
@@ -228,6 +239,11 @@ def main() -> None:
     barrier()
     elapsed = time.perf_counter() - t0
     kern_ms, launches = rx.kernel_timing(reset=-1)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the S16 mono PCM of the whole
+        # stream (83,886 x 128 frames; 43 MB as float32, exact), rank 0's stream at N > 1
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pcm_mono.npy"), d_pcm.cpu().numpy().astype(np.float32))
     ranks = None
     if dist is not None:  # every rank's own (seconds, kernel ms): a slow rank shows by name
         dmod = iqgen.load_module("dist")
@@ -283,10 +299,11 @@ def main() -> None:
             "flop_per_iq": round(flops_per_iq(RF_TAPS), 2),
         },
     }
-    # the attainable HBM bandwidth next to the datasheet peak -- a device-to-device
-    # copy of the 1 GiB input (read + write counted), after the timed region
-    line["roofline"]["hbm_attainable_GBs"] = hbm_copy_bandwidth(d_iq)
-    line["roofline"]["frac_of_attainable"] = round(achieved / line["roofline"]["hbm_attainable_GBs"], 4)
+    if args.full:
+        # the attainable HBM bandwidth next to the datasheet peak -- a device-to-device
+        # copy of the 1 GiB input (read + write counted), after the timed region
+        line["roofline"]["hbm_attainable_GBs"] = hbm_copy_bandwidth(d_iq)
+        line["roofline"]["frac_of_attainable"] = round(achieved / line["roofline"]["hbm_attainable_GBs"], 4)
     # binding roof: the kernel is bound by the FP32 VALU without FMA (bit parity), not by HBM
     line["roofline"]["binding"] = dict(line["compute"])
     # PMC traffic of record, only while it was measured on this kernel's sources
@@ -311,14 +328,15 @@ def main() -> None:
                         "per_rank": [{"rank": r, "seconds": round(v[0], 4), "kernel_ms": round(v[1], 4)}
                                      for r, v in enumerate(ranks)]}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # the contract: rank 0 at N=1 only
+    # everything below the headline takes runs of its own: --full only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # the contract: rank 0 at N=1 only
         host = host_info()
         line["cpu_baseline"] = cpu_baseline(d_iq, d_pcm, args.cpu_sample_bytes, bb, na)
         line["cpu_baseline"]["host"] = host
         line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(d_iq, args.cpu_sample_bytes, bb, host["usable_cores"])
         if line["cpu_baseline_all_cores"] is not None:
             line["cpu_baseline_all_cores"]["host"] = host
-    if not args.no_other_configs:
+    if args.full and not args.no_other_configs:
         del d_iq, d_pcm
         rx.close()
         torch.cuda.empty_cache()

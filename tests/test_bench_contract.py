@@ -1,6 +1,7 @@
 """bench.py's output contract (the driver parses this line every round): one JSON line with
-the metric, whole-job value, timing fields, roofline and the CPU baseline keys.  A short run
-(2 steps, 1 warmup) on the GPU, in a child process (it owns the device while it runs)."""
+the metric, whole-job value, timing fields and roofline; with --full the other BASELINE configs
+and the CPU baseline keys too.  A short run (2 steps, 1 warmup) on the GPU, in a child process
+(it owns the device while it runs)."""
 from __future__ import annotations
 
 import json
@@ -24,7 +25,7 @@ def _run(*extra):
 
 
 def test_bench_json_contract():
-    j = _run("--no-cpu-baseline", "--streams-seconds", "0.5")
+    j = _run("--full", "--no-cpu-baseline", "--streams-seconds", "0.5")
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int),
                  ("warmup", int), ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str),
                  ("dtype", str), ("data", str), ("config", dict), ("roofline", dict)):
@@ -87,7 +88,7 @@ def test_bench_json_contract():
 
 
 def test_bench_cpu_baseline_keys():
-    j = _run("--cpu-sample-bytes", str(64 * 12800), "--no-other-configs")
+    j = _run("--full", "--cpu-sample-bytes", str(64 * 12800), "--no-other-configs")
     cb = j["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] == 1 and cb["value"] > 0
     assert cb["bit_exact_vs_gpu"] is True
@@ -95,3 +96,31 @@ def test_bench_cpu_baseline_keys():
         h = j[key]["host"]
         assert h["nproc"] >= 1 and h["cpu_model"] and 1 <= h["usable_cores"] <= h["affinity_cpus"]
     assert j["cpu_baseline_all_cores"]["cores"] == j["cpu_baseline_all_cores"]["host"]["usable_cores"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_output(tmp_path, fmrx, orc):
+    """Without --full the line carries the headline and the timed kernel's own figures, none of
+    the legs that take runs of their own; --dump-outputs leaves the last timed step's PCM.  The
+    timed steps carry state from pass to pass, which reaches into block 0 only (100 RF taps, 50
+    audio taps at 240 kS/s and one demod sample: 600 of the block's 6,400 IQ pairs), so blocks
+    1.. of the dump equal a fresh oracle pass over the same seeded input bit for bit."""
+    import numpy as np
+
+    j = _run("--dump-outputs", str(tmp_path / "out"))
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float),
+                 ("higher_is_better", bool), ("dtype", str)):
+        assert isinstance(j[k], t), k
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert j["roofline"]["kernel_ms"] > 0 and j["roofline"]["launches_timed"] == 2
+    for k in ("cpu_baseline", "cpu_baseline_all_cores", "baseline_configs"):
+        assert k not in j, k
+    assert "hbm_attainable_GBs" not in j["roofline"]
+    assert [p.name for p in (tmp_path / "out").iterdir()] == ["pcm_mono.npy"]
+    pcm = np.load(tmp_path / "out" / "pcm_mono.npy")
+    assert pcm.dtype == np.float32 and pcm.shape == (j["config"]["blocks_per_gpu"] * 128,)
+    assert pcm.nbytes <= 64 << 20
+    nb = 8
+    iq = fmrx.synth_host(1000, 2400000, 0, nb * 6400)  # bench.py's rank-0 stream
+    want = orc.run(0, 101, iq, ["pcm_mono"])["pcm_mono"]
+    assert want[128:].any()
+    assert np.array_equal(pcm[128:nb * 128], want[128:].astype(np.float32))

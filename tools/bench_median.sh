@@ -5,6 +5,6 @@ set -o pipefail
 OUT=gpurun_out/${1:-median}
 mkdir -p $OUT
 for i in 1 2 3 4 5; do
-  timeout -k 10 120 python bench.py --no-cpu-baseline --no-other-configs > $OUT/bench_$i.json 2> $OUT/bench_$i.err || exit 1
+  timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-other-configs > $OUT/bench_$i.json 2> $OUT/bench_$i.err || exit 1
 done
 echo done

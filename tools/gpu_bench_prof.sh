@@ -6,7 +6,7 @@ TAG=${1:-r01}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $OUT/kt -o run --output-format csv -- \
     python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-other-configs > $OUT/kt.log 2>&1 || exit 2
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -T -d $OUT/pmc_fetch -o run --output-format csv -- \

@@ -42,7 +42,7 @@ for step in "$@"; do
          tail -2 $OUT/pll.log ;;
     stages) timeout -k 10 300 python tools/stage_times.py > $OUT/stages.json 2> $OUT/stages.err || { tail $OUT/stages.err; exit 3; }
             cat $OUT/stages.json ;;
-    bench) timeout -k 10 400 python bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 4; }
+    bench) timeout -k 10 400 python bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 4; }
            python -c "import json; j=json.load(open('$OUT/bench.json')); print(j['value'], j['roofline']['kernel_ms'], json.dumps(j.get('baseline_configs',{}))[:1500])" ;;
     pllcnt) FMRX_PLL_CNT=${CNT:-31} timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --timeout 300 --timeout-method thread -k "pll or stereo or index or bench_config or refdata or cli or pipe" > $OUT/pllcnt.log 2>&1 || { tail -40 $OUT/pllcnt.log; exit 12; }
          tail -2 $OUT/pllcnt.log ;;
@@ -65,7 +65,7 @@ for step in "$@"; do
            done; done
            grep -v amdgpu.ids $OUT/rprof.txt ;;
     n2) FMRX_BENCH_BACKEND=gloo timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 3 --no-cpu-baseline \
+          --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 3 --full --no-cpu-baseline \
           > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err || { tail $OUT/bench_n2_gloo.err; exit 9; }
         python -c "import json; j=json.load(open('$OUT/bench_n2_gloo.json')); c=j['baseline_configs']['configs[4]']; print(j['value'], {k: c.get(k) for k in ('seconds', 'seconds_process', 'seconds_gather', 'gather_chunks', 'gather_GBs_after_processing', 'bit_exact_vs_reference')})" ;;
     profmono) bash tools/gpu_bench_prof.sh $TAG/prof_mono || exit 20 ;;

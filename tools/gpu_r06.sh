@@ -8,7 +8,7 @@ mkdir -p "$out"
 timeout -k 10 600 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread \
     > "$out/gpu_tests.log" 2>&1 || { echo "tests failed"; tail -30 "$out/gpu_tests.log"; exit 1; }
 tail -3 "$out/gpu_tests.log"
-timeout -k 10 600 python -u bench.py > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -20 "$out/bench.err"; exit 1; }
+timeout -k 10 600 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -20 "$out/bench.err"; exit 1; }
 if [ -e software-defined-radio-course-project_amd/build_ab_head/libfmrx.so ]; then
   tools/gpu_r06_ab.sh "$out/ab" new= head=software-defined-radio-course-project_amd/build_ab_head/libfmrx.so || exit 1
 fi
