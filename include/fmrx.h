@@ -227,6 +227,10 @@ int fmrx_debug_pll_stats(fmrx_ctx* ctx, unsigned long long* d_counts);
  * d_counts[8 s + r] += the intervals the runner redid on the exact path (a trigArg outside its    *
  * candidates or an uncertified step), d_counts[8 s + 4 + r] += the steps it ran demoted (most of   *
  * its last 32 intervals missed, as on an unlocked loop: the rest of the range on the exact path). *
+ * Demoted steps are filed under the range of the trigOffset at which the stream was demoted: in a *
+ * call whose runner launches share one demoted launch (the pipelined engine, one a chunk), the    *
+ * steps of the later launches it covers land in that slot too, also past a range boundary.  The   *
+ * sum of a stream's slots 4 .. 7 is its demoted steps.                                            *
  * Results are unchanged.  d_counts = NULL turns it off.                                           */
 int fmrx_debug_pll_redos(fmrx_ctx* ctx, unsigned* d_counts);
 

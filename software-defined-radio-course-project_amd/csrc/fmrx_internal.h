@@ -206,7 +206,10 @@ int launch_pll_demoted(hipStream_t s, const float* io, int n, int n_streams, siz
 // fmrx_debug_pll_redos: per stream kPllRedoSlots u32, by the trigOffset range r of the runner's
 // launch (0 [2^17, 2^20), 1 [2^20, 2^21), 2 [2^21, 2^22), 3 from 2^22, the stick included):
 // slot r the intervals the self-certifying runners redid exactly, slot 4 + r the steps they ran
-// demoted (pll_demote: the rest of a range on the exact path after most intervals missed)
+// demoted (pll_demote: the rest of a range on the exact path after most intervals missed).  Demoted
+// steps go by the trigOffset at which the stream was demoted (state slot 5 as the runner left it):
+// a later launch that only adds its steps to the hand-off (PllHint::demote_once) files them in
+// that slot too, also past a range boundary; a stream's slots 4 .. 7 sum to its demoted steps
 constexpr int kPllRedoSlots = 8;
 constexpr int kPllIdxSimds = 4;  // SIMDs a stream takes: one CU (launch_pll admits n_simd / 4 streams)
 // the index runner's lowest trigOffset: 2^17 (kPllIdxMin64; 2^18, kPllIdxMin, with FMRX_PLL_IDX=1).  In

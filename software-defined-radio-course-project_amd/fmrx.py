@@ -406,7 +406,10 @@ class Receiver:
     def debug_pll_redos(self, d_counts) -> None:
         """fmrx_debug_pll_redos: per stream and trigOffset range of the self-certifying runners
         (REDO_RANGES), redone intervals and demoted steps (n_streams x 8 u32 on the device, zeroed
-        by the caller: [r] redone intervals, [4 + r] demoted steps; None turns it off)."""
+        by the caller: [r] redone intervals, [4 + r] demoted steps; None turns it off).  Demoted
+        steps are filed under the range of the trigOffset where the stream was demoted: where one
+        demoted launch covers several runner launches (the pipelined engine, one a chunk), the later
+        launches' steps land in that slot too, also past a range boundary -- [4:].sum() is exact."""
         _check(lib().fmrx_debug_pll_redos(self.h, d_counts))
 
 

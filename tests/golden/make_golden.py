@@ -28,7 +28,11 @@ Inputs (no reference data file holds I/Q — data/samples*.raw are missing blobs
                         no pilot, heavy noise) and of a mode-2 stream of > 2^24 PLL steps (the
                         reference hands its PLL the upsampled if_fs, project.cpp:166,348)
 
-Usage: python tests/golden/make_golden.py [--rds-only | --bench-only | --streams-all | --unlocked-only]
+  unlocked_c4_*         in hashes.json: the same fields for unlocked streams of BASELINE configs[4]'s
+                        length (60 s, 22,500 blocks), which the many-stream tests run among the
+                        locked streams of streams_c4_60s
+
+Usage: python tests/golden/make_golden.py [--rds-only | --bench-only | --streams-all | --unlocked-only | --mixed-only]
        (needs /root/reference; not run on the GPU box)
 """
 from __future__ import annotations
@@ -83,6 +87,15 @@ UNLOCKED = [
     ("unlocked_m0_nopilot_80s", 0, 51, "nopilot:62", 80.0),  # no pilot: the loop runs off frequency
     ("unlocked_m0_noisy_80s", 0, 51, "noisy:63", 80.0),      # heavy noise: cycle slips
     ("unlocked_m2_synth_170b", 2, 51, "synth:64", 72.6),     # 170 blocks, 17.4 M steps at if_fs 35.28 MHz
+]
+
+# Unlocked streams of the configs[4] length (60 s: 14.4 M steps, through every runner form below the
+# stick), run among the locked synth:<id> streams of streams_c4_60s in one many-stream call.
+MIXED = [
+    ("unlocked_c4_nopilot_60s", 0, 51, "nopilot:301", 60.0),
+    ("unlocked_c4_noisy_60s", 0, 51, "noisy:302", 60.0),
+    ("unlocked_c4_rand_60s", 0, 51, "rand:303", 60.0),
+    ("unlocked_c4_noisy2_60s", 0, 51, "noisy:304", 60.0),
 ]
 
 
@@ -214,12 +227,12 @@ def long_entry(ref, mode: int, rf_taps: int, recipe: str, secs: float) -> dict:
             "pll_state_last": [float(v) for v in out["pll_state"][-6:]]}
 
 
-def make_unlocked(ref) -> None:
-    """Add the UNLOCKED entries to hashes.json (the other entries stay as they are)."""
+def make_unlocked(ref, entries=None) -> None:
+    """Add the UNLOCKED (or the given) entries to hashes.json (the other entries stay as they are)."""
     path = os.path.join(HERE, "hashes.json")
     with open(path) as f:
         hashes = json.load(f)
-    for name, mode, rf_taps, recipe, secs in UNLOCKED:
+    for name, mode, rf_taps, recipe, secs in UNLOCKED if entries is None else entries:
         hashes[name] = long_entry(ref, mode, rf_taps, recipe, secs)
         print(f"unlocked {name}: {hashes[name]['n_blocks']} blocks, PLL {hashes[name]['pll_state_last']}")
     with open(path, "w") as f:
@@ -240,6 +253,9 @@ def main() -> None:
         return
     if "--unlocked-only" in sys.argv:
         make_unlocked(ref)
+        return
+    if "--mixed-only" in sys.argv:
+        make_unlocked(ref, MIXED)
         return
     meta = {"glibc": platform.libc_ver(), "generator": "oracle/_ref/libfmref.so (reference "
             "src/filter.cpp + src/iofunc.cpp, g++ -O3, no -march) via oracle/ref_driver.cpp"}
@@ -288,6 +304,7 @@ def main() -> None:
         json.dump(hashes, f, indent=1)
     make_bench(ref)
     make_unlocked(ref)
+    make_unlocked(ref, MIXED)
 
 
 if __name__ == "__main__":

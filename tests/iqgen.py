@@ -53,6 +53,18 @@ def stream_hashes(n_streams: int, n_blocks: int) -> dict:
     return {}
 
 
+def unlocked_stream_runs() -> dict:
+    """The unlocked streams of BASELINE configs[4]'s length (hashes.json unlocked_c4_*: no pilot,
+    heavy noise, random bytes; 22,500 blocks like streams_c4_60s, beside whose locked streams the
+    many-stream tests run them): name -> entry (recipe, input / PCM SHA-256, final PLL state).
+    They are unlocked_* entries too, so conftest's unlocked_runs() holds them as well."""
+    import json
+
+    with open(os.path.join(REPO, "tests", "golden", "hashes.json")) as f:
+        h = json.load(f)
+    return {k: v for k, v in h.items() if k.startswith("unlocked_c4_")}
+
+
 def splitmix64(x: np.ndarray) -> np.ndarray:
     x = x.astype(np.uint64)
     with np.errstate(over="ignore"):

@@ -750,7 +750,7 @@ def _unlocked_input(rx, h):
         rx.synth_device(int(arg) | iqgen.SYNTH_FLAGS[kind], 0, n // 2, d.data_ptr())
         rx.synchronize()
     else:
-        d.copy_(torch.from_numpy(iqgen.make(h["recipe"], n, rx.geo.rf_fs)))
+        d.copy_(torch.from_numpy(_recipe_bytes(h["recipe"], n)))
     assert sha(d.cpu().numpy()) == h["input_sha256"]
     return d
 
@@ -1322,6 +1322,422 @@ def test_predicted_runner_rows(fmrx, monkeypatch):
             r1.process(ins[s, : 2 * bb])
             r1.set_state(_stream_blob(bytes(blob), r1.get_state(), ns, s))
             assert np.array_equal(r1.process(ins[s, 2 * bb:]), out[s]), s
+
+
+# ---- unlocked streams beside locked ones, across calls, and the demoted kernel's edges ----------
+
+_RECIPE_CACHE = {}
+
+
+def _recipe_bytes(recipe, n):
+    """A mode-0 recipe's bytes.  The random ones (numpy, seconds for a long stream) are kept for the
+    next test that asks for the same (one array at a time: hundreds of MB), never modified."""
+    if not recipe.startswith("rand:"):
+        return iqgen.make(recipe, n)
+    if (recipe, n) not in _RECIPE_CACHE:
+        _RECIPE_CACHE.clear()
+        _RECIPE_CACHE[(recipe, n)] = iqgen.make(recipe, n)
+    return _RECIPE_CACHE[(recipe, n)]
+
+
+def _pll_rows(rx, ns):
+    """Every stream's 8-float PLL row of a context's state blob (api.cpp state_io order)."""
+    blob = rx.get_state()
+    hdr = np.frombuffer(blob[:40], np.uint32)
+    off = 40 + ns * (int(hdr[6]) + 4 * int(hdr[7]) + 4 * 64)
+    return np.frombuffer(blob[off: off + ns * 32], np.float32).reshape(ns, 8)
+
+
+# stream index -> unlocked fixture, the other streams locked (synth:<index>, streams_c4_60s): the
+# first, a middle and the last index, and two neighbours
+_MIXED_24 = {0: "unlocked_c4_rand_60s", 11: "unlocked_c4_nopilot_60s", 16: "unlocked_c4_noisy_60s",
+             17: "unlocked_c4_noisy2_60s", 23: "unlocked_c4_nopilot_60s"}
+_MIXED_4 = {0: "unlocked_c4_nopilot_60s", 2: "unlocked_c4_noisy_60s"}
+
+
+@pytest.mark.parametrize("n_streams,cuts", [(24, ()), (24, (7001, 18001)), (4, ())],
+                         ids=["24-one-call", "24-three-calls", "4-serial"])
+def test_mixed_locked_unlocked_streams(fmrx, n_streams, cuts):
+    """Locked and unlocked streams in one context, 60 s (22,500 blocks: every runner form below the
+    stick): the unlocked fixtures (no pilot, heavy noise, random bytes) among locked synth streams.
+    24 streams take the pipelined engine, where ONE pll_demoted_kernel launch a chunk follows the
+    chunk's runner launches (PllHint::demote_once: a demoted stream's later launches only add their
+    steps to state slot 6, across the form boundaries and a long form's body / 16-step tail), in one
+    call and in three calls of 7,001 / 11,000 / 4,499 blocks (no multiple of the chunk count: the
+    state and a cleared slot 6 across calls); 4 streams take the serial engine (a demoted launch
+    after every range).  Every stream's PCM and the unlocked streams' final PLL state against the
+    reference build's; every unlocked stream demoted, no locked one; the runners were chosen
+    (3 x and kPllIdxSimds x n_streams fit the SIMDs: batches were checked)."""
+    import time
+
+    t_start = time.perf_counter()
+    unl = iqgen.unlocked_stream_runs()
+    where = _MIXED_24 if n_streams == 24 else _MIXED_4
+    nb = 22500
+    locked = iqgen.stream_hashes(256, nb)
+    hs = [unl[where[s]] if s in where else None for s in range(n_streams)]
+    seeds = []
+    for s, h in enumerate(hs):
+        kind, _, arg = (h["recipe"] if h else "synth:%d" % s).partition(":")
+        seeds.append(int(arg) | iqgen.SYNTH_FLAGS[kind] if kind in iqgen.SYNTH_FLAGS else None)
+    edges = [0, *cuts, nb]
+    with fmrx.Receiver(0, fmrx.STEREO, n_streams=n_streams) as rx:
+        bb, ps = rx.geo.block_bytes, rx.geo.pcm_samples
+        assert all(h is None or h["n_blocks"] == nb for h in hs)
+        counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+        redos = torch.zeros((n_streams, fmrx.REDO_SLOTS), dtype=torch.int32, device="cuda")
+        rx.debug_pll_stats(counts.data_ptr())
+        rx.debug_pll_redos(redos.data_ptr())
+        parts = []
+        for b0, b1 in zip(edges[:-1], edges[1:]):
+            m = (b1 - b0) * bb
+            d_iq = torch.empty((n_streams, m), dtype=torch.uint8, device="cuda")
+            d_pcm = torch.empty((n_streams, (b1 - b0) * ps), dtype=torch.int16, device="cuda")
+            # the synth recipes on the device (identical bytes: test_device_synth_equals_host; a
+            # stream of host-made bytes gets a locked seed first and is overwritten)
+            rx.synth_device_streams([0 if v is None else v for v in seeds], b0 * bb // 2, m // 2, d_iq.data_ptr(), m)
+            rx.synchronize()
+            for s, h in enumerate(hs):
+                if seeds[s] is None:
+                    d_iq[s].copy_(torch.from_numpy(_recipe_bytes(h["recipe"], nb * bb)[b0 * bb: b1 * bb]))
+                if h is not None and n_streams == 4:
+                    assert sha(d_iq[s].cpu().numpy()) == h["input_sha256"], s
+                if h is not None and b0 == 0:  # the head of every unlocked stream against the host's bytes
+                    head = _recipe_bytes(h["recipe"], nb * bb)[: 4 * bb] if seeds[s] is None else \
+                        fmrx.synth_host(seeds[s], rx.geo.rf_fs, 0, 2 * bb)
+                    assert np.array_equal(d_iq[s, : 4 * bb].cpu().numpy(), head), s
+            torch.cuda.synchronize()
+            rx.process_device(d_iq.data_ptr(), b1 - b0, d_pcm.data_ptr())
+            rx.synchronize()
+            parts.append(d_pcm.cpu().numpy())
+            del d_iq, d_pcm
+        rx.debug_pll_stats(None)
+        rx.debug_pll_redos(None)
+        blob = rx.get_state()
+    with fmrx.Receiver(0, fmrx.STEREO) as r1:
+        hdr1 = r1.get_state()
+    for s, h in enumerate(hs):
+        got = sha(np.concatenate([p[s] for p in parts]))
+        assert got == (h["pcm_sha256"] if h else locked[s]), (s, where.get(s))
+        if h:
+            b1 = _stream_blob(blob, hdr1, n_streams, s)
+            hdr = np.frombuffer(b1[:40], np.uint32)
+            off = 40 + int(hdr[6]) + 4 * int(hdr[7]) + 4 * 64
+            assert same(np.frombuffer(b1[off: off + 24], np.float32), np.asarray(h["pll_state_last"], np.float32)), s
+    resumed, checked = counts.cpu().tolist()
+    assert checked > 0, (resumed, checked)
+    dem = redos.cpu().numpy()[:, 4:].astype(np.int64).sum(axis=1)
+    print("mixed %s: %.2f s wall, demoted steps %s" % ((n_streams, cuts), time.perf_counter() - t_start, dem.tolist()))
+    for s in range(n_streams):
+        assert (dem[s] > 0) == (s in where), (s, dem.tolist())
+
+
+# (edge, steps an interval of the form in front of it, of the form behind it: pll_form_interval)
+_FORM_EDGES = [(262144.0, 16, 16), (524288.0, 16, 64), (1048576.0, 64, 128), (2097152.0, 128, 128),
+               (4194304.0, 128, 256), (16777216.0, 256, 256)]
+
+
+def _chunk_begin(nb, k, K, head=8, tail=8):
+    """api.cpp chunk_begin: the first block of chunk k of K (the first chunk head / 16 of a middle
+    one, the last tail / 16)."""
+    if K <= 1 or k <= 0:
+        return 0 if k <= 0 else nb
+    if k >= K:
+        return nb
+    return nb * (head + 16 * (k - 1)) // (head + 16 * (K - 2) + tail)
+
+
+def _default_chunks(nb, ns):
+    """api.cpp stereo_chunks without the knob: 8 from 16 streams, fewer until a chunk holds 2^14 steps."""
+    k = 8 if ns >= 16 else 1
+    while k > 1 and nb * 640 // k < 16384:
+        k -= 1
+    return k
+
+
+def _edge_call(chunks, need, ns):
+    """(blocks, chunk count, stereo_head, stereo_tail) of a call whose LAST chunk holds `need` steps.
+    chunks 1: the serial engine, one chunk.  2: knob stereo_chunks = 2 with a two-block first chunk
+    (stereo_head 2, stereo_tail 64).  None: the default chunk count, two chunks at 52-76 blocks --
+    equal halves (the default head and tail) where a half holds `need`, else stereo_tail 64."""
+    if chunks == 1:
+        return -(-need // 640), 1, 8, 8
+    if chunks == 2:
+        for nb in range(66, 400):
+            if _chunk_begin(nb, 1, 2, 2, 64) >= 2 and (nb - _chunk_begin(nb, 1, 2, 2, 64)) * 640 >= need:
+                return nb, 2, 2, 64
+    for tail in (8, 64):
+        for nb in range(52, 77):
+            if _default_chunks(nb, ns) == 2 and (nb - _chunk_begin(nb, 1, 2, 8, tail)) * 640 >= need:
+                return nb, 2, 8, tail
+    raise AssertionError((chunks, need))
+
+
+@pytest.mark.parametrize("chunks", [1, 2, None])
+@pytest.mark.parametrize("edge,ni_front,ni_behind", _FORM_EDGES)
+def test_demote_once_across_form_edges(fmrx, monkeypatch, edge, ni_front, ni_behind, chunks):
+    """The demoted hand-off across one form boundary (2^18 .. 2^22, the stick hand-over at 2^24): 20
+    streams, 4 of them unlocked recipes, put at trigOffset edge - pre through the state blob, one
+    call.  The call's LAST chunk holds the edge: in front of it at least 64 intervals of the form
+    there (a launch of fewer never demotes) + 48 of the form behind it as margin (the unlocked
+    streams demote within ~30 intervals), behind it 32 intervals of the form there -- too few for
+    that launch to demote on its own, so a demoted step behind the edge was handed across it.
+      chunks 1: the serial engine, the call is that chunk (a demoted launch after every range).
+      chunks 2: knob stereo_chunks = 2, the pipelined engine (PllHint::demote_once: ONE demoted
+    launch a chunk; the launch behind the edge only adds its steps to state slot 6), the first
+    chunk two blocks (knobs stereo_head = 2, stereo_tail = 64).
+      chunks None: the default chunk count, which is two at this length (_default_chunks mirrors
+    api.cpp): equal halves, the first a chunk in which the streams demote too; for the 2^22 and
+    2^24 edges, whose last chunk needs more than a half, knob stereo_tail = 64.
+    The PCM of every stream and the whole PLL state (8 floats a stream: slot 6 cleared) equal the
+    same call on the plain certified launch (knob pll_spec = 0, which
+    test_pll_speculation_fallbacks pins to the oracle).  Every unlocked stream demoted in front of
+    the edge INSIDE the chunk that crosses it: its demoted steps exceed all the steps of the chunks
+    in front plus the steps behind the edge, which neither of those can supply alone."""
+    ns, bb = 20, 12800
+    behind = 32 * ni_behind
+    nb, K, head, tail = _edge_call(chunks, 64 * ni_front + 48 * ni_behind + behind, ns)
+    front = _chunk_begin(nb, K - 1, K, head, tail) * 640  # the steps of the chunks in front of the last
+    pre = nb * 640 - behind
+    assert pre - front >= 64 * ni_front and (K == 1 or front >= 2 * 640)
+    assert chunks is not None or _default_chunks(nb, ns) == K == 2
+    unlocked = {0: "rand:71", 7: "nopilot:72", 8: "noisy:73", 19: "rand:74"}
+    ins = np.stack([iqgen.make(unlocked.get(s, "synth:%d" % (780 + s)), (nb + 2) * bb) for s in range(ns)])
+    res = {}
+    for spec in (0, 1):
+        kw = {"pll_spec": spec, "stereo_head": head, "stereo_tail": tail}
+        if chunks is not None:
+            kw["stereo_chunks"] = chunks
+        knobs(monkeypatch, fmrx, **kw)
+        with fmrx.Receiver(0, fmrx.STEREO, n_streams=ns) as rx:
+            rx.process(ins[:, : 2 * bb])
+            _at_trig(rx, ns, edge - pre)
+            redos = torch.zeros((ns, fmrx.REDO_SLOTS), dtype=torch.int32, device="cuda")
+            counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+            rx.debug_pll_redos(redos.data_ptr())
+            rx.debug_pll_stats(counts.data_ptr())
+            out = rx.process(ins[:, 2 * bb:])
+            rx.debug_pll_redos(None)
+            rx.debug_pll_stats(None)
+            res[spec] = (out, _pll_rows(rx, ns).copy(), redos.cpu().numpy().astype(np.int64), counts.cpu().tolist())
+    (o0, st0, r0, c0), (o1, st1, r1, c1) = res[0], res[1]
+    assert c0 == [0, 0] and not r0.any()  # the plain launch: no runner ran
+    assert c1[1] > 0
+    assert np.array_equal(o1, o0), np.flatnonzero((o1 != o0).any(axis=1))
+    assert same(st1, st0), np.flatnonzero((bits(st1) != bits(st0)).any(axis=1))
+    dem = r1[:, 4:].sum(axis=1)
+    print("form edge %d chunks %s: %d blocks, %d steps in front chunks, %d behind, demoted %s"
+          % (edge, chunks, nb, front, behind, [int(dem[s]) for s in unlocked]))
+    for s in unlocked:
+        assert dem[s] > front + behind, (s, dem.tolist(), front, behind)
+
+
+@pytest.mark.parametrize("name,hop", [("unlocked_m0_noisy_80s", None), ("unlocked_m0_nopilot_80s", 3),
+                                      ("unlocked_m0_rand_80s", None)])
+def test_unlocked_seam_calls(fmrx, name, hop):
+    """test_seam_calls_in_every_pll_regime's cutting on streams whose loop never locks: long fused
+    calls, between them runs of 1-block fmrx_rf_block + fmrx_audio_block calls (640 steps: fewer than
+    kPllDemoteMinIntervals intervals, never demoted, nearly every interval redone) and 2-9-block
+    fused calls (1,280-5,760 steps: demoted with a few hundred steps left; the next call starts from
+    the state pll_demoted_kernel wrote) at trigOffsets 2^17.., 2^19.., 2^20.., 2^21.., 2^22.. and
+    the stick.  hop: inside that run, after its first call (one block through rf_block + audio_block,
+    never demoted) and before the 2-block call, the state goes through get_state into a new context.
+    The whole PCM and the final PLL state against the reference build's."""
+    h = unlocked_runs()[name]
+    bb, nb = oracle.MODES[0][0], h["n_blocks"]
+    iq = _recipe_bytes(h["recipe"], nb * bb)
+    assert sha(iq) == h["input_sha256"]
+    runs = [(210, 12), (900, 12), (1700, 12), (3400, 12), (7000, 12), (26300, 12)]
+    sizes = [1, 2, 3, 5, 6, 7, 9]
+    parts, b = [], 0
+    rx = fmrx.Receiver(0, fmrx.STEREO, rf_taps=h["rf_taps"])
+    try:
+        redos = torch.zeros(fmrx.REDO_SLOTS, dtype=torch.int32, device="cuda")
+        for r, (start, count) in enumerate(runs):
+            parts.append(rx.process(iq[b * bb:start * bb]))
+            b = start
+            rx.debug_pll_redos(redos.data_ptr())  # the short calls' demoted steps only
+            for k in range(count):
+                m = sizes[k % len(sizes)]
+                chunk = iq[b * bb:(b + m) * bb]
+                parts.append(rx.audio_block(rx.rf_block(chunk)) if m == 1 else rx.process(chunk))
+                b += m
+                if r == hop and k == 0:
+                    blob = rx.get_state()
+                    rx.close()
+                    rx = fmrx.Receiver(0, fmrx.STEREO, rf_taps=h["rf_taps"])
+                    rx.set_state(blob)
+                    rx.debug_pll_redos(redos.data_ptr())
+            rx.debug_pll_redos(None)
+        parts.append(rx.process(iq[b * bb:]))
+        assert same(_pll_floats(rx), np.asarray(h["pll_state_last"], np.float32))
+    finally:
+        rx.close()
+    _RECIPE_CACHE.clear()  # (the module's last user of the random bytes)
+    assert sha(np.concatenate(parts)) == h["pcm_sha256"]
+    assert redos.cpu().numpy()[4:].sum() > 0, redos.cpu().numpy()
+
+
+def test_unlocked_seam_calls_mode2(fmrx):
+    """Mode 2's PLL (handed the upsampled if_fs, project.cpp:166,348: never locked) across calls of
+    1, 2, 3, ... blocks: a block is 102,400 steps there, so every call demotes and the next starts
+    from the demoted kernel's state.  The whole PCM and the final PLL state against the reference
+    build's."""
+    h = unlocked_runs()["unlocked_m2_synth_170b"]
+    bb, rf_fs = oracle.MODES[2][0], oracle.MODES[2][3]
+    nb = h["n_blocks"]
+    iq = iqgen.make(h["recipe"], nb * bb, rf_fs)
+    parts, b, m = [], 0, 1
+    with fmrx.Receiver(2, fmrx.STEREO, rf_taps=h["rf_taps"]) as rx:
+        redos = torch.zeros(fmrx.REDO_SLOTS, dtype=torch.int32, device="cuda")
+        rx.debug_pll_redos(redos.data_ptr())
+        while b < nb:
+            m = min(m, nb - b)
+            parts.append(rx.process(iq[b * bb:(b + m) * bb]))
+            b, m = b + m, m + 1
+        rx.debug_pll_redos(None)
+        assert same(_pll_floats(rx), np.asarray(h["pll_state_last"], np.float32))
+    assert sha(np.concatenate(parts)) == h["pcm_sha256"]
+    assert redos.cpu().numpy()[4:].sum() > nb * 102400 // 2, redos.cpu().numpy()
+
+
+def _pll_call(fmrx, rx, x, st0):
+    """fmrx_pll on one stream: (output, state, demoted steps, (resumed, checked))."""
+    buf, st = _d(x), _d(st0)
+    redos = torch.zeros(fmrx.REDO_SLOTS, dtype=torch.int32, device="cuda")
+    counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+    rx.debug_pll_redos(redos.data_ptr())
+    rx.debug_pll_stats(counts.data_ptr())
+    torch.cuda.synchronize()
+    rx.pll(buf.data_ptr(), x.size, 19000, 240000, 2.0, 0.0, 0.01, st.data_ptr())
+    rx.synchronize()
+    rx.debug_pll_redos(None)
+    rx.debug_pll_stats(None)
+    return buf.cpu().numpy(), st.cpu().numpy(), int(redos.cpu().numpy()[4:].sum()), counts.cpu().tolist()
+
+
+# steps left to the demoted kernel: the round numbers' neighbours, and (fmrx_pll speculates only on
+# rows of a multiple of 4 floats) their neighbours that are multiples of 4
+_DEM_M = [1, 15, 16, 17, 255, 256, 257, 511, 512, 513, 773, 4, 12, 20, 252, 260, 508, 516, 528, 772, 1028, 1300]
+
+
+@pytest.mark.parametrize("inject", [None, 0])
+@pytest.mark.parametrize("trig0,ni", [(300000.0, 16), (700000.0, 64)])
+def test_pll_demoted_small_shapes(fmrx, orc, monkeypatch, trig0, ni, inject):
+    """pll_demoted_kernel's small and odd shapes: with m steps left to it, nbt = m / 16 whole batches
+    in sub-segments of 16 -- nbt = 1 (the inject hook has no batch to corrupt), 1, 2 and 3
+    sub-segments (the prologue's second side order, the ring of four side slots), a partial last
+    sub-segment, m % 16 != 0 (the exact tail).  fmrx_pll on one stream whose every interval from 59
+    on misses (knob pll_pipe_miss = -60) in the 16-step index form [2^18, 2^19) and the 64-step
+    count form [2^19, 2^20): a first call finds the step jd at which the runner leaves (a whole
+    number of intervals), then n = jd + m for m in 1, 15, 16, 17, 255, 256, 257, 511, 512, 513, 773
+    and 4, 12, 20, 252, 260, 508, 516, 528, 772, 1028, 1300.  Output and state against the oracle
+    for every one, and the m the kernel got read back from the redo counters.
+      What reaches the kernel:
+      * fmrx_pll speculates only on a row of a multiple of 4 floats (launch_pll: stride % 4), so the
+        other n -- m = 1, 15, 17, 255, 257, 511, 513, 773 -- run on the plain certified launch, no
+        runner and no demotion (checked == 0); their multiple-of-4 neighbours stand in for them:
+        20 (nbt = 1 with an exact tail), 252 / 260, 508 / 516 (one / two / three sub-segments'
+        edges with a tail), 528 (a last sub-segment of one batch), 772, 1028 and 1300 (four and six
+        sub-segments: the ring of four side slots wraps);
+      * a runner leaves only while a whole interval is still ahead (dem_i < ni, pll_pred.hip), so m
+        below an interval (4, 12; 16 and 20 too in the 64-step form) runs undemoted: nbt = 0 cannot
+        be reached through the library;
+      * launch_pll gives a 64-step form's tail of >= 48 steps to a 16-step launch of its own, so
+        252 and 508 arrive as 192 and 448 there.
+    The sets asserted below are what is left; they would shrink if one of these rules changed.
+      pll_inject = 0: one batch of the chain is corrupted and rolled back ("resumed" above an
+    undemoted speculative call's count, m = 4) -- except with nbt = 1, where the hook is a no-op."""
+    knobs(monkeypatch, fmrx, pll_pipe_miss=-60)
+    if inject is not None:
+        knobs(monkeypatch, fmrx, pll_inject=inject)
+    n_max = 16384
+    rng = np.random.default_rng(ni)
+    t = np.arange(n_max)
+    x = (0.1 * np.cos(2 * np.pi * 19000 / 240000 * t + 0.3) + 0.02 * rng.standard_normal(n_max)).astype(np.float32)
+    st0 = np.array([1e-4, 0.4, 0.6, 0.8, 1.0, trig0], np.float32)
+    want_x, _ = orc.pll(x, 19000, 240000, 2.0, 0.0, 0.01, st0)  # (a prefix's output is the prefix)
+    n_probe = 128 * ni
+    produced, resumed = {}, {}
+    with fmrx.Receiver(0, fmrx.STEREO) as rx:
+        _, _, m_probe, _ = _pll_call(fmrx, rx, x[:n_probe], st0)
+        assert 0 < m_probe < n_probe, m_probe
+        jd = n_probe - m_probe
+        assert jd % ni == 0 and jd + max(_DEM_M) <= n_max, jd
+        for m in _DEM_M:
+            n = jd + m
+            got_x, got_st, produced[m], (resumed[m], checked) = _pll_call(fmrx, rx, x[:n], st0)
+            _, want_st = orc.pll(x[:n], 19000, 240000, 2.0, 0.0, 0.01, st0)
+            assert same(got_x, want_x[:n]), (m, np.flatnonzero(bits(got_x) != bits(want_x[:n]))[:4])
+            assert same(got_st, want_st), (m, got_st, want_st)
+            assert (checked > 0) == (n % 4 == 0), (m, checked)
+    print("demoted shapes trig0 %d: jd %d, m asked -> got %s, resumed %s" % (trig0, jd, produced, resumed))
+    if ni == 16:
+        assert set(produced.values()) >= {16, 20, 252, 256, 260, 508, 512, 516, 528, 772, 1028, 1300}, produced
+    else:
+        assert set(produced.values()) >= {192, 256, 260, 448, 512, 516, 528, 772, 1028, 1300}, produced
+    assert produced[4] == 0 and min(v for v in produced.values() if v) >= ni, produced
+    if inject is not None:
+        for m, got in produced.items():
+            if m % 4:
+                assert resumed[m] == 0, (m, resumed)
+            elif got // 16 > 1:
+                assert resumed[m] > resumed[4], (m, resumed)
+            else:
+                assert resumed[m] == resumed[4], (m, resumed)
+
+
+def _special_input(case, n, first):
+    """A clean pilot with special samples from index `first` on (test_pll_demoted_special_values)."""
+    rng = np.random.default_rng(77)
+    t = np.arange(n)
+    x = (0.1 * np.cos(2 * np.pi * 19000 / 240000 * t + 0.3) + 0.02 * rng.standard_normal(n)).astype(np.float32)
+    a = first
+    x[a: a + 40] = 0.0          # a run of exact zeros longer than two batches
+    x[a + 100] = 0.0            # isolated zeros, either sign
+    x[a + 150] = -0.0
+    x[a + 200: a + 204] = [1e-30, -1e-30, 1e30, -1e30]  # (1e-30: just above kPllMinV = 2^-100 = 7.9e-31)
+    x[a + 204: a + 206] = [5e-31, -5e-31]               # just below it
+    x[a + 300: a + 400] = 0.1 * (-1.0) ** np.arange(100)  # +0.1, -0.1, ...: the sign alternates every step
+    x[a + 500] = 1e-38          # the smallest normals' neighbourhood, a denormal
+    x[a + 501] = -1e-41
+    x[a + 600] = 3.0e38
+    if case == "inf":
+        x[a + 700] = np.inf
+        x[a + 800] = -np.inf
+    if case == "nan":
+        x[a + 700] = np.nan
+    return x
+
+
+@pytest.mark.parametrize("case", ["finite", "inf", "nan"])
+@pytest.mark.parametrize("trig0", [300000.0, 700000.0])
+def test_pll_demoted_special_values(fmrx, orc, monkeypatch, trig0, case):
+    """Special input values on a demoted stream (dem_iv gives NaN for |v| < kPllMinV and for |v| >=
+    1e300: the chain's batch fails its check and is redone exactly): fmrx_pll on 4,800 steps, every
+    interval from 9 on missed (knob pll_pipe_miss = -10; the 16-step index form and the 64-step
+    count form, which needs 4,096 steps to demote), and from step 2,800 on -- behind the step at
+    which the runner leaves, asserted -- a run of 40 exact zeros, isolated +0.0 and -0.0, +-1e-30
+    and +-5e-31 (either side of kPllMinV), +-1e30, 100 samples alternating in sign, a tiny normal,
+    a denormal, 3e38; `inf` adds +inf and -inf, `nan` a NaN.
+    Output and state against the oracle, bit for bit.  On the CPU the oracle's state stays finite
+    in `finite` and in `inf` (atan2 of two infinities is a finite angle; asserted below) and is NaN
+    from the NaN sample on in `nan` (the quiet NaN's own bits, carried by every operation)."""
+    knobs(monkeypatch, fmrx, pll_pipe_miss=-10)
+    n, first = 4800, 2800
+    x = _special_input(case, n, first)
+    st0 = np.array([1e-4, 0.4, 0.6, 0.8, 1.0, trig0], np.float32)
+    want_x, want_st = orc.pll(x, 19000, 240000, 2.0, 0.0, 0.01, st0)
+    if case == "nan":
+        assert np.isnan(want_st[:5]).all() and np.isfinite(want_x[: first + 700]).all()
+    else:
+        assert np.isfinite(want_st).all() and np.isfinite(want_x).all()
+    with fmrx.Receiver(0, fmrx.STEREO) as rx:
+        got_x, got_st, m, _ = _pll_call(fmrx, rx, x, st0)
+    print("special values trig0 %d %s: %d steps demoted" % (trig0, case, m))
+    assert m >= n - first, m  # the kernel under test ran every special sample
+    assert same(got_x, want_x), np.flatnonzero(bits(got_x) != bits(want_x))[:4]
+    assert same(got_st, want_st), (got_st, want_st)
 
 
 def test_quantize_and_elementwise(fmrx, orc):

@@ -88,6 +88,32 @@ def test_oracle_matches_unlocked_hashes(orc, name):
     assert np.array_equal(bits(out["pll_state"][-6:]), bits(np.asarray(h["pll_state_last"], np.float32)))
 
 
+def test_unlocked_stream_fixtures_load():
+    """hashes.json unlocked_c4_* (the unlocked streams the many-stream GPU tests run among the
+    locked streams of streams_c4_60s): one of each unlocked recipe and a second noisy id, the
+    configs[4] shape, the fields of the other unlocked_* entries, inside unlocked_runs() too."""
+    runs = iqgen.unlocked_stream_runs()
+    kinds = sorted(h["recipe"].partition(":")[0] for h in runs.values())
+    assert kinds == ["noisy", "noisy", "nopilot", "rand"], kinds
+    assert len({h["recipe"] for h in runs.values()}) == 4
+    locked = iqgen.stream_hashes(256, 22500)
+    assert len(locked) == 256
+    for name, h in runs.items():
+        assert (h["mode"], h["rf_taps"], h["n_blocks"]) == (0, 51, 22500), name
+        assert len(h["pcm_sha256"]) == 64 and len(h["input_sha256"]) == 64 and len(h["pll_state_last"]) == 6
+        assert h["pll_state_last"][5] == 22500 * 640  # the trigOffset: one step a sample, below the stick
+        assert h["pcm_sha256"] not in locked.values()
+        assert unlocked_runs()[name] == h
+
+
+@pytest.mark.parametrize("name", sorted(iqgen.unlocked_stream_runs()))
+def test_unlocked_stream_fixture_inputs(name):
+    """iqgen.make reproduces each new fixture's input bytes."""
+    h = iqgen.unlocked_stream_runs()[name]
+    iq = iqgen.make(h["recipe"], h["n_blocks"] * oracle.MODES[0][0], oracle.MODES[0][3])
+    assert sha(iq) == h["input_sha256"]
+
+
 def test_const128_is_silence(orc):
     out = orc.run(0, 51, np.full(12800 * 3, 128, np.uint8), ["pcm", "pcm_mono", "demod"])
     assert not out["pcm"].any() and not out["pcm_mono"].any() and not out["demod"].any()
