@@ -128,6 +128,35 @@ void* fmrx_stream(fmrx_ctx* ctx);                       /* the hipStream_t used 
  * clear and disarm; 0: just read.                                                         */
 int fmrx_kernel_timing(fmrx_ctx* ctx, int reset, double* avg_ms, long* launches);
 
+/* ---- off-centre tuning: several stations from one capture -------------------------------- */
+/* A stream tuned to offset f Hz (integer, |f| < rf_fs/2) rotates its normalised I/Q pair n (the
+ * absolute pair index of the stream) by e^(-j 2 pi f n / rf_fs) in front of the RF low-pass, so a
+ * station at +f of the capture lands on 0 Hz; the rest of the chain is unchanged.  Arithmetic
+ * (csrc/tuner.hip): N = rf_fs / gcd(|f|, rf_fs), k = (f / gcd) mod N, p = (k n) mod N,
+ * I' = fl(fl(x_i c[p]) + fl(x_q s[p])), Q' = fl(fl(x_q c[p]) - fl(x_i s[p])) with the table below.
+ * fmrx_tuner_design is host only, like fmrx_impulse_response_lpf: N, k and (cos_sin may be NULL)
+ * the 2N floats c[0],s[0],c[1],s[1],..., c[p] = (float)cos(2 pi p / N), s[p] = (float)sin(2 pi p
+ * / N) in double.  FMRX_EINVAL for |f| >= rf_fs/2 and for N > 4096 (any multiple of 1 kHz is
+ * accepted in all four modes; cos_sin holds at most 8192 floats).                             */
+int fmrx_tuner_design(int rf_fs, int offset_hz, int* N, int* k, float* cos_sin);
+/* offsets_hz: n_streams ints, or NULL = tuning off (the untuned kernels run, exactly as today).
+ * first_pair: absolute pair index of the next call's first I/Q pair (all streams).  Does not touch
+ * filter/PLL/audio state.  A non-NULL array of zeros still takes the tuned front end.  While
+ * tuning is on, fmrx_process, fmrx_process_device(_ex), fmrx_rf_block and the shared forms below
+ * run the tuned front end, then the audio stage fmrx_audio_block runs (stereo contexts: the
+ * non-pipelined engine), and advance the position by n_blocks * iq_pairs.  fmrx_reset keeps the
+ * offsets and rewinds the position to 0.  Tuning is configuration, not state: the fmrx_get_state
+ * blob does not hold it; a checkpoint is restored by fmrx_set_state plus fmrx_tune(..., first_pair)
+ * with the position fmrx_tuner_info gave, and a time shard by fmrx_seek plus the same.
+ * FMRX_EINVAL (nothing changed): an offset fmrx_tuner_design refuses.                          */
+int fmrx_tune(fmrx_ctx* ctx, const int32_t* offsets_hz, uint64_t first_pair);
+/* read back: offsets (n_streams, may be NULL), next pair index, 1/0 tuned (each may be NULL)  */
+int fmrx_tuner_info(fmrx_ctx* ctx, int32_t* offsets_hz, uint64_t* next_pair, int* enabled);
+/* one capture for every stream: iq is ONE stream's n_blocks*block_bytes, read by all n_streams
+ * (each with its own offset); pcm as fmrx_process.  Tuning must be on (FMRX_ESTATE otherwise). */
+int fmrx_process_shared(fmrx_ctx* ctx, const uint8_t* iq, size_t n_blocks, int16_t* pcm);
+int fmrx_process_shared_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

@@ -17,6 +17,7 @@
 #include "../../include/fmrx.h"
 #include "fmrx_internal.h"
 #include "synth.h"
+#include "tuner.h"
 
 using namespace fmrx;
 
@@ -164,6 +165,13 @@ struct fmrx_ctx {
     hipStream_t s_front = nullptr, s_audio = nullptr;
     std::vector<hipEvent_t> pipe_ev;
     int n_simd = 1024;                        // SIMDs of cfg.device (4 per CU), set at creation
+    // off-centre tuning (fmrx_tune): configuration, not part of the state blob
+    bool tuned = false;
+    std::vector<int32_t> tune_offsets;        // n_streams (zeros until fmrx_tune sets them)
+    uint64_t tune_pos = 0;                    // absolute pair index of the next call's first I/Q pair
+    int tune_max_n = 1;                       // the longest rotator period among the streams
+    DevBuf<float> d_tune_tab;                 // the streams' (c, s) tables, one after the other
+    DevBuf<uint32_t> d_tune_streams;          // TunerStream per stream
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -239,6 +247,7 @@ int reset_state(fmrx_ctx* c) {
     const int ns = c->cfg.n_streams;
     c->pll_trig = fmrx_ctx::TrigTrack{};
     c->rds_trig = fmrx_ctx::TrigTrack{};
+    c->tune_pos = 0;  // the offsets stay (configuration)
     HIPCHK(hipMemsetAsync(c->d_halo[0].p, 0x80, c->halo_bytes * ns, c->stream));
     HIPCHK(hipMemsetAsync(c->d_halo[1].p, 0x80, c->halo_bytes * ns, c->stream));
     c->halo_cur = 0;
@@ -783,6 +792,66 @@ int ensure_demod(fmrx_ctx* c, size_t n_if) {
     return 0;
 }
 
+// The tuned front end (tuner.hip) over n_blocks blocks a stream: demod rows out, the halo moved,
+// the position advanced.  iq_stride: bytes between the streams' rows, 0 for a shared capture.
+// pre_tail: also the 50 demod samples in front of the call (at demod_hist - 50, from the halo).
+int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,
+                    size_t demod_stride, int demod_hist, bool pre_tail) {
+    const int ns = c->cfg.n_streams;
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 3) != 0 || iq_stride % 4 != 0)
+        return fail(FMRX_EINVAL, "tuned calls need 4-byte aligned I/Q rows");
+    TunerLaunch L{};
+    L.iq = d_iq;
+    L.iq_stride = iq_stride;
+    L.halo = c->d_halo[c->halo_cur].p;
+    L.halo_next = c->d_halo[c->halo_cur ^ 1].p;
+    L.halo_bytes = c->halo_bytes;
+    L.stream_bytes = n_blocks * c->geo.block_bytes;
+    L.demod = d_demod;
+    L.demod_stride = demod_stride;
+    L.demod_hist = demod_hist;
+    L.pre_tail = pre_tail ? 1 : 0;
+    L.n_if = (long long)(n_blocks * c->geo.if_samples);
+    L.segs = tuner_segments(L.n_if, c->geo.rf_taps, c->geo.rf_decim, ns, c->n_simd / 4, c->tune_max_n);
+    L.streams = reinterpret_cast<const TunerStream*>(c->d_tune_streams.p);
+    L.tables = reinterpret_cast<const float2*>(c->d_tune_tab.p);
+    L.first_pair = c->tune_pos;
+    const int st_t = c->stage_timer.begin(c->stream);
+    const int rc = launch_tuner(L, ns, c->geo.rf_taps, c->geo.rf_decim, c->tune_max_n, c->mono_taps, c->stream);
+    c->stage_timer.end(st_t, kStFront, 0.0, c->stream);
+    if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "tuned front end launch failed (%d)", rc);
+    c->halo_cur ^= 1;
+    c->tune_pos += (uint64_t)n_blocks * c->geo.iq_pairs;
+    return 0;
+}
+
+// A tuned call: the front end for the whole call into the context's demod rows, then the audio
+// stage fmrx_audio_block runs (mono: the polyphase stage; stereo: the non-pipelined engine).
+int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
+    const int ns = c->cfg.n_streams;
+    const size_t n_if = n_blocks * c->geo.if_samples;
+    int rc = ensure_demod(c, n_if);
+    if (rc) return rc;
+    if (c->cfg.channels != FMRX_MONO) {
+        if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, false)))
+            return rc;
+        return run_stereo_audio(c, n_blocks, d_pcm, d_mono);
+    }
+    // after fmrx_seek the audio history is rebuilt from the halo, as the fused kernel's pre-roll
+    // does: the 50 demod samples in front of the call (all a resampler output reads back)
+    const bool stale = c->audio_hist_stale;
+    if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, stale)))
+        return rc;
+    if (stale) {
+        if (launch_copy_streams(c->d_audio_hist.p + (c->audio_hist - kAudioHist50), c->audio_hist,
+                                c->d_demod.p + (kDemodHist - kAudioHist50), c->demod_stride, kAudioHist50, ns,
+                                c->stream))
+            return fail(FMRX_EHIP, "audio history copy failed");
+        c->audio_hist_stale = false;
+    }
+    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1017,6 +1086,7 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
         if (hipMemcpy(c->d_audio_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice) != hipSuccess)
             return cleanup(fail(FMRX_EHIP, "tap upload failed"));
     }
+    c->tune_offsets.assign((size_t)ns, 0);
     if ((rc = reset_state(c))) return cleanup(rc);
     *out = c;
     return FMRX_OK;
@@ -1034,6 +1104,7 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_pll_side.release(); c->d_pll_side2.release();
     c->d_rds_taps.release(); c->d_rds_dhist.release(); c->d_rds_chan.release(); c->d_rds_car.release();
     c->d_rds_pll.release();
+    c->d_tune_tab.release(); c->d_tune_streams.release();
     for (auto& e : c->evs) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -1200,6 +1271,7 @@ int fmrx_process_device_ex(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, in
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
+    if (c->tuned) return run_tuned(c, d_iq, n_blocks * c->geo.block_bytes, n_blocks, d_pcm, d_mono);
     const size_t n_if = n_blocks * c->geo.if_samples;
     if (c->cfg.channels == FMRX_MONO)  // every mode: RF + demod + audio resampler in one launch
         return run_fused(c, d_iq, n_blocks, d_pcm, d_mono, nullptr, 0, 0, true);
@@ -1214,6 +1286,72 @@ int fmrx_process_device_ex(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, in
 
 int fmrx_process_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
     return fmrx_process_device_ex(c, d_iq, n_blocks, d_pcm, nullptr);
+}
+
+int fmrx_process_shared_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    CtxLock lock_(c);
+    if (!c || !d_iq || !d_pcm) return fail(FMRX_EINVAL, "null argument");
+    if (!c->tuned) return fail(FMRX_ESTATE, "fmrx_process_shared_device: tuning is off (fmrx_tune first)");
+    if (n_blocks == 0) return FMRX_OK;
+    int rc = set_device(c);
+    if (rc) return rc;
+    return run_tuned(c, d_iq, 0, n_blocks, d_pcm, nullptr);
+}
+
+// ---- off-centre tuning ----------------------------------------------------------------------
+int fmrx_tuner_design(int rf_fs, int offset_hz, int* N, int* k, float* cos_sin) {
+    int why = 0;
+    if (tuner_design(rf_fs, offset_hz, N, k, cos_sin, &why)) return FMRX_OK;
+    if (why == 2)
+        return fail(FMRX_EINVAL, "offset %d Hz at %d S/s: rotator period above %d pairs (use a multiple of 1 kHz)",
+                    offset_hz, rf_fs, kTunerMaxN);
+    return fail(FMRX_EINVAL, "offset %d Hz outside (-%d/2, %d/2)", offset_hz, rf_fs, rf_fs);
+}
+
+int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (!offsets_hz) {  // tuning off: the untuned kernels, exactly as before
+        c->tuned = false;
+        c->tune_pos = first_pair;
+        return FMRX_OK;
+    }
+    if (!tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d", c->geo.rf_taps, c->geo.rf_decim);
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t ns = c->cfg.n_streams;
+    std::vector<TunerStream> ts(ns);
+    size_t entries = 0;
+    int max_n = 1;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int N = 0, k = 0;
+        if ((rc = fmrx_tuner_design(c->geo.rf_fs, offsets_hz[s], &N, &k, nullptr))) return rc;
+        ts[s] = TunerStream{(uint32_t)N, (uint32_t)k, (uint32_t)entries, 0u};
+        entries += (size_t)N;
+        max_n = std::max(max_n, N);
+    }
+    std::vector<float> tab(2 * entries);
+    for (size_t s = 0; s < ns; s++) tuner_design(c->geo.rf_fs, offsets_hz[s], nullptr, nullptr, tab.data() + 2 * ts[s].tab);
+    // a call in flight may still read the old tables: drain the stream before they are replaced
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = c->d_tune_tab.ensure(tab.size())) || (rc = c->d_tune_streams.ensure(4 * ns))) return rc;
+    HIPCHK(hipMemcpy(c->d_tune_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_tune_streams.p, ts.data(), sizeof(TunerStream) * ns, hipMemcpyHostToDevice));
+    c->tune_offsets.assign(offsets_hz, offsets_hz + ns);
+    c->tune_max_n = max_n;
+    c->tune_pos = first_pair;
+    c->tuned = true;
+    return FMRX_OK;
+}
+
+int fmrx_tuner_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (offsets_hz) std::copy(c->tune_offsets.begin(), c->tune_offsets.end(), offsets_hz);
+    if (next_pair) *next_pair = c->tune_pos;
+    if (enabled) *enabled = c->tuned ? 1 : 0;
+    return FMRX_OK;
 }
 
 int fmrx_synchronize(fmrx_ctx* c) {
@@ -1275,14 +1413,17 @@ int wait_small(fmrx_ctx* c) {
     return FMRX_OK;
 }
 
-int fmrx_process(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) {
+// shared (fmrx_process_shared): iq is one stream's bytes, read by every (tuned) stream
+static int process_host(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm, bool shared) {
     CtxLock lock_(c);
     if (!c || !iq || !pcm) return fail(FMRX_EINVAL, "null argument");
+    if (shared && !c->tuned) return fail(FMRX_ESTATE, "fmrx_process_shared: tuning is off (fmrx_tune first)");
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
     const size_t ns = c->cfg.n_streams;
-    const size_t in_bytes = ns * n_blocks * c->geo.block_bytes;
+    const size_t in_bytes = (shared ? 1 : ns) * n_blocks * c->geo.block_bytes;
+    auto on_device = shared ? fmrx_process_shared_device : fmrx_process_device;
     const size_t out_n = ns * n_blocks * c->geo.pcm_samples;
     if (in_bytes <= kPinnedCallBytes) {  // pinned staging: the input by DMA, the PCM written in place
         if ((rc = c->h_in.ensure(in_bytes)) || (rc = c->h_out.ensure(out_n * sizeof(int16_t))) ||
@@ -1290,17 +1431,25 @@ int fmrx_process(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) 
             return rc;
         std::memcpy(c->h_in.p, iq, in_bytes);
         HIPCHK(hipMemcpyAsync(c->d_in.p, c->h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
-        if ((rc = fmrx_process_device(c, c->d_in.p, n_blocks, reinterpret_cast<int16_t*>(c->h_out.p)))) return rc;
+        if ((rc = on_device(c, c->d_in.p, n_blocks, reinterpret_cast<int16_t*>(c->h_out.p)))) return rc;
         if ((rc = wait_small(c))) return rc;
         std::memcpy(pcm, c->h_out.p, out_n * sizeof(int16_t));
         return FMRX_OK;
     }
     if ((rc = c->d_in.ensure(in_bytes)) || (rc = c->d_out.ensure(out_n))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_in.p, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = fmrx_process_device(c, c->d_in.p, n_blocks, c->d_out.p))) return rc;
+    if ((rc = on_device(c, c->d_in.p, n_blocks, c->d_out.p))) return rc;
     HIPCHK(hipMemcpyAsync(pcm, c->d_out.p, out_n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return FMRX_OK;
+}
+
+int fmrx_process(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) {
+    return process_host(c, iq, n_blocks, pcm, false);
+}
+
+int fmrx_process_shared(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) {
+    return process_host(c, iq, n_blocks, pcm, true);
 }
 
 // rf_thread body (project.cpp:48-70): u8 blocks -> demod floats.
@@ -1321,14 +1470,18 @@ int fmrx_rf_block(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, float* demod)
         std::memcpy(c->h_in.p, iq, in_bytes);
         HIPCHK(hipMemcpyAsync(c->d_in.p, c->h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
         float* h_demod = reinterpret_cast<float*>(c->h_out.p);
-        if ((rc = run_fused(c, c->d_in.p, n_blocks, nullptr, nullptr, h_demod, n_if, 0, false))) return rc;
+        if ((rc = c->tuned ? run_tuned_front(c, c->d_in.p, n_blocks * c->geo.block_bytes, n_blocks, h_demod, n_if, 0, false)
+                           : run_fused(c, c->d_in.p, n_blocks, nullptr, nullptr, h_demod, n_if, 0, false)))
+            return rc;
         if ((rc = wait_small(c))) return rc;
         std::memcpy(demod, h_demod, sizeof(float) * ns * n_if);
         return FMRX_OK;
     }
     if ((rc = c->d_in.ensure(in_bytes)) || (rc = c->d_f32.ensure(ns * n_if))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_in.p, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_fused(c, c->d_in.p, n_blocks, nullptr, nullptr, c->d_f32.p, n_if, 0, false))) return rc;
+    if ((rc = c->tuned ? run_tuned_front(c, c->d_in.p, n_blocks * c->geo.block_bytes, n_blocks, c->d_f32.p, n_if, 0, false)
+                       : run_fused(c, c->d_in.p, n_blocks, nullptr, nullptr, c->d_f32.p, n_if, 0, false)))
+        return rc;
     HIPCHK(hipMemcpyAsync(demod, c->d_f32.p, sizeof(float) * ns * n_if, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return FMRX_OK;

@@ -1,4 +1,5 @@
-// cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]`:
+// cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
+// [--offset-hz F]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -8,7 +9,9 @@
 //     `channels` is only logged (:301-302), the reference has no mono-only output;
 //   * --mono-product (an fmrx extension, not a project argument) writes the 1-channel mono
 //     product instead (project.cpp:146's mono resample with a private history, quantised like
-//     :187) -- the BASELINE headline path.
+//     :187) -- the BASELINE headline path;
+//   * --offset-hz F (an fmrx extension) decodes the station F Hz off the capture's centre
+//     (fmrx_tune: the I/Q is rotated by -F in front of the RF low-pass); the same loop otherwise.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -76,7 +79,7 @@ void usage(const char* argv0) {
     std::fprintf(stderr,
                  "Usage: %s\nor \nUsage %s <mode> <channels>\n"
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
-                 "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product]\n",
+                 "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n",
                  argv0, argv0);
 }
 
@@ -96,13 +99,18 @@ void usage(const char* argv0) {
 
 int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false;
+    bool mono_product = false, tuned = false;
+    long offset_hz = 0;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--rf-taps") && i + 1 < argc) rf_taps = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
+        else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) {
+            offset_hz = std::atol(argv[++i]);
+            tuned = true;
+        }
         else if (argv[i][0] == '-' && argv[i][1] != '\0' && !(argv[i][1] >= '0' && argv[i][1] <= '9')) {
             usage(argv[0]);
             return 1;
@@ -136,6 +144,15 @@ int main(int argc, char** argv) {
     if (fmrx_geometry(&cfg, &geo) != FMRX_OK || fmrx_create(&cfg, &ctx) != FMRX_OK) {
         std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
         return 1;
+    }
+    if (tuned) {  // out of range (or no 32-bit value) -> message, exit 1
+        const int32_t f = (int32_t)offset_hz;
+        if ((long)f != offset_hz || fmrx_tune(ctx, &f, 0) != FMRX_OK) {
+            std::fprintf(stderr, "fmrx: --offset-hz %ld: %s\n", offset_hz,
+                         (long)f != offset_hz ? "out of range" : fmrx_last_error());
+            fmrx_destroy(ctx);
+            return 1;
+        }
     }
     const size_t in_cap = geo.block_bytes * (size_t)batch;
     const size_t out_cap = geo.pcm_samples * (size_t)batch;

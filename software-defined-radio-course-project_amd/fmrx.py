@@ -69,6 +69,11 @@ PROTOTYPES = {
     "fmrx_psd_device": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_float, _vp]),
     "fmrx_process_device": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_process_device_ex": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "fmrx_tuner_design": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
+    "fmrx_tune": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "fmrx_tuner_info": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "fmrx_process_shared": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_process_shared_device": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -172,6 +177,16 @@ def bpf(fs: float, fb: float, fe: float, taps: int) -> np.ndarray:
     h = np.zeros(taps, np.float32)
     _check(lib().fmrx_impulse_response_bpf(h.ctypes.data_as(_fp), fs, fb, fe, taps))
     return h
+
+
+def tuner_design(rf_fs: int, offset_hz: int) -> tuple[int, int, np.ndarray]:
+    """Rotator of a stream tuned to offset_hz (fmrx_tuner_design): (N, k, table), table[p] =
+    (c[p], s[p]) as float32, shape (N, 2); pair n of the stream takes entry (k n) mod N."""
+    n, k = C.c_int(), C.c_int()
+    _check(lib().fmrx_tuner_design(rf_fs, offset_hz, C.byref(n), C.byref(k), None))
+    tab = np.zeros((n.value, 2), np.float32)
+    _check(lib().fmrx_tuner_design(rf_fs, offset_hz, C.byref(n), C.byref(k), _np_ptr(tab)))
+    return n.value, k.value, tab
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:
@@ -300,6 +315,41 @@ class Receiver:
     # ---- device entry points (pointers are device addresses)
     def process_device(self, d_iq: int, n_blocks: int, d_pcm: int, d_mono: int | None = None) -> None:
         _check(lib().fmrx_process_device_ex(self.h, d_iq, n_blocks, d_pcm, d_mono))
+
+    # ---- off-centre tuning (several stations from one capture)
+    def tune(self, offsets, first_pair: int = 0) -> None:
+        """fmrx_tune: per-stream offsets in Hz (an int for one stream), or None for tuning off;
+        first_pair is the absolute pair index of the next call's first I/Q pair."""
+        if offsets is None:
+            _check(lib().fmrx_tune(self.h, None, first_pair))
+            return
+        off = np.ascontiguousarray(np.atleast_1d(np.asarray(offsets, dtype=np.int64)))
+        if off.size != self.n_streams:
+            raise ValueError(f"{off.size} offsets for {self.n_streams} streams")
+        if np.any(np.abs(off) >= 2 ** 31):
+            raise FmrxError(FMRX_EINVAL, "offset does not fit 32 bits")
+        off = off.astype(np.int32)
+        _check(lib().fmrx_tune(self.h, _np_ptr(off), first_pair))
+
+    def tuner_info(self) -> tuple[list[int], int, bool]:
+        """fmrx_tuner_info: (offsets in Hz, next pair index, tuned)."""
+        off = np.zeros(self.n_streams, np.int32)
+        pos, on = C.c_uint64(), C.c_int()
+        _check(lib().fmrx_tuner_info(self.h, _np_ptr(off), C.byref(pos), C.byref(on)))
+        return [int(v) for v in off], pos.value, bool(on.value)
+
+    def process_shared(self, iq: np.ndarray) -> np.ndarray:
+        """One capture (one stream's whole blocks of u8 I/Q) decoded by every tuned stream:
+        S16 PCM, n_streams rows."""
+        iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+        nb = iq.size // self.geo.block_bytes
+        iq = np.ascontiguousarray(iq[: nb * self.geo.block_bytes])
+        out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
+        _check(lib().fmrx_process_shared(self.h, _np_ptr(iq), nb, _np_ptr(out)))
+        return out if self.n_streams > 1 else out[0]
+
+    def process_shared_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
+        _check(lib().fmrx_process_shared_device(self.h, d_iq, n_blocks, d_pcm))
 
     def synchronize(self) -> None:
         _check(lib().fmrx_synchronize(self.h))
