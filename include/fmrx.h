@@ -157,6 +157,57 @@ int fmrx_tuner_info(fmrx_ctx* ctx, int32_t* offsets_hz, uint64_t* next_pair, int
 int fmrx_process_shared(fmrx_ctx* ctx, const uint8_t* iq, size_t n_blocks, int16_t* pcm);
 int fmrx_process_shared_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
 
+/* ---- band scan: which offsets of a capture hold a station -------------------------------------- */
+/* The step in front of fmrx_tune.  Spectrum (csrc/scan.hip): with x[n] = ((I_n - 128)
+ * + j (Q_n - 128)) / 128, N = fft_bins, nseg = n_pairs / N whole segments (no overlap, trailing pairs
+ * ignored), w[i] = 0.5 - 0.5 cos(2 pi i / N) and X_s the N-point DFT of w . x_s,
+ *     power[j] = 8 / (3 N^2 nseg) sum_s |X_s[(j - N/2) mod N]|^2,   j = 0 .. N-1:
+ * linear power, FFT-shifted (bin j at (j - N/2) rf_fs / N Hz), sum_j power[j] ~ mean |x|^2, so 0 dB is
+ * full scale on both rails.  A float32 estimate (within 0.01 dB a bin of the float64 value on 8-bit
+ * captures), the same bits on every run.  The scan has scratch of its own in the context and does
+ * not touch the receiver state: a scan between two fmrx_process calls leaves their output as it was.
+ *
+ * fmrx_scan_detect (host only, no context) on such a spectrum, everything in double:
+ *   1. p[j] = max(power[j], 1e-20); kept bins: |j - N/2| >= dc_notch_bins;
+ *   2. floor = element (floor_percentile (M - 1)) / 100 (integer division) of the M kept bins sorted
+ *      ascending; *floor_db = 10 log10 floor;
+ *   3. candidates f_m = raster_origin_hz + m raster_hz, every integer m with 2 |f_m| + channel_hz <= rf_fs;
+ *   4. C_m = sum of p over the nb_m kept bins with 2 |(j - N/2) rf_fs - f_m N| <= channel_hz N (64-bit
+ *      integers, no rounding); a candidate with nb_m = 0 is never reported;
+ *   5. power_db = 10 log10 C_m, snr_db = 10 log10(C_m / (floor nb_m));
+ *   6. candidates visited by C_m descending (ties: lower offset first); one is accepted when snr_db >=
+ *      min_snr_db and it is at least min_separation_hz from every accepted one;
+ *   7. *n_found = the number accepted; out gets the strongest max_out of them, ascending by offset_hz.
+ * FMRX_EINVAL, nothing written: fft_bins no power of two in [256, 8192]; n_pairs < fft_bins; a
+ * non-positive rf_fs, raster, channel or separation; channel_hz >= rf_fs; floor_percentile outside
+ * 1..99; dc_notch_bins outside [0, fft_bins/2]; a candidate offset fmrx_tuner_design refuses (so every
+ * reported offset can go straight into fmrx_tune).  cfg = NULL: the defaults.  fmrx_scan_detect takes the
+ * transform size from its fft_bins argument, fmrx_scan from cfg->fft_bins.                          */
+typedef struct {
+    int fft_bins;            /* power of two in [256, 8192]; default 4096                     */
+    int raster_hz;           /* channel raster; default 100000                                */
+    int raster_origin_hz;    /* offset of one raster point from the capture centre; default 0 */
+    int channel_hz;          /* integration bandwidth per candidate; default 150000           */
+    int min_separation_hz;   /* between reported stations; default 200000                     */
+    int dc_notch_bins;       /* bins j with |j - N/2| < this are ignored; default 1           */
+    int floor_percentile;    /* 1..99, default 25                                             */
+    float min_snr_db;        /* default 10                                                    */
+} fmrx_scan_config;
+typedef struct { int32_t offset_hz; float power_db; float snr_db; } fmrx_station;
+
+int fmrx_scan_config_default(fmrx_scan_config* cfg);
+/* host buffers; returns when power (fft_bins floats) is in host memory; n_segments may be NULL */
+int fmrx_scan_spectrum(fmrx_ctx* ctx, const uint8_t* iq, size_t n_pairs, int fft_bins, float* power,
+                       size_t* n_segments);
+/* device buffers, async on the context stream; d_iq needs no alignment beyond the pair's 2 bytes */
+int fmrx_scan_spectrum_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_pairs, int fft_bins, float* d_power);
+/* host only, no context (like fmrx_tuner_design); floor_db may be NULL */
+int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_scan_config* cfg,
+                     fmrx_station* out, int max_out, int* n_found, float* floor_db);
+/* spectrum + detect with the context's rf_fs */
+int fmrx_scan(fmrx_ctx* ctx, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg,
+              fmrx_station* out, int max_out, int* n_found);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

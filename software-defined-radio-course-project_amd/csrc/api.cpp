@@ -16,6 +16,7 @@
 
 #include "../../include/fmrx.h"
 #include "fmrx_internal.h"
+#include "scan.h"
 #include "synth.h"
 #include "tuner.h"
 
@@ -172,6 +173,13 @@ struct fmrx_ctx {
     int tune_max_n = 1;                       // the longest rotator period among the streams
     DevBuf<float> d_tune_tab;                 // the streams' (c, s) tables, one after the other
     DevBuf<uint32_t> d_tune_streams;          // TunerStream per stream
+    // band scan (fmrx_scan*): scratch of its own, grown on demand; nothing the decode path reads
+    int scan_bins = 0;                        // the transform size d_scan_tab holds (0: none yet)
+    std::vector<float> scan_tab;              // host copy: 2 N twiddle floats, then N window floats
+    DevBuf<float> d_scan_tab;                 // the same on the device
+    DevBuf<float> d_scan_part;                // the launch's partial rows (scan_workgroups x N)
+    DevBuf<float> d_scan_power;               // the host entry points' result, N floats
+    DevBuf<uint8_t> d_scan_in;                // the host entry points' capture
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -1105,6 +1113,7 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_rds_taps.release(); c->d_rds_dhist.release(); c->d_rds_chan.release(); c->d_rds_car.release();
     c->d_rds_pll.release();
     c->d_tune_tab.release(); c->d_tune_streams.release();
+    c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
     for (auto& e : c->evs) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -1630,6 +1639,173 @@ int fmrx_estimate_psd(fmrx_ctx* c, const float* samples, size_t n, int freq_bins
     const float df = fs / (float)freq_bins;  // fourier.cpp:42-50
     for (int i = 0; i < freq_bins / 2; i++) freq[i] = (float)i * df;
     return FMRX_OK;
+}
+
+// ---- band scan: Welch spectrum of the raw capture (scan.hip) + the host station detector -----
+int fmrx_scan_config_default(fmrx_scan_config* cfg) {
+    if (!cfg) return fail(FMRX_EINVAL, "null config");
+    *cfg = fmrx_scan_config{4096, 100000, 0, 150000, 200000, 1, 25, 10.0f};
+    return FMRX_OK;
+}
+
+namespace {
+int scan_check_size(int fft_bins, size_t n_pairs) {
+    if (!scan_bins_ok(fft_bins))
+        return fail(FMRX_EINVAL, "fft_bins %d: need a power of two in [%d, %d]", fft_bins, kScanMinBins, kScanMaxBins);
+    if (n_pairs < (size_t)fft_bins) return fail(FMRX_EINVAL, "%zu I/Q pairs: fewer than fft_bins (%d)", n_pairs, fft_bins);
+    if (n_pairs / (size_t)fft_bins > 0xffffffffu) return fail(FMRX_EINVAL, "capture too long");
+    return 0;
+}
+
+// arguments checked, device set; enqueues on the context stream
+int scan_run(fmrx_ctx* c, const uint8_t* d_iq, size_t n_pairs, int N, float* d_power) {
+    int rc;
+    const size_t nseg = n_pairs / (size_t)N;
+    if (c->scan_bins != N) {  // tables of this size: stream-ordered behind a scan still in flight
+        c->scan_bins = 0;
+        HIPCHK(hipStreamSynchronize(c->stream));  // the host copy is replaced below
+        c->scan_tab.resize(3 * (size_t)N);
+        scan_tables(N, c->scan_tab.data(), c->scan_tab.data() + 2 * (size_t)N);
+        if ((rc = c->d_scan_tab.ensure(3 * (size_t)kScanMaxBins))) return rc;
+        HIPCHK(hipMemcpyAsync(c->d_scan_tab.p, c->scan_tab.data(), sizeof(float) * c->scan_tab.size(),
+                              hipMemcpyHostToDevice, c->stream));
+        c->scan_bins = N;
+    }
+    const int G = scan_workgroups(N, nseg, c->n_simd / 4);
+    if (G < 1) return fail(FMRX_EHIP, "scan: no resident workgroup for %d bins", N);
+    if ((rc = c->d_scan_part.ensure((size_t)G * N))) return rc;
+    rc = launch_scan(d_iq, nseg, N, c->d_scan_tab.p, c->d_scan_tab.p + 2 * (size_t)N, c->d_scan_part.p, G, d_power,
+                     c->stream);
+    if (rc) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "scan launch failed");
+    return 0;
+}
+}  // namespace
+
+int fmrx_scan_spectrum_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_pairs, int fft_bins, float* d_power) {
+    CtxLock lock_(c);
+    if (!c || !d_iq || !d_power) return fail(FMRX_EINVAL, "null argument");
+    int rc = scan_check_size(fft_bins, n_pairs);
+    if (rc || (rc = set_device(c))) return rc;
+    return scan_run(c, d_iq, n_pairs, fft_bins, d_power);
+}
+
+int fmrx_scan_spectrum(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int fft_bins, float* power, size_t* n_segments) {
+    CtxLock lock_(c);
+    if (!c || !iq || !power) return fail(FMRX_EINVAL, "null argument");
+    int rc = scan_check_size(fft_bins, n_pairs);
+    if (rc || (rc = set_device(c))) return rc;
+    const size_t nseg = n_pairs / (size_t)fft_bins, bytes = 2 * nseg * (size_t)fft_bins;
+    if ((rc = c->d_scan_in.ensure(bytes)) || (rc = c->d_scan_power.ensure(kScanMaxBins))) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_scan_in.p, iq, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = scan_run(c, c->d_scan_in.p, nseg * (size_t)fft_bins, fft_bins, c->d_scan_power.p))) return rc;
+    std::vector<float> got((size_t)fft_bins);  // the caller's buffer is written only on success
+    HIPCHK(hipMemcpyAsync(got.data(), c->d_scan_power.p, sizeof(float) * fft_bins, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::copy(got.begin(), got.end(), power);
+    if (n_segments) *n_segments = nseg;
+    return FMRX_OK;
+}
+
+int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_scan_config* cfg_in, fmrx_station* out,
+                     int max_out, int* n_found, float* floor_db) {
+    fmrx_scan_config cfg;
+    (void)fmrx_scan_config_default(&cfg);
+    if (cfg_in) cfg = *cfg_in;
+    if (!power || !n_found || max_out < 0 || (max_out > 0 && !out)) return fail(FMRX_EINVAL, "bad argument");
+    const int N = fft_bins;
+    if (!scan_bins_ok(N))
+        return fail(FMRX_EINVAL, "fft_bins %d: need a power of two in [%d, %d]", N, kScanMinBins, kScanMaxBins);
+    if (rf_fs <= 0 || cfg.raster_hz <= 0 || cfg.channel_hz <= 0 || cfg.min_separation_hz <= 0)
+        return fail(FMRX_EINVAL, "rf_fs, raster_hz, channel_hz and min_separation_hz must be positive");
+    if (cfg.channel_hz >= rf_fs) return fail(FMRX_EINVAL, "channel_hz %d is not below rf_fs %d", cfg.channel_hz, rf_fs);
+    if (cfg.floor_percentile < 1 || cfg.floor_percentile > 99)
+        return fail(FMRX_EINVAL, "floor_percentile %d outside 1..99", cfg.floor_percentile);
+    if (cfg.dc_notch_bins < 0 || cfg.dc_notch_bins > N / 2)
+        return fail(FMRX_EINVAL, "dc_notch_bins %d outside [0, fft_bins / 2]", cfg.dc_notch_bins);
+    // candidates f_m = origin + m raster with 2 |f_m| + channel_hz <= rf_fs, ascending
+    const long long fs = rf_fs, ch = cfg.channel_hz, ras = cfg.raster_hz, org = cfg.raster_origin_hz;
+    const long long reach = (fs - ch) / 2;  // |f_m| <= (rf_fs - channel_hz) / 2, f_m an integer
+    auto floor_div = [](long long a, long long b) { return a / b - ((a % b != 0 && (a % b < 0) != (b < 0)) ? 1 : 0); };
+    const long long m_lo = -floor_div(reach + org, ras), m_hi = floor_div(reach - org, ras);
+    struct Cand {
+        long long f;
+        double c;
+        int nb;
+        double snr;
+    };
+    std::vector<Cand> cands;
+    for (long long m = m_lo; m <= m_hi; m++) {
+        const long long f = org + m * ras;
+        int tn = 0, tk = 0;
+        const int rc = fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr);  // every reported offset can be tuned to
+        if (rc) return rc;
+        cands.push_back(Cand{f, 0.0, 0, 0.0});
+    }
+    // noise floor: a percentile of the kept bins
+    std::vector<double> p((size_t)N), kept;
+    kept.reserve((size_t)N);
+    auto is_kept = [&](int j) { return std::abs(j - N / 2) >= cfg.dc_notch_bins; };
+    for (int j = 0; j < N; j++) {
+        p[j] = std::max((double)power[j], 1e-20);
+        if (is_kept(j)) kept.push_back(p[j]);
+    }
+    if (kept.empty()) return fail(FMRX_EINVAL, "dc_notch_bins %d leaves no bin", cfg.dc_notch_bins);
+    std::sort(kept.begin(), kept.end());
+    const double floor_p = kept[((size_t)cfg.floor_percentile * (kept.size() - 1)) / 100];
+    for (Cand& cd : cands) {
+        for (int j = 0; j < N; j++) {
+            if (!is_kept(j)) continue;
+            long long d = (long long)(j - N / 2) * fs - cd.f * N;
+            if (d < 0) d = -d;
+            if (2 * d <= ch * N) {
+                cd.c += p[j];
+                cd.nb++;
+            }
+        }
+        cd.snr = cd.nb ? 10.0 * std::log10(cd.c / (floor_p * cd.nb)) : 0.0;
+    }
+    // strongest first (ties: lower offset); a candidate with no kept bin is never reported
+    std::vector<const Cand*> order;
+    for (const Cand& cd : cands)
+        if (cd.nb) order.push_back(&cd);
+    std::stable_sort(order.begin(), order.end(), [](const Cand* a, const Cand* b) { return a->c > b->c; });
+    std::vector<const Cand*> acc;
+    for (const Cand* cd : order) {
+        if (!(cd->snr >= (double)cfg.min_snr_db)) continue;
+        bool clear = true;
+        for (const Cand* a : acc) {
+            const long long d = cd->f > a->f ? cd->f - a->f : a->f - cd->f;
+            if (d < cfg.min_separation_hz) clear = false;
+        }
+        if (clear) acc.push_back(cd);
+    }
+    *n_found = (int)acc.size();
+    if (floor_db) *floor_db = (float)(10.0 * std::log10(floor_p));
+    if (acc.size() > (size_t)max_out) acc.resize((size_t)max_out);
+    std::sort(acc.begin(), acc.end(), [](const Cand* a, const Cand* b) { return a->f < b->f; });
+    for (size_t i = 0; i < acc.size(); i++)
+        out[i] = fmrx_station{(int32_t)acc[i]->f, (float)(10.0 * std::log10(acc[i]->c)), (float)acc[i]->snr};
+    return FMRX_OK;
+}
+
+int fmrx_scan(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
+              int max_out, int* n_found) {
+    CtxLock lock_(c);
+    if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
+    fmrx_scan_config cfg;
+    (void)fmrx_scan_config_default(&cfg);
+    if (cfg_in) cfg = *cfg_in;
+    int rc = scan_check_size(cfg.fft_bins, n_pairs);
+    if (rc) return rc;
+    {  // refuse a bad detector configuration before any GPU work
+        std::vector<float> flat((size_t)cfg.fft_bins, 1.0f);
+        std::vector<fmrx_station> tmp((size_t)std::max(max_out, 0));
+        int n = 0;
+        if ((rc = fmrx_scan_detect(flat.data(), cfg.fft_bins, c->geo.rf_fs, &cfg, tmp.data(), max_out, &n, nullptr))) return rc;
+    }
+    std::vector<float> power((size_t)cfg.fft_bins);
+    if ((rc = fmrx_scan_spectrum(c, iq, n_pairs, cfg.fft_bins, power.data(), nullptr))) return rc;
+    return fmrx_scan_detect(power.data(), cfg.fft_bins, c->geo.rf_fs, &cfg, out, max_out, n_found, nullptr);
 }
 
 // ---- filter.h primitives ---------------------------------------------------------------

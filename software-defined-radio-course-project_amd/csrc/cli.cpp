@@ -1,5 +1,5 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
-// [--offset-hz F]`:
+// [--offset-hz F] [--scan [--scan-bytes B]]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -12,6 +12,10 @@
 //     :187) -- the BASELINE headline path;
 //   * --offset-hz F (an fmrx extension) decodes the station F Hz off the capture's centre
 //     (fmrx_tune: the I/Q is rotated by -F in front of the RF low-pass); the same loop otherwise.
+//   * --scan (an fmrx extension) decodes nothing: it reads up to B bytes of stdin (--scan-bytes,
+//     default 2^24; fewer at EOF), runs the band scan (fmrx_scan, default settings) and prints one
+//     line per station found, `offset_hz power_db snr_db` (two decimals), ascending by offset; no
+//     PCM, exit 0.  Fewer bytes than one transform (2 * fft_bins): message, exit 1.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -79,7 +83,9 @@ void usage(const char* argv0) {
     std::fprintf(stderr,
                  "Usage: %s\nor \nUsage %s <mode> <channels>\n"
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
-                 "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n",
+                 "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
+                 "                [--scan [--scan-bytes B]]  list the stations of the first B bytes (default 16777216)\n"
+                 "                                           as `offset_hz power_db snr_db` lines; no PCM\n",
                  argv0, argv0);
 }
 
@@ -87,6 +93,34 @@ void usage(const char* argv0) {
     std::fprintf(stderr, "fmrx: %s: %s\n", what, hipGetErrorString(e));
     std::fflush(stdout);
     std::_Exit(1);
+}
+
+// --scan: the stations in the first max_bytes of stdin, one line each
+int scan_stdin(fmrx_ctx* ctx, size_t max_bytes) {
+    fmrx_scan_config sc;
+    (void)fmrx_scan_config_default(&sc);
+    std::vector<uint8_t> iq(max_bytes);
+    size_t got = 0;
+    while (got < max_bytes) {
+        const size_t r = std::fread(iq.data() + got, 1, max_bytes - got, stdin);
+        if (r == 0) break;
+        got += r;
+    }
+    if (got < 2 * (size_t)sc.fft_bins) {
+        std::fprintf(stderr, "fmrx: --scan needs at least %d bytes of I/Q on stdin, got %zu\n", 2 * sc.fft_bins, got);
+        return 1;
+    }
+    constexpr int kMaxStations = 256;
+    fmrx_station st[kMaxStations];
+    int n = 0;
+    if (fmrx_scan(ctx, iq.data(), got / 2, &sc, st, kMaxStations, &n) != FMRX_OK) {
+        std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
+        return 1;
+    }
+    for (int i = 0; i < n && i < kMaxStations; i++)
+        std::printf("%d %.2f %.2f\n", (int)st[i].offset_hz, (double)st[i].power_db, (double)st[i].snr_db);
+    std::fflush(stdout);
+    return 0;
 }
 
 #define CLI_HIP(x)                              \
@@ -99,14 +133,17 @@ void usage(const char* argv0) {
 
 int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false, tuned = false;
+    bool mono_product = false, tuned = false, scan = false;
     long offset_hz = 0;
+    long long scan_bytes = 1ll << 24;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--rf-taps") && i + 1 < argc) rf_taps = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
+        else if (!std::strcmp(argv[i], "--scan")) scan = true;
+        else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) {
             offset_hz = std::atol(argv[++i]);
             tuned = true;
@@ -144,6 +181,12 @@ int main(int argc, char** argv) {
     if (fmrx_geometry(&cfg, &geo) != FMRX_OK || fmrx_create(&cfg, &ctx) != FMRX_OK) {
         std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
         return 1;
+    }
+    if (scan) {
+        const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes) : 1;
+        if (scan_bytes <= 0) std::fprintf(stderr, "fmrx: --scan-bytes must be positive\n");
+        fmrx_destroy(ctx);
+        return rc;
     }
     if (tuned) {  // out of range (or no 32-bit value) -> message, exit 1
         const int32_t f = (int32_t)offset_hz;

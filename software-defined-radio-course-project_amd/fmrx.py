@@ -43,6 +43,21 @@ class Geometry(C.Structure):
                 ("pcm_samples", C.c_size_t)]
 
 
+class ScanConfig(C.Structure):
+    """fmrx_scan_config (include/fmrx.h): the band scan's transform size and detector settings."""
+    _fields_ = [("fft_bins", C.c_int), ("raster_hz", C.c_int), ("raster_origin_hz", C.c_int),
+                ("channel_hz", C.c_int), ("min_separation_hz", C.c_int), ("dc_notch_bins", C.c_int),
+                ("floor_percentile", C.c_int), ("min_snr_db", C.c_float)]
+
+
+class Station(C.Structure):
+    """fmrx_station: a station the band scan found, offset_hz from the capture's centre."""
+    _fields_ = [("offset_hz", C.c_int32), ("power_db", C.c_float), ("snr_db", C.c_float)]
+
+    def __repr__(self):
+        return f"Station(offset_hz={self.offset_hz}, power_db={self.power_db:.2f}, snr_db={self.snr_db:.2f})"
+
+
 _vp, _sz, _fp, _i16p, _u8p = C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every function declared in include/fmrx.h
@@ -74,6 +89,12 @@ PROTOTYPES = {
     "fmrx_tuner_info": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "fmrx_process_shared": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_process_shared_device": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_scan_config_default": (C.c_int, [C.POINTER(ScanConfig)]),
+    "fmrx_scan_spectrum": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, C.POINTER(_sz)]),
+    "fmrx_scan_spectrum_device": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp]),
+    "fmrx_scan_detect": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "fmrx_scan": (C.c_int, [_vp, _vp, _sz, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int, C.POINTER(C.c_int)]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -187,6 +208,50 @@ def tuner_design(rf_fs: int, offset_hz: int) -> tuple[int, int, np.ndarray]:
     tab = np.zeros((n.value, 2), np.float32)
     _check(lib().fmrx_tuner_design(rf_fs, offset_hz, C.byref(n), C.byref(k), _np_ptr(tab)))
     return n.value, k.value, tab
+
+
+MAX_STATIONS = 256  # stations a scan reports unless max_out says otherwise
+
+
+def scan_config(**kw) -> ScanConfig:
+    """fmrx_scan_config_default with the given fields replaced."""
+    cfg = ScanConfig()
+    _check(lib().fmrx_scan_config_default(C.byref(cfg)))
+    for k, v in kw.items():
+        if k not in dict(ScanConfig._fields_):
+            raise TypeError(f"no scan setting {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def _stations(arr, n: int) -> list:
+    return [Station(arr[i].offset_hz, arr[i].power_db, arr[i].snr_db) for i in range(n)]
+
+
+def scan_detect(power: np.ndarray, rf_fs: int, max_out: int = MAX_STATIONS, **cfg):
+    """fmrx_scan_detect on an FFT-shifted linear power spectrum (Receiver.scan_spectrum): (stations
+    ascending by offset -- the strongest max_out of those found --, floor_db).  Host only."""
+    p = np.ascontiguousarray(power, np.float32).reshape(-1)
+    out = (Station * max(max_out, 1))()
+    n, fl = C.c_int(), C.c_float()
+    _check(lib().fmrx_scan_detect(_np_ptr(p), p.size, rf_fs, C.byref(scan_config(**cfg)), out, max_out,
+                                  C.byref(n), C.byref(fl)))
+    return _stations(out, min(n.value, max_out)), fl.value
+
+
+def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, **cfg):
+    """Decode everything in a capture: scan it, tune one stream to every station found and run
+    process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
+    ([], an empty array) when the scan finds none."""
+    iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+    with Receiver(mode, channels, rf_taps=rf_taps) as rx:
+        stations = rx.scan(iq, **cfg)
+    if not stations:
+        return [], np.zeros((0, 0), np.int16)
+    with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
+        rx.tune([s.offset_hz for s in stations])
+        pcm = rx.process_shared(iq)
+    return stations, pcm.reshape(len(stations), -1)
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:
@@ -350,6 +415,29 @@ class Receiver:
 
     def process_shared_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
         _check(lib().fmrx_process_shared_device(self.h, d_iq, n_blocks, d_pcm))
+
+    # ---- band scan: which offsets of a capture hold a station
+    def scan_spectrum(self, iq: np.ndarray, fft_bins: int = 4096) -> tuple[np.ndarray, int]:
+        """Welch power spectrum of a u8 I/Q capture (fmrx_scan_spectrum): (power, n_segments), power
+        linear and FFT-shifted, bin j at (j - fft_bins / 2) * rf_fs / fft_bins Hz."""
+        iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+        power = np.zeros(max(fft_bins, 0), np.float32)
+        nseg = _sz()
+        _check(lib().fmrx_scan_spectrum(self.h, _np_ptr(iq), iq.size // 2, fft_bins, _np_ptr(power), C.byref(nseg)))
+        return power, nseg.value
+
+    def scan_spectrum_device(self, d_iq: int, n_pairs: int, fft_bins: int, d_power: int) -> None:
+        _check(lib().fmrx_scan_spectrum_device(self.h, d_iq, n_pairs, fft_bins, d_power))
+
+    def scan(self, iq: np.ndarray, max_out: int = MAX_STATIONS, **cfg) -> list:
+        """fmrx_scan: the stations of a u8 I/Q capture, ascending by offset (settings: ScanConfig's
+        fields)."""
+        iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+        out = (Station * max(max_out, 1))()
+        n = C.c_int()
+        _check(lib().fmrx_scan(self.h, _np_ptr(iq), iq.size // 2, C.byref(scan_config(**cfg)), out, max_out,
+                               C.byref(n)))
+        return _stations(out, min(n.value, max_out))
 
     def synchronize(self) -> None:
         _check(lib().fmrx_synchronize(self.h))
