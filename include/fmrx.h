@@ -157,9 +157,46 @@ int fmrx_tuner_info(fmrx_ctx* ctx, int32_t* offsets_hz, uint64_t* next_pair, int
 int fmrx_process_shared(fmrx_ctx* ctx, const uint8_t* iq, size_t n_blocks, int16_t* pcm);
 int fmrx_process_shared_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
 
+/* ---- raw I/Q formats: int8, int16 and float32 captures ------------------------------------------- */
+/* The calls that take raw I/Q (fmrx_process, fmrx_process_device(_ex), fmrx_rf_block,
+ * fmrx_process_shared(_device), fmrx_seek, fmrx_scan_spectrum(_device), fmrx_scan) read interleaved
+ * pairs, I then Q, in the context's input format; their `const uint8_t*` is then the raw bytes of it.
+ * The normalised samples x_i, x_q below are exact in float32 and take the place of the reference's
+ * (u - 128) / 128 (src/iofunc.cpp:67) in front of everything else: with the tuner's table c, s
+ * (fmrx_tune above) exactly I' = fl(fl(x_i c[p]) + fl(x_q s[p])), Q' = fl(fl(x_q c[p]) - fl(x_i s[p])),
+ * then the RF FIR, the decimation and the discriminator as for u8 (csrc/tuner.hip rotates the
+ * integers and applies the power of two once per RF output: DESIGN.md §5.7 says why that is exact).
+ * For FMRX_IQ_F32 the bits are promised for samples that are 0 or of magnitude in [2^-20, 4];
+ * anything else, NaN and Inf included, follows IEEE arithmetic and never faults.                   */
+#define FMRX_IQ_U8  0   /* x = (u - 128) / 128       2 B a pair  (the default)                     */
+#define FMRX_IQ_S8  1   /* x = s / 128               2 B a pair  int8                              */
+#define FMRX_IQ_S16 2   /* x = s / 32768             4 B a pair  int16, little-endian              */
+#define FMRX_IQ_F32 3   /* x = the float itself      8 B a pair  IEEE float32 (cf32)               */
+/* bytes an I/Q pair of the format; host only; FMRX_EINVAL if unknown */
+int fmrx_iq_pair_bytes(int format);
+/* Sets the format of every stream of the context, then does what fmrx_reset does: the halo is
+ * reallocated at its pair count times the pair's bytes and filled with the format's zero (0x80 for
+ * u8, 0 otherwise), the offsets of fmrx_tune are kept, the position is rewound to 0.  Setting the
+ * format the context already has is a reset and nothing else.  A block stays geo.iq_pairs pairs:
+ * iq_pairs * fmrx_iq_pair_bytes(format) bytes (geo.block_bytes is the u8 figure), and every count
+ * in bytes follows: fmrx_history_bytes, fmrx_seek's n (a whole number of pairs, FMRX_EINVAL
+ * otherwise), the halo inside fmrx_state_size's blob (whose header records the format: a blob taken
+ * in another format is refused with FMRX_ESTATE).  n_pairs of the scan stays a pair count.
+ * With a format other than u8 every call that takes raw I/Q runs the tuned front end, also while
+ * tuning is off: fmrx_tune(ctx, NULL, p) then means offset 0 for every stream (N = 1, c = 1, s = 0:
+ * the bits of the untuned kernels); fmrx_process_shared* still needs an explicit fmrx_tune.  With
+ * u8 nothing changes: tuning off runs the fused, untuned kernels.
+ * Alignment: device pointers and row strides of those calls are aligned to two pairs (4, 4, 8, 16
+ * bytes), the scan's d_iq to one pair (2, 2, 4, 8); anything less is FMRX_EINVAL and no launch.
+ * FMRX_EINVAL, nothing changed: an unknown format; a format other than u8 where the mode and tap
+ * count have no tuned kernel (rf_taps other than 51 and 101).
+ * fmrx_normalize_iq, fmrx_synth_* and the RDS entry points stay u8 / float as they are.          */
+int fmrx_set_input_format(fmrx_ctx* ctx, int format);
+int fmrx_input_format(const fmrx_ctx* ctx, int* format);
+
 /* ---- band scan: which offsets of a capture hold a station -------------------------------------- */
 /* The step in front of fmrx_tune.  Spectrum (csrc/scan.hip): with x[n] = ((I_n - 128)
- * + j (Q_n - 128)) / 128, N = fft_bins, nseg = n_pairs / N whole segments (no overlap, trailing pairs
+ * + j (Q_n - 128)) / 128 (u8; the context's input format's x_i + j x_q otherwise), N = fft_bins, nseg = n_pairs / N whole segments (no overlap, trailing pairs
  * ignored), w[i] = 0.5 - 0.5 cos(2 pi i / N) and X_s the N-point DFT of w . x_s,
  *     power[j] = 8 / (3 N^2 nseg) sum_s |X_s[(j - N/2) mod N]|^2,   j = 0 .. N-1:
  * linear power, FFT-shifted (bin j at (j - N/2) rf_fs / N Hz), sum_j power[j] ~ mean |x|^2, so 0 dB is
@@ -199,7 +236,7 @@ int fmrx_scan_config_default(fmrx_scan_config* cfg);
 /* host buffers; returns when power (fft_bins floats) is in host memory; n_segments may be NULL */
 int fmrx_scan_spectrum(fmrx_ctx* ctx, const uint8_t* iq, size_t n_pairs, int fft_bins, float* power,
                        size_t* n_segments);
-/* device buffers, async on the context stream; d_iq needs no alignment beyond the pair's 2 bytes */
+/* device buffers, async on the context stream; d_iq needs no alignment beyond one pair's bytes */
 int fmrx_scan_spectrum_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_pairs, int fft_bins, float* d_power);
 /* host only, no context (like fmrx_tuner_design); floor_db may be NULL */
 int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_scan_config* cfg,

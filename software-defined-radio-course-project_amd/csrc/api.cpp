@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -120,7 +121,10 @@ struct fmrx_ctx {
     DevBuf<float> d_audio, d_rf;
     DevBuf<float> d_audio_rows;   // modes 2/3: the audio prototype by phase (kAudioRow floats per row)
     // RF state: the raw bytes preceding the next call, double-buffered
-    size_t halo_bytes = 0;
+    size_t halo_bytes = 0;                    // halo_pairs * pair_bytes
+    size_t halo_pairs = 0;
+    int iq_format = kIqU8;                    // fmrx_set_input_format: the raw I/Q format of every stream
+    size_t pair_bytes = 2;                    // bytes an I/Q pair of it
     DevBuf<uint8_t> d_halo[2];
     int halo_cur = 0;
     // audio state of the mono product: last (audio_taps_total - 1) demod samples
@@ -246,6 +250,23 @@ bool fused_rf_supported(const fmrx_ctx* c) {
     return (t == 51 || t == 101) && (d == 10 || d == 4 || d == 9);
 }
 
+// The byte that fills a run of x = 0.0 samples of the context's format
+int iq_zero_byte(const fmrx_ctx* c) { return c->iq_format == kIqU8 ? 0x80 : 0; }
+// Bytes a block of one stream's raw I/Q takes in the context's format (geo.block_bytes for u8)
+size_t iq_block_bytes(const fmrx_ctx* c) { return c->geo.iq_pairs * c->pair_bytes; }
+// The calls that take raw I/Q run the tuned front end (tuner.hip) while tuning is on, and always
+// for a format other than u8 (the fused kernels read u8 only): with tuning off the context's
+// tables then hold zero offsets, which gives the untuned bits.
+bool front_tuned(const fmrx_ctx* c) { return c->tuned || c->iq_format != kIqU8; }
+// n_streams rows of n_blocks blocks in format bytes must fit size_t with room to spare (a block of
+// f32 is four times a block of u8)
+int check_call_size(const fmrx_ctx* c, size_t n_blocks) {
+    const size_t per_block = (size_t)c->cfg.n_streams * c->geo.iq_pairs * 8;
+    if (n_blocks > (std::numeric_limits<size_t>::max() / 4) / per_block)
+        return fail(FMRX_EINVAL, "%zu blocks: the call's byte count overflows", n_blocks);
+    return 0;
+}
+
 int set_device(const fmrx_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     return 0;
@@ -256,8 +277,8 @@ int reset_state(fmrx_ctx* c) {
     c->pll_trig = fmrx_ctx::TrigTrack{};
     c->rds_trig = fmrx_ctx::TrigTrack{};
     c->tune_pos = 0;  // the offsets stay (configuration)
-    HIPCHK(hipMemsetAsync(c->d_halo[0].p, 0x80, c->halo_bytes * ns, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_halo[1].p, 0x80, c->halo_bytes * ns, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_halo[0].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_halo[1].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     c->halo_cur = 0;
     HIPCHK(hipMemsetAsync(c->d_audio_hist.p, 0, sizeof(float) * c->audio_hist * ns, c->stream));
     c->audio_hist_stale = false;
@@ -806,15 +827,19 @@ int ensure_demod(fmrx_ctx* c, size_t n_if) {
 int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,
                     size_t demod_stride, int demod_hist, bool pre_tail) {
     const int ns = c->cfg.n_streams;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 3) != 0 || iq_stride % 4 != 0)
-        return fail(FMRX_EINVAL, "tuned calls need 4-byte aligned I/Q rows");
+    const size_t unit = 2 * c->pair_bytes;  // the kernel's staging unit: two pairs
+    if (reinterpret_cast<uintptr_t>(d_iq) % unit != 0 || iq_stride % unit != 0)
+        return fail(FMRX_EINVAL, "tuned calls need %zu-byte aligned I/Q rows", unit);
+    int rc_size = check_call_size(c, n_blocks);
+    if (rc_size) return rc_size;
     TunerLaunch L{};
     L.iq = d_iq;
     L.iq_stride = iq_stride;
     L.halo = c->d_halo[c->halo_cur].p;
     L.halo_next = c->d_halo[c->halo_cur ^ 1].p;
     L.halo_bytes = c->halo_bytes;
-    L.stream_bytes = n_blocks * c->geo.block_bytes;
+    L.stream_bytes = n_blocks * iq_block_bytes(c);
+    L.format = c->iq_format;
     L.demod = d_demod;
     L.demod_stride = demod_stride;
     L.demod_hist = demod_hist;
@@ -858,6 +883,35 @@ int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_block
         c->audio_hist_stale = false;
     }
     return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
+}
+
+// The streams' rotators for offsets_hz on the device (tables, TunerStream rows, tune_max_n);
+// FMRX_EINVAL with nothing changed for an offset fmrx_tuner_design refuses.
+int tuner_upload(fmrx_ctx* c, const int32_t* offsets_hz) {
+    if (!tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d", c->geo.rf_taps, c->geo.rf_decim);
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t ns = c->cfg.n_streams;
+    std::vector<TunerStream> ts(ns);
+    size_t entries = 0;
+    int max_n = 1;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int N = 0, k = 0;
+        if ((rc = fmrx_tuner_design(c->geo.rf_fs, offsets_hz[s], &N, &k, nullptr))) return rc;
+        ts[s] = TunerStream{(uint32_t)N, (uint32_t)k, (uint32_t)entries, 0u};
+        entries += (size_t)N;
+        max_n = std::max(max_n, N);
+    }
+    std::vector<float> tab(2 * entries);
+    for (size_t s = 0; s < ns; s++) tuner_design(c->geo.rf_fs, offsets_hz[s], nullptr, nullptr, tab.data() + 2 * ts[s].tab);
+    // a call in flight may still read the old tables: drain the stream before they are replaced
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = c->d_tune_tab.ensure(tab.size())) || (rc = c->d_tune_streams.ensure(4 * ns))) return rc;
+    HIPCHK(hipMemcpy(c->d_tune_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_tune_streams.p, ts.data(), sizeof(TunerStream) * ns, hipMemcpyHostToDevice));
+    c->tune_max_n = max_n;
+    return FMRX_OK;
 }
 
 }  // namespace
@@ -1064,6 +1118,7 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
         hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi) != hipSuccess)
         return cleanup(fail(FMRX_EHIP, "hipStreamCreate failed"));
     c->halo_bytes = mono_halo_bytes(g.rf_taps, g.rf_decim, g.audio_down);
+    c->halo_pairs = c->halo_bytes / 2;
     c->audio_hist = g.audio_taps_total - 1;
     if ((rc = c->d_halo[0].ensure(c->halo_bytes * ns)) || (rc = c->d_halo[1].ensure(c->halo_bytes * ns)) ||
         (rc = c->d_audio_hist.ensure((size_t)c->audio_hist * ns)) ||
@@ -1137,17 +1192,19 @@ int fmrx_history_bytes(const fmrx_ctx* c, size_t* bytes) {
 
 // The fused kernel rebuilds every float state of the mono product from the raw bytes in the
 // halo by a pre-roll chunk (mono_fused.hip), so seeking is setting the halo: the last
-// halo_bytes of prev, 0x80 (x = 0.0, the reference's zero-initialised state) in front of a
-// shorter prev.
+// halo_bytes of prev, the format's zero (0x80 for u8: x = 0.0, the reference's zero-initialised
+// state) in front of a shorter prev.  Bytes are the context's format's (fmrx_set_input_format).
 int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     CtxLock lock_(c);
     if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
+    if (n % c->pair_bytes != 0)
+        return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
     int rc = set_device(c);
     if (rc) return rc;
     const size_t ns = c->cfg.n_streams, hb = c->halo_bytes, m = std::min(n, hb);
     uint8_t* h = c->d_halo[c->halo_cur].p;
-    if (m < hb) HIPCHK(hipMemset2DAsync(h, hb, 0x80, hb - m, ns, c->stream));
+    if (m < hb) HIPCHK(hipMemset2DAsync(h, hb, iq_zero_byte(c), hb - m, ns, c->stream));
     if (m > 0)
         HIPCHK(hipMemcpy2DAsync(h + (hb - m), hb, prev + (n - m), n, m, ns,
                                 prev_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
@@ -1192,11 +1249,13 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
     int rc = set_device(c);
     if (rc) return rc;
     // words 0-7 identify the context shape and must match; word 8 carries the audio-history
-    // staleness of a context taken between fmrx_seek and its next fused call (restored with
-    // the blob, so fmrx_audio_block refuses the stale history there too)
+    // staleness of a context taken between fmrx_seek and its next fused call (bit 0; restored with
+    // the blob, so fmrx_audio_block refuses the stale history there too) and the raw I/Q format
+    // (bits 8-15), which must match
     uint32_t hdr[kStateHdrWords] = {kStateMagic, kStateVersion, (uint32_t)c->cfg.mode, (uint32_t)c->cfg.channels,
                                     (uint32_t)c->geo.rf_taps, (uint32_t)c->cfg.n_streams, (uint32_t)c->halo_bytes,
-                                    (uint32_t)c->audio_hist, c->audio_hist_stale ? 1u : 0u, 0u};
+                                    (uint32_t)c->audio_hist,
+                                    (c->audio_hist_stale ? 1u : 0u) | ((uint32_t)c->iq_format << 8), 0u};
     if (put) {
         uint32_t got[kStateHdrWords];
         std::memcpy(got, buf, sizeof got);
@@ -1204,10 +1263,16 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
         if (got[1] != kStateVersion)
             return fail(FMRX_ESTATE, "state blob version %u, expected %u (INTEGRATION.md: blob versions)", got[1],
                         kStateVersion);
+        // word 8, bits 8-15: the raw I/Q format of the halo bytes (0 = u8: the blobs from before the
+        // bits had a meaning carry 0 there and stay valid); checked before the shape, whose halo word
+        // the format changes
+        if ((got[8] & ~0xFF01u) == 0u && (got[8] >> 8) != (uint32_t)c->iq_format)
+            return fail(FMRX_ESTATE, "state blob holds input format %u, the context is set to %d", got[8] >> 8,
+                        c->iq_format);
         if (std::memcmp(hdr + 2, got + 2, 6 * sizeof(uint32_t)) != 0)
             return fail(FMRX_ESTATE, "state blob is for another context shape (mode %u, channels %u, rf_taps %u, "
                         "%u streams)", got[2], got[3], got[4], got[5]);
-        if (got[8] > 1u) return fail(FMRX_ESTATE, "state blob: unknown flags 0x%x", got[8]);
+        if ((got[8] & ~0xFF01u) != 0u) return fail(FMRX_ESTATE, "state blob: unknown flags 0x%x", got[8]);
         if (got[9] != 0u) return fail(FMRX_ESTATE, "state blob: reserved word 9 is 0x%x, must be 0", got[9]);
     } else {
         std::memcpy(buf, hdr, sizeof hdr);
@@ -1280,7 +1345,10 @@ int fmrx_process_device_ex(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, in
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
-    if (c->tuned) return run_tuned(c, d_iq, n_blocks * c->geo.block_bytes, n_blocks, d_pcm, d_mono);
+    if (front_tuned(c)) {
+        if ((rc = check_call_size(c, n_blocks))) return rc;
+        return run_tuned(c, d_iq, n_blocks * iq_block_bytes(c), n_blocks, d_pcm, d_mono);
+    }
     const size_t n_if = n_blocks * c->geo.if_samples;
     if (c->cfg.channels == FMRX_MONO)  // every mode: RF + demod + audio resampler in one launch
         return run_fused(c, d_iq, n_blocks, d_pcm, d_mono, nullptr, 0, 0, true);
@@ -1321,36 +1389,58 @@ int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
     if (!offsets_hz) {  // tuning off: the untuned kernels, exactly as before
+        if (c->iq_format != kIqU8) {  // no untuned kernel reads this format: the tuned one at offset 0
+            const std::vector<int32_t> zeros((size_t)c->cfg.n_streams, 0);
+            const int rc = tuner_upload(c, zeros.data());
+            if (rc) return rc;
+        }
         c->tuned = false;
         c->tune_pos = first_pair;
         return FMRX_OK;
     }
-    if (!tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
-        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d", c->geo.rf_taps, c->geo.rf_decim);
-    int rc = set_device(c);
+    const int rc = tuner_upload(c, offsets_hz);
     if (rc) return rc;
-    const size_t ns = c->cfg.n_streams;
-    std::vector<TunerStream> ts(ns);
-    size_t entries = 0;
-    int max_n = 1;
-    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
-        int N = 0, k = 0;
-        if ((rc = fmrx_tuner_design(c->geo.rf_fs, offsets_hz[s], &N, &k, nullptr))) return rc;
-        ts[s] = TunerStream{(uint32_t)N, (uint32_t)k, (uint32_t)entries, 0u};
-        entries += (size_t)N;
-        max_n = std::max(max_n, N);
-    }
-    std::vector<float> tab(2 * entries);
-    for (size_t s = 0; s < ns; s++) tuner_design(c->geo.rf_fs, offsets_hz[s], nullptr, nullptr, tab.data() + 2 * ts[s].tab);
-    // a call in flight may still read the old tables: drain the stream before they are replaced
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if ((rc = c->d_tune_tab.ensure(tab.size())) || (rc = c->d_tune_streams.ensure(4 * ns))) return rc;
-    HIPCHK(hipMemcpy(c->d_tune_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_tune_streams.p, ts.data(), sizeof(TunerStream) * ns, hipMemcpyHostToDevice));
-    c->tune_offsets.assign(offsets_hz, offsets_hz + ns);
-    c->tune_max_n = max_n;
+    c->tune_offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
     c->tune_pos = first_pair;
     c->tuned = true;
+    return FMRX_OK;
+}
+
+// ---- raw I/Q formats ----------------------------------------------------------------------------
+int fmrx_iq_pair_bytes(int format) {
+    const int b = iq_pair_bytes(format);
+    return b > 0 ? b : fail(FMRX_EINVAL, "unknown I/Q format %d", format);
+}
+
+int fmrx_set_input_format(fmrx_ctx* c, int format) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    const int pb = iq_pair_bytes(format);
+    if (pb < 0) return fail(FMRX_EINVAL, "unknown I/Q format %d", format);
+    if (format != kIqU8 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: u8 input only", c->geo.rf_taps,
+                    c->geo.rf_decim);
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the halo
+    if (format != c->iq_format) {
+        const size_t ns = c->cfg.n_streams, hb = c->halo_pairs * (size_t)pb;
+        if (format != kIqU8 && !c->tuned) {  // the zero-offset tables of the format's untuned calls
+            const std::vector<int32_t> zeros(ns, 0);
+            if ((rc = tuner_upload(c, zeros.data()))) return rc;
+        }
+        if ((rc = c->d_halo[0].ensure(hb * ns)) || (rc = c->d_halo[1].ensure(hb * ns))) return rc;
+        c->iq_format = format;
+        c->pair_bytes = (size_t)pb;
+        c->halo_bytes = hb;
+    }
+    return reset_state(c);
+}
+
+int fmrx_input_format(const fmrx_ctx* c, int* format) {
+    CtxLock lock_(c);
+    if (!c || !format) return fail(FMRX_EINVAL, "null argument");
+    *format = c->iq_format;
     return FMRX_OK;
 }
 
@@ -1430,8 +1520,9 @@ static int process_host(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
+    if ((rc = check_call_size(c, n_blocks))) return rc;
     const size_t ns = c->cfg.n_streams;
-    const size_t in_bytes = (shared ? 1 : ns) * n_blocks * c->geo.block_bytes;
+    const size_t in_bytes = (shared ? 1 : ns) * n_blocks * iq_block_bytes(c);
     auto on_device = shared ? fmrx_process_shared_device : fmrx_process_device;
     const size_t out_n = ns * n_blocks * c->geo.pcm_samples;
     if (in_bytes <= kPinnedCallBytes) {  // pinned staging: the input by DMA, the PCM written in place
@@ -1468,8 +1559,9 @@ int fmrx_rf_block(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, float* demod)
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
+    if ((rc = check_call_size(c, n_blocks))) return rc;
     const size_t ns = c->cfg.n_streams;
-    const size_t in_bytes = ns * n_blocks * c->geo.block_bytes;
+    const size_t in_bytes = ns * n_blocks * iq_block_bytes(c);
     const size_t n_if = n_blocks * c->geo.if_samples;
     if (in_bytes <= kPinnedCallBytes) {  // pinned staging: the input by DMA (the fused kernel's
                                          // staging reads host memory 4x slower), the demod in place
@@ -1479,7 +1571,7 @@ int fmrx_rf_block(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, float* demod)
         std::memcpy(c->h_in.p, iq, in_bytes);
         HIPCHK(hipMemcpyAsync(c->d_in.p, c->h_in.p, in_bytes, hipMemcpyHostToDevice, c->stream));
         float* h_demod = reinterpret_cast<float*>(c->h_out.p);
-        if ((rc = c->tuned ? run_tuned_front(c, c->d_in.p, n_blocks * c->geo.block_bytes, n_blocks, h_demod, n_if, 0, false)
+        if ((rc = front_tuned(c) ? run_tuned_front(c, c->d_in.p, n_blocks * iq_block_bytes(c), n_blocks, h_demod, n_if, 0, false)
                            : run_fused(c, c->d_in.p, n_blocks, nullptr, nullptr, h_demod, n_if, 0, false)))
             return rc;
         if ((rc = wait_small(c))) return rc;
@@ -1488,7 +1580,7 @@ int fmrx_rf_block(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, float* demod)
     }
     if ((rc = c->d_in.ensure(in_bytes)) || (rc = c->d_f32.ensure(ns * n_if))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_in.p, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = c->tuned ? run_tuned_front(c, c->d_in.p, n_blocks * c->geo.block_bytes, n_blocks, c->d_f32.p, n_if, 0, false)
+    if ((rc = front_tuned(c) ? run_tuned_front(c, c->d_in.p, n_blocks * iq_block_bytes(c), n_blocks, c->d_f32.p, n_if, 0, false)
                        : run_fused(c, c->d_in.p, n_blocks, nullptr, nullptr, c->d_f32.p, n_if, 0, false)))
         return rc;
     HIPCHK(hipMemcpyAsync(demod, c->d_f32.p, sizeof(float) * ns * n_if, hipMemcpyDeviceToHost, c->stream));
@@ -1671,10 +1763,12 @@ int scan_run(fmrx_ctx* c, const uint8_t* d_iq, size_t n_pairs, int N, float* d_p
                               hipMemcpyHostToDevice, c->stream));
         c->scan_bins = N;
     }
-    const int G = scan_workgroups(N, nseg, c->n_simd / 4);
+    if (reinterpret_cast<uintptr_t>(d_iq) % c->pair_bytes != 0)
+        return fail(FMRX_EINVAL, "scan: the capture must be aligned to one %zu-byte I/Q pair", c->pair_bytes);
+    const int G = scan_workgroups(N, nseg, c->n_simd / 4, c->iq_format);
     if (G < 1) return fail(FMRX_EHIP, "scan: no resident workgroup for %d bins", N);
     if ((rc = c->d_scan_part.ensure((size_t)G * N))) return rc;
-    rc = launch_scan(d_iq, nseg, N, c->d_scan_tab.p, c->d_scan_tab.p + 2 * (size_t)N, c->d_scan_part.p, G, d_power,
+    rc = launch_scan(d_iq, c->iq_format, nseg, N, c->d_scan_tab.p, c->d_scan_tab.p + 2 * (size_t)N, c->d_scan_part.p, G, d_power,
                      c->stream);
     if (rc) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "scan launch failed");
     return 0;
@@ -1694,7 +1788,7 @@ int fmrx_scan_spectrum(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int fft_b
     if (!c || !iq || !power) return fail(FMRX_EINVAL, "null argument");
     int rc = scan_check_size(fft_bins, n_pairs);
     if (rc || (rc = set_device(c))) return rc;
-    const size_t nseg = n_pairs / (size_t)fft_bins, bytes = 2 * nseg * (size_t)fft_bins;
+    const size_t nseg = n_pairs / (size_t)fft_bins, bytes = c->pair_bytes * nseg * (size_t)fft_bins;
     if ((rc = c->d_scan_in.ensure(bytes)) || (rc = c->d_scan_power.ensure(kScanMaxBins))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_scan_in.p, iq, bytes, hipMemcpyHostToDevice, c->stream));
     if ((rc = scan_run(c, c->d_scan_in.p, nseg * (size_t)fft_bins, fft_bins, c->d_scan_power.p))) return rc;

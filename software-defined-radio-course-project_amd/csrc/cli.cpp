@@ -1,7 +1,7 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
-// [--offset-hz F] [--scan [--scan-bytes B]]`:
+// [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
-// from stdin and writes raw S16LE to stdout under project's process contract:
+// (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
 //     mode 0 (a lone one is ignored, as `project 3` ignores it), exactly two are <mode>
 //     <channels> (atoi; out of range -> message, exit 1), more print the usage and exit 1;
@@ -16,6 +16,10 @@
 //     default 2^24; fewer at EOF), runs the band scan (fmrx_scan, default settings) and prints one
 //     line per station found, `offset_hz power_db snr_db` (two decimals), ascending by offset; no
 //     PCM, exit 0.  Fewer bytes than one transform (2 * fft_bins): message, exit 1.
+//   * --iq-format u8|s8|s16|f32 (an fmrx extension, default u8) reads stdin as int8, little-endian
+//     int16 or float32 pairs (fmrx_set_input_format), in blocks of iq_pairs times the pair's bytes;
+//     with a format other than u8 and no --offset-hz the station at offset 0 is decoded; --scan-bytes
+//     counts bytes of that format.  Without the flag nothing differs from before.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -84,6 +88,7 @@ void usage(const char* argv0) {
                  "Usage: %s\nor \nUsage %s <mode> <channels>\n"
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
+                 "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
                  "                [--scan [--scan-bytes B]]  list the stations of the first B bytes (default 16777216)\n"
                  "                                           as `offset_hz power_db snr_db` lines; no PCM\n",
                  argv0, argv0);
@@ -96,7 +101,7 @@ void usage(const char* argv0) {
 }
 
 // --scan: the stations in the first max_bytes of stdin, one line each
-int scan_stdin(fmrx_ctx* ctx, size_t max_bytes) {
+int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes) {
     fmrx_scan_config sc;
     (void)fmrx_scan_config_default(&sc);
     std::vector<uint8_t> iq(max_bytes);
@@ -106,14 +111,15 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes) {
         if (r == 0) break;
         got += r;
     }
-    if (got < 2 * (size_t)sc.fft_bins) {
-        std::fprintf(stderr, "fmrx: --scan needs at least %d bytes of I/Q on stdin, got %zu\n", 2 * sc.fft_bins, got);
+    if (got < pair_bytes * (size_t)sc.fft_bins) {
+        std::fprintf(stderr, "fmrx: --scan needs at least %zu bytes of I/Q on stdin, got %zu\n",
+                     pair_bytes * (size_t)sc.fft_bins, got);
         return 1;
     }
     constexpr int kMaxStations = 256;
     fmrx_station st[kMaxStations];
     int n = 0;
-    if (fmrx_scan(ctx, iq.data(), got / 2, &sc, st, kMaxStations, &n) != FMRX_OK) {
+    if (fmrx_scan(ctx, iq.data(), got / pair_bytes, &sc, st, kMaxStations, &n) != FMRX_OK) {
         std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
         return 1;
     }
@@ -135,6 +141,8 @@ int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
     bool mono_product = false, tuned = false, scan = false;
     long offset_hz = 0;
+    int iq_format = FMRX_IQ_U8;
+    const char* bad_format = nullptr;
     long long scan_bytes = 1ll << 24;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; i++) {
@@ -144,6 +152,14 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
         else if (!std::strcmp(argv[i], "--scan")) scan = true;
         else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
+        else if (!std::strcmp(argv[i], "--iq-format") && i + 1 < argc) {
+            const char* f = argv[++i];
+            if (!std::strcmp(f, "u8")) iq_format = FMRX_IQ_U8;
+            else if (!std::strcmp(f, "s8")) iq_format = FMRX_IQ_S8;
+            else if (!std::strcmp(f, "s16")) iq_format = FMRX_IQ_S16;
+            else if (!std::strcmp(f, "f32")) iq_format = FMRX_IQ_F32;
+            else bad_format = f;
+        }
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) {
             offset_hz = std::atol(argv[++i]);
             tuned = true;
@@ -164,6 +180,10 @@ int main(int argc, char** argv) {
         usage(argv[0]);
         return 1;
     }
+    if (bad_format) {
+        std::fprintf(stderr, "fmrx: --iq-format %s: expected u8, s8, s16 or f32\n", bad_format);
+        return 1;
+    }
     if (batch < 1) batch = 1;
     std::fprintf(stderr, "Operating in mode %d, %s\n", mode, channels == 1 ? "mono" : "stereo");
 
@@ -182,8 +202,15 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
         return 1;
     }
+    if (iq_format != FMRX_IQ_U8 && fmrx_set_input_format(ctx, iq_format) != FMRX_OK) {
+        std::fprintf(stderr, "fmrx: --iq-format: %s\n", fmrx_last_error());
+        fmrx_destroy(ctx);
+        return 1;
+    }
+    const size_t pair_bytes = (size_t)fmrx_iq_pair_bytes(iq_format);
+    const size_t block_bytes = geo.iq_pairs * pair_bytes;  // geo.block_bytes for u8
     if (scan) {
-        const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes) : 1;
+        const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes, pair_bytes) : 1;
         if (scan_bytes <= 0) std::fprintf(stderr, "fmrx: --scan-bytes must be positive\n");
         fmrx_destroy(ctx);
         return rc;
@@ -197,7 +224,7 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const size_t in_cap = geo.block_bytes * (size_t)batch;
+    const size_t in_cap = block_bytes * (size_t)batch;
     const size_t out_cap = geo.pcm_samples * (size_t)batch;
 
     CLI_HIP(hipSetDevice(device));
@@ -229,7 +256,7 @@ int main(int argc, char** argv) {
                 if (r == 0) break;
                 got += r;
             }
-            s.blocks = got / geo.block_bytes;
+            s.blocks = got / block_bytes;
             s.last = got < in_cap;
             filled_q.push(i);
             if (s.last) return;
@@ -252,7 +279,7 @@ int main(int argc, char** argv) {
         const int i = filled_q.pop();
         Slot& s = slots[i];
         if (s.blocks > 0) {
-            CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks * geo.block_bytes, hipMemcpyHostToDevice, up));
+            CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks * block_bytes, hipMemcpyHostToDevice, up));
             CLI_HIP(hipEventRecord(s.uploaded, up));
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
             if (fmrx_process_device(ctx, s.d_in, s.blocks, s.d_out) != FMRX_OK) {

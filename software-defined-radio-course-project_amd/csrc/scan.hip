@@ -1,11 +1,12 @@
-// scan.hip — the band scan's spectrum: Welch power spectrum of a raw u8 I/Q capture
+// scan.hip — the band scan's spectrum: Welch power spectrum of a raw I/Q capture (u8, s8, s16, f32)
 // (fmrx_scan_spectrum*).  A floating-point estimate, checked against numpy
 // float64 to a stated tolerance (tests/test_gpu_scan.py); the same input gives the same bits
 // on every run (no atomics, fixed summation order).
 //
-//   scan_segments_kernel<L>  N = 2^L.  Workgroup g walks segments g, g + G, ...: coalesced dword
-//                            loads of the u8 pairs (the next segment's in flight during the
-//                            transform), (u - 128) * window into LDS as complex float, an in-place
+//   scan_segments_kernel<L, F>  N = 2^L, F the raw format (ScanFmt below).
+//                            Workgroup g walks segments g, g + G, ...: coalesced loads of two
+//                            pairs a lane (a dword of u8 / s8, the next segment's in flight during the
+//                            transform), integer sample * window into LDS as complex float, an in-place
 //                            decimation-in-frequency FFT -- one radix-2/4/8 pass when L is no
 //                            multiple of 4, then radix-16 passes, every butterfly in registers and
 //                            one LDS round trip a pass -- whose last pass adds |X|^2 to registers
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "scan.h"
+#include "tuner.h"
 
 namespace fmrx {
 
@@ -179,7 +181,55 @@ __device__ __forceinline__ uint32_t scan_dword(const uint32_t* __restrict__ base
     return w;
 }
 
-template <int L>
+// A raw format's unit of two I/Q pairs (Raw), how a unit is loaded and its samples as exact floats
+// (i0, q0, i1, q1) times a power of two that launch_scan folds into the final scale.  u8 and s8
+// share the dword layout and the funnel shift of a start on any pair; s16 and f32 pairs are
+// always element-aligned (4 and 8 bytes), so they take plain loads of that alignment.
+template <int F>
+struct ScanFmt;
+template <>
+struct ScanFmt<kIqU8> {
+    using Raw = uint32_t;
+    static __device__ __forceinline__ Raw load(const uint8_t* iq, const uint32_t* base, unsigned shift, size_t d) {
+        return scan_dword(base, shift, d);
+    }
+    static __device__ __forceinline__ float4 unpack(Raw w) {
+        return make_float4((float)(w & 255u) - 128.0f, (float)((w >> 8) & 255u) - 128.0f,
+                           (float)((w >> 16) & 255u) - 128.0f, (float)(w >> 24) - 128.0f);
+    }
+};
+template <>
+struct ScanFmt<kIqS8> {
+    using Raw = uint32_t;
+    static __device__ __forceinline__ Raw load(const uint8_t* iq, const uint32_t* base, unsigned shift, size_t d) {
+        return scan_dword(base, shift, d);
+    }
+    static __device__ __forceinline__ float4 unpack(Raw w) { return ScanFmt<kIqU8>::unpack(w ^ 0x80808080u); }
+};
+template <>
+struct ScanFmt<kIqS16> {
+    using Raw = uint2;
+    static __device__ __forceinline__ Raw load(const uint8_t* iq, const uint32_t*, unsigned, size_t d) {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(iq) + 2 * d;  // a pair a dword
+        return make_uint2(p[0], p[1]);
+    }
+    static __device__ __forceinline__ float4 unpack(Raw w) {
+        return make_float4((float)((int)(w.x << 16) >> 16), (float)((int)w.x >> 16), (float)((int)(w.y << 16) >> 16),
+                           (float)((int)w.y >> 16));
+    }
+};
+template <>
+struct ScanFmt<kIqF32> {
+    using Raw = float4;
+    static __device__ __forceinline__ Raw load(const uint8_t* iq, const uint32_t*, unsigned, size_t d) {
+        const float2* p = reinterpret_cast<const float2*>(iq) + 2 * d;  // 8-byte aligned pairs
+        const float2 a = p[0], b = p[1];
+        return make_float4(a.x, a.y, b.x, b.y);
+    }
+    static __device__ __forceinline__ float4 unpack(Raw w) { return w; }
+};
+
+template <int L, int F>
 __global__ void __launch_bounds__(kScanThreads)
 scan_segments_kernel(const uint8_t* __restrict__ iq, unsigned nseg, const float2* __restrict__ tw,
                      const float2* __restrict__ win, float* __restrict__ part) {
@@ -188,13 +238,18 @@ scan_segments_kernel(const uint8_t* __restrict__ iq, unsigned nseg, const float2
     constexpr int MA = N / R0;              // sub-length of the first radix-16 pass
     constexpr int N16 = L / 4;              // radix-16 passes, the last one included
     constexpr bool PRE = N <= 4096;         // twiddles and window in registers
-    constexpr int DW = scan_iters(N / 2);   // dwords a thread loads per segment
+    constexpr int DW = scan_iters(N / 2);   // units (two pairs) a thread loads per segment
+    using Fmt = ScanFmt<F>;
+    using Raw = typename Fmt::Raw;
+    // the next segment's units stay in flight during the transform while they fit the 16 registers
+    // the u8 kernel gives them at 8192 bins; a wider format past that loads at staging time
+    constexpr bool PF = DW * (int)(sizeof(Raw) / 4) <= 16;
     constexpr int IT0 = scan_iters(N / (R0 > 1 ? R0 : 2)), IT16 = scan_iters(N / 16);
     static_assert(N16 == 2 || N16 == 3, "256 <= N <= 8192");
     __shared__ float2 buf[N + N / 16];
 
     const int tid = threadIdx.x;
-    const unsigned shift = (unsigned)(reinterpret_cast<uintptr_t>(iq) & 3u);
+    const unsigned shift = sizeof(Raw) == 4 ? (unsigned)(reinterpret_cast<uintptr_t>(iq) & 3u) : 0u;
     const uint32_t* base = reinterpret_cast<const uint32_t*>(iq - shift);
 
     float2 wv[DW];
@@ -212,34 +267,38 @@ scan_segments_kernel(const uint8_t* __restrict__ iq, unsigned nseg, const float2
 #pragma unroll
         for (int p = 0; p < 16; p++) acc[it][p] = 0.0f;
 
-    uint32_t raw[DW];
+    Raw raw[PF ? DW : 1];
     unsigned seg = blockIdx.x;
-    if (seg < nseg) {
+    if (PF && seg < nseg) {
 #pragma unroll
         for (int it = 0; it < DW; it++) {
             const int d = tid + it * T;
-            if ((N / 2) % T == 0 || d < N / 2) raw[it] = scan_dword(base, shift, (size_t)seg * (N / 2) + d);
+            if ((N / 2) % T == 0 || d < N / 2) raw[it] = Fmt::load(iq, base, shift, (size_t)seg * (N / 2) + d);
         }
     }
     for (; seg < nseg; seg += gridDim.x) {
-        // (u - 128) is exact in float; the 1/128 of the normalisation is folded into the final scale
+        // the integer sample is exact in float; the power of two of the normalisation (2^-7, 2^-15)
+        // is folded into the final scale
 #pragma unroll
         for (int it = 0; it < DW; it++) {
             const int d = tid + it * T;
             if ((N / 2) % T == 0 || d < N / 2) {
-                const uint32_t w = raw[it];
+                const float4 x = Fmt::unpack(PF ? raw[it] : Fmt::load(iq, base, shift, (size_t)seg * (N / 2) + d));
                 const float2 h = PRE ? wv[it] : win[d];
                 const int at = padi(2 * d);
-                buf[at] = make_float2(((float)(w & 255u) - 128.0f) * h.x, ((float)((w >> 8) & 255u) - 128.0f) * h.x);
-                buf[at + 1] = make_float2(((float)((w >> 16) & 255u) - 128.0f) * h.y, ((float)(w >> 24) - 128.0f) * h.y);
+                buf[at] = make_float2(x.x * h.x, x.y * h.x);
+                buf[at + 1] = make_float2(x.z * h.y, x.w * h.y);
             }
+            // loads at staging time go four units at a time: hoisted together they would take the
+            // registers the transform's twiddles and accumulators hold
+            if (!PF && it % 4 == 3) __builtin_amdgcn_sched_barrier(0);
         }
         const unsigned next = seg + gridDim.x;
-        if (next < nseg) {
+        if (PF && next < nseg) {
 #pragma unroll
             for (int it = 0; it < DW; it++) {
                 const int d = tid + it * T;
-                if ((N / 2) % T == 0 || d < N / 2) raw[it] = scan_dword(base, shift, (size_t)next * (N / 2) + d);
+                if ((N / 2) % T == 0 || d < N / 2) raw[it] = Fmt::load(iq, base, shift, (size_t)next * (N / 2) + d);
             }
         }
         __syncthreads();
@@ -289,17 +348,39 @@ scan_reduce_kernel(const float* __restrict__ part, int G, int N, double scale, f
     }
 }
 
-template <int L>
-int scan_occupancy(int* per_cu) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, scan_segments_kernel<L>, kScanThreads, 0) == hipSuccess
+template <int L, int F>
+int scan_occupancy_format(int* per_cu) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, scan_segments_kernel<L, F>, kScanThreads, 0) == hipSuccess
                ? 0 : -2;
 }
 
 template <int L>
-void scan_launch(const uint8_t* iq, unsigned nseg, const float* tw, const float* win, float* part, int G,
-                 hipStream_t s) {
-    hipLaunchKernelGGL(scan_segments_kernel<L>, dim3(G), dim3(kScanThreads), 0, s, iq, nseg,
+int scan_occupancy(int format, int* per_cu) {
+    switch (format) {
+        case kIqU8: return scan_occupancy_format<L, kIqU8>(per_cu);
+        case kIqS8: return scan_occupancy_format<L, kIqS8>(per_cu);
+        case kIqS16: return scan_occupancy_format<L, kIqS16>(per_cu);
+        case kIqF32: return scan_occupancy_format<L, kIqF32>(per_cu);
+    }
+    return -2;
+}
+
+template <int L, int F>
+void scan_launch_format(const uint8_t* iq, unsigned nseg, const float* tw, const float* win, float* part, int G,
+                        hipStream_t s) {
+    hipLaunchKernelGGL((scan_segments_kernel<L, F>), dim3(G), dim3(kScanThreads), 0, s, iq, nseg,
                        reinterpret_cast<const float2*>(tw), reinterpret_cast<const float2*>(win), part);
+}
+
+template <int L>
+void scan_launch(int format, const uint8_t* iq, unsigned nseg, const float* tw, const float* win, float* part, int G,
+                 hipStream_t s) {
+    switch (format) {
+        case kIqU8: scan_launch_format<L, kIqU8>(iq, nseg, tw, win, part, G, s); break;
+        case kIqS8: scan_launch_format<L, kIqS8>(iq, nseg, tw, win, part, G, s); break;
+        case kIqS16: scan_launch_format<L, kIqS16>(iq, nseg, tw, win, part, G, s); break;
+        case kIqF32: scan_launch_format<L, kIqF32>(iq, nseg, tw, win, part, G, s); break;
+    }
 }
 
 int scan_log2(int N) {
@@ -320,36 +401,39 @@ void scan_tables(int N, float* tw, float* win) {
     }
 }
 
-int scan_workgroups(int N, size_t nseg, int cus) {
-    if (!scan_bins_ok(N) || nseg < 1) return 0;
+int scan_workgroups(int N, size_t nseg, int cus, int format) {
+    if (!scan_bins_ok(N) || nseg < 1 || iq_pair_bytes(format) < 0) return 0;
     int per_cu = 0, rc = -2;
     switch (scan_log2(N)) {
-        case 8: rc = scan_occupancy<8>(&per_cu); break;
-        case 9: rc = scan_occupancy<9>(&per_cu); break;
-        case 10: rc = scan_occupancy<10>(&per_cu); break;
-        case 11: rc = scan_occupancy<11>(&per_cu); break;
-        case 12: rc = scan_occupancy<12>(&per_cu); break;
-        case 13: rc = scan_occupancy<13>(&per_cu); break;
+        case 8: rc = scan_occupancy<8>(format, &per_cu); break;
+        case 9: rc = scan_occupancy<9>(format, &per_cu); break;
+        case 10: rc = scan_occupancy<10>(format, &per_cu); break;
+        case 11: rc = scan_occupancy<11>(format, &per_cu); break;
+        case 12: rc = scan_occupancy<12>(format, &per_cu); break;
+        case 13: rc = scan_occupancy<13>(format, &per_cu); break;
     }
     if (rc || per_cu < 1) return 0;
     const size_t resident = (size_t)(cus > 0 ? cus : 1) * (size_t)per_cu;
     return (int)(nseg < resident ? nseg : resident);
 }
 
-int launch_scan(const uint8_t* iq, size_t nseg, int N, const float* d_tw, const float* d_win, float* d_part, int G,
-                float* d_power, hipStream_t s) {
+int launch_scan(const uint8_t* iq, int format, size_t nseg, int N, const float* d_tw, const float* d_win, float* d_part,
+                int G, float* d_power, hipStream_t s) {
     if (!scan_bins_ok(N) || nseg < 1 || nseg > 0xffffffffu || G < 1 || (size_t)G > nseg) return -1;
+    if (iq_pair_bytes(format) < 0) return -1;
     const unsigned ns = (unsigned)nseg;
     switch (scan_log2(N)) {
-        case 8: scan_launch<8>(iq, ns, d_tw, d_win, d_part, G, s); break;
-        case 9: scan_launch<9>(iq, ns, d_tw, d_win, d_part, G, s); break;
-        case 10: scan_launch<10>(iq, ns, d_tw, d_win, d_part, G, s); break;
-        case 11: scan_launch<11>(iq, ns, d_tw, d_win, d_part, G, s); break;
-        case 12: scan_launch<12>(iq, ns, d_tw, d_win, d_part, G, s); break;
-        case 13: scan_launch<13>(iq, ns, d_tw, d_win, d_part, G, s); break;
+        case 8: scan_launch<8>(format, iq, ns, d_tw, d_win, d_part, G, s); break;
+        case 9: scan_launch<9>(format, iq, ns, d_tw, d_win, d_part, G, s); break;
+        case 10: scan_launch<10>(format, iq, ns, d_tw, d_win, d_part, G, s); break;
+        case 11: scan_launch<11>(format, iq, ns, d_tw, d_win, d_part, G, s); break;
+        case 12: scan_launch<12>(format, iq, ns, d_tw, d_win, d_part, G, s); break;
+        case 13: scan_launch<13>(format, iq, ns, d_tw, d_win, d_part, G, s); break;
     }
-    // P = 8 / (3 N^2 nseg) sum |FFT(w x)|^2 with x = (u - 128) / 128: the 2^-14 is the folded 1/128^2
-    const double scale = 8.0 / (3.0 * (double)N * (double)N * (double)nseg) / 16384.0;
+    // P = 8 / (3 N^2 nseg) sum |FFT(w x)|^2 with x the integer sample times 2^-7 (u8, s8) or 2^-15
+    // (s16): the folded square of that power of two; none for f32
+    const double fold = format == kIqF32 ? 1.0 : format == kIqS16 ? 1073741824.0 : 16384.0;
+    const double scale = 8.0 / (3.0 * (double)N * (double)N * (double)nseg) / fold;
     hipLaunchKernelGGL(scan_reduce_kernel, dim3(N / kReduceBins), dim3(kReduceBins * kReduceSlices), 0, s, d_part, G, N,
                        scale, d_power);
     return hipGetLastError() == hipSuccess ? 0 : -2;

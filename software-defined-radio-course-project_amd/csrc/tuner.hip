@@ -1,4 +1,4 @@
-// tuner.hip — the frequency-translating front end: u8 I/Q -> rotate by a per-stream offset ->
+// tuner.hip — the frequency-translating front end: raw I/Q -> rotate by a per-stream offset ->
 // RF LPF + decimate -> FM demod, one launch, demod rows out (the audio stages of api.cpp take them
 // unchanged).  A stream tuned to +f Hz multiplies pair n by e^(-j 2 pi f n / rf_fs), so a station
 // at +f of the capture lands on 0 Hz; several streams may read ONE capture (iq_stride = 0).
@@ -13,13 +13,19 @@
 // The kernel rotates the integer samples u - 128 instead (x = (u - 128) 2^-7: every product and
 // sum scales exactly, all values stay far from the subnormal range) and applies the 2^-7 once per
 // RF output, in front of the discriminator.
+// Input formats (TunerLaunch::format, fmrx.h FMRX_IQ_*): x = (u - 128) 2^-7 for u8, s 2^-7 for s8,
+// s 2^-15 for little-endian s16, the float itself for f32 -- only the samples in front of the
+// rotation differ.  The integer formats rotate the integers and scale once per RF output as above
+// (nothing becomes subnormal); f32 takes no scale at all, so its arithmetic is the
+// definition's operation for operation.  A lane's staging unit is two pairs in every format: a
+// dword (u8, s8), a uint2 (s16), a float4 (f32).
 //
 // Decomposition: mono_fused.hip's.  A workgroup (one wave) walks a run of chunks of one stream;
 // a pre-roll chunk in front rebuilds the RF history and the discriminator's previous I/Q from the
-// raw bytes there (halo, then the call's bytes, then 0x80 padding).  The phase of a pair is a
-// function of its absolute index alone, so the pre-roll carries no rotator state: a workgroup
+// raw bytes there (halo, then the call's bytes, then padding of the format's zero).  The phase of a
+// pair is a function of its absolute index alone, so the pre-roll carries no rotator state: a workgroup
 // reduces its first pair's index mod N in 64 bits once, then steps phases by conditional subtracts.
-// Per chunk: coalesced dword loads (two pairs a lane, prefetched one chunk ahead), u8 -> float,
+// Per chunk: coalesced unit loads (two pairs a lane, prefetched one chunk ahead), raw -> float,
 // rotation against the stream's table (staged in LDS once per workgroup: N <= 4096 entries always
 // fit), rotated pairs to LDS as float4; the RF FIR with I and Q together in packed f32 ops and the
 // taps in VGPRs; the neighbour's last output by a DPP wave shift; demod to global memory.
@@ -54,7 +60,7 @@ struct TunerCfg {
     // pairs every S pairs; (even b, b + 1) groups never straddle a pad
     static constexpr int slot(int b) { return b + G * (b / S); }
     static constexpr int XB = slot(H + P + 2) + 4;      // LDS pairs
-    static constexpr int NLD = (P / 2) / NT;            // 4-B (2-pair) loads per thread and chunk
+    static constexpr int NLD = (P / 2) / NT;            // unit (2-pair) loads per thread and chunk
     static constexpr int LH0 = ((P - H) / 2) / NT;      // first load index holding history pairs
     static constexpr int NG = (T + 1) / 2;              // tap groups: {0}, {1,2}, {3,4}, ...
     static_assert(T % 2 == 1, "odd tap count");
@@ -63,27 +69,81 @@ struct TunerCfg {
     static_assert(CIF >= kPreTail, "the pre-roll chunk holds the audio history");
 };
 
-// 4 bytes (two I/Q pairs) of the virtual stream (halo ++ data ++ 0x80 padding) at byte offset
-// `off` (a multiple of 4).  Bytes past the end read as 128, i.e. x = 0.0.
-__device__ inline uint32_t load4(const uint8_t* in, const uint8_t* halo, long long off, long long total,
-                                 long long halo_bytes) {
-    if (off >= 0) {
-        if (off + 4 <= total) return *reinterpret_cast<const uint32_t*>(in + off);
-        return 0x80808080u;
-    }
-    return *reinterpret_cast<const uint32_t*>(halo + (halo_bytes + off));
-}
-
 // u - 128 of byte K of w as an exact float
 template <int K>
 __device__ inline float sbyte(uint32_t w) {
     return static_cast<float>((w >> (8 * K)) & 0xFFu) - 128.0f;
 }
 
+// A raw format's staging unit: two I/Q pairs as one load (Raw), the unit of zeros (padding past the
+// end of the stream), the samples as exact floats times 2^SH (the kernel rotates and filters these
+// and applies SCALE = 2^-SH once per RF output; F32 takes the floats themselves, no scale).
+template <int F>
+struct IqFmt;
+template <>
+struct IqFmt<kIqU8> {
+    using Raw = uint32_t;
+    static constexpr int PB = 2;
+    static constexpr float SCALE = 0.0078125f;
+    static __device__ inline Raw zero() { return 0x80808080u; }
+    static __device__ inline void unpack(Raw w, float2v& x0, float2v& x1) {
+        x0 = float2v{sbyte<0>(w), sbyte<1>(w)};
+        x1 = float2v{sbyte<2>(w), sbyte<3>(w)};
+    }
+};
+template <>
+struct IqFmt<kIqS8> {  // s = (s ^ 0x80 as u8) - 128: one xor a unit, then U8's conversion
+    using Raw = uint32_t;
+    static constexpr int PB = 2;
+    static constexpr float SCALE = 0.0078125f;
+    static __device__ inline Raw zero() { return 0u; }
+    static __device__ inline void unpack(Raw w, float2v& x0, float2v& x1) {
+        IqFmt<kIqU8>::unpack(w ^ 0x80808080u, x0, x1);
+    }
+};
+template <>
+struct IqFmt<kIqS16> {  // little-endian int16: I in the low half of a dword, Q in the high half
+    using Raw = uint2;
+    static constexpr int PB = 4;
+    static constexpr float SCALE = 0.000030517578125f;  // 2^-15
+    static __device__ inline Raw zero() { return make_uint2(0u, 0u); }
+    static __device__ inline float lo(uint32_t w) { return static_cast<float>(static_cast<int>(w << 16) >> 16); }
+    static __device__ inline float hi(uint32_t w) { return static_cast<float>(static_cast<int>(w) >> 16); }
+    static __device__ inline void unpack(Raw w, float2v& x0, float2v& x1) {
+        x0 = float2v{lo(w.x), hi(w.x)};
+        x1 = float2v{lo(w.y), hi(w.y)};
+    }
+};
+template <>
+struct IqFmt<kIqF32> {
+    using Raw = float4;
+    static constexpr int PB = 8;  // no SCALE: the floats are the samples
+    static __device__ inline Raw zero() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    static __device__ inline void unpack(Raw w, float2v& x0, float2v& x1) {
+        x0 = float2v{w.x, w.y};
+        x1 = float2v{w.z, w.w};
+    }
+};
+
+// One unit (two I/Q pairs) of the virtual stream (halo ++ data ++ padding of the format's zero) at
+// byte offset `off` (a multiple of the unit).  Pairs past the end read as x = 0.0.
+template <int F>
+__device__ inline typename IqFmt<F>::Raw load_unit(const uint8_t* in, const uint8_t* halo, long long off,
+                                                   long long total, long long halo_bytes) {
+    using Raw = typename IqFmt<F>::Raw;
+    if (off >= 0) {
+        if (off + (long long)sizeof(Raw) <= total) return *reinterpret_cast<const Raw*>(in + off);
+        return IqFmt<F>::zero();
+    }
+    return *reinterpret_cast<const Raw*>(halo + (halo_bytes + off));
+}
+
 // The two pairs of w rotated by table entries a (first pair) and b: (I', Q', I', Q'), every
 // product and sum rounded separately (no FMA: -ffp-contract=off).
-__device__ inline float4 rotate2(uint32_t w, float2 a, float2 b) {
-    const float2v x0 = {sbyte<0>(w), sbyte<1>(w)}, x1 = {sbyte<2>(w), sbyte<3>(w)};
+template <int F>
+__device__ inline float4 rotate2(typename IqFmt<F>::Raw w, float2 a, float2 b) {
+    float2v x0, x1;
+    IqFmt<F>::unpack(w, x0, x1);
     const float2v c0 = x0 * a.x, c1 = x1 * b.x;                        // (i c, q c)
     const float2v s0 = float2v{x0.y, -x0.x} * a.y, s1 = float2v{x1.y, -x1.x} * b.y;  // (q s, -(i s))
     const float2v r0 = c0 + s0, r1 = c1 + s1;
@@ -104,9 +164,12 @@ __device__ inline void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int T, int D, int R, int PD>
+template <int T, int D, int R, int PD, int F>
 __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps) {
     using C = TunerCfg<T, D, R>;
+    using Fmt = IqFmt<F>;
+    using Raw = typename Fmt::Raw;
+    constexpr int PB = Fmt::PB;                  // bytes an I/Q pair; a Raw holds two pairs
     constexpr int NT = kNT, CIF = C::CIF, P = C::P, H = C::H, S = C::S, G = C::G, NLD = C::NLD;
     constexpr int WH = C::WH, NG = C::NG;
     extern __shared__ float2 rot[];              // the stream's table: (c[p], s[p]), p < N
@@ -134,7 +197,7 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
     const int c0 = (int)((long long)seg * n_chunks / L.segs);
     const int c1 = (int)((long long)(seg + 1) * n_chunks / L.segs);
     if (c0 >= c1) return;
-    const int c_full = (int)(L.stream_bytes / (2 * P));  // chunks lying wholly in the data
+    const int c_full = (int)(L.stream_bytes / (PB * P));  // chunks lying wholly in the data
 
     const uint8_t* in = L.iq + (size_t)stream * L.iq_stride;
     const uint8_t* halo = L.halo + (size_t)stream * L.halo_bytes;
@@ -161,18 +224,18 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
     // ---- prologue: RF history in front of the pre-roll chunk (pairs [(c0-1)P - H, (c0-1)P))
     for (int i = tid; i < H / 2; i += NT) {
         const long long rel = (long long)(c0 - 1) * P - H + 2 * i;
-        const uint32_t w = load4(in, halo, rel * 2, total, hb);
+        const Raw w = load_unit<F>(in, halo, rel * PB, total, hb);
         const uint32_t p0 = phase_of(rel);
-        xb4[C::slot(2 * i) / 2] = rotate2(w, rot[p0], rot[addmod(p0, k, N)]);
+        xb4[C::slot(2 * i) / 2] = rotate2<F>(w, rot[p0], rot[addmod(p0, k, N)]);
     }
-    // Input prefetch, one chunk ahead: always the same coalesced dword loads, from a base clamped
+    // Input prefetch, one chunk ahead: always the same coalesced unit loads, from a base clamped
     // into the stream so that they never leave it; the chunks that touch the halo or run past the
     // end (c outside [0, c_full)) are rebuilt at staging time.
-    uint32_t pf[NLD];
+    Raw pf[NLD];
     auto fetch = [&](int cc) {
         if (c_full == 0) return;  // stream shorter than a chunk: every chunk is rebuilt
         const int cl = cc < 0 ? 0 : (cc < c_full ? cc : c_full - 1);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(in + (size_t)cl * (2 * P)) + tid;
+        const Raw* src = reinterpret_cast<const Raw*>(in + (size_t)cl * (PB * P)) + tid;
 #pragma unroll
         for (int l = 0; l < NLD; l++) pf[l] = src[l * NT];
     };
@@ -188,13 +251,13 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
         if (!(c >= 0 && c < c_full)) {  // rare (one uniform branch): from the halo / padding
 #pragma unroll
             for (int l = 0; l < NLD; l++)
-                pf[l] = load4(in, halo, (long long)c * (2 * P) + 4LL * (tid + l * NT), total, hb);
+                pf[l] = load_unit<F>(in, halo, (long long)c * (PB * P) + (long long)sizeof(Raw) * (tid + l * NT), total, hb);
         }
         uint32_t ph = addmod(pc, ph_tid, N);
 #pragma unroll
         for (int l = 0; l < NLD; l++) {
             const int u = tid + l * NT;
-            const float4 f = rotate2(pf[l], rot[ph], rot[addmod(ph, k, N)]);
+            const float4 f = rotate2<F>(pf[l], rot[ph], rot[addmod(ph, k, N)]);
             ph = addmod(ph, ph_ld, N);
             xb4[C::slot(H + 2 * u) / 2] = f;
             if (l >= C::LH0) hist[l - C::LH0] = f;  // the chunk's last H pairs: next chunk's history
@@ -243,12 +306,14 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        // pin the accumulators (the FIR chains stay in front of the hand-off), then the 2^-7 of
-        // the normalisation, exact, once per output
+        // pin the accumulators (the FIR chains stay in front of the hand-off), then the power of
+        // two of the normalisation (2^-7, 2^-15; none for f32), exact, once per output
 #pragma unroll
         for (int r = 0; r < R; r++) asm volatile("" ::"v"(acc[r]));
+        if constexpr (F != kIqF32) {
 #pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = acc[r] * 0.0078125f;
+            for (int r = 0; r < R; r++) acc[r] = acc[r] * Fmt::SCALE;
+        }
         wave_sync();  // (B) all RF reads of xb done
 
         // ---- carries for chunk c+1: RF history (the chunk's pairs [P - H, P) -> [0, H)) from the
@@ -279,11 +344,22 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
     }
 }
 
-template <int T, int D, int R, int PD>
-int launch_variant(const TunerLaunch& L, int n_streams, int max_n, const MonoTaps& taps, hipStream_t s) {
-    hipLaunchKernelGGL((tuner_kernel<T, D, R, PD>), dim3(n_streams * L.segs), dim3(kNT),
+template <int T, int D, int R, int PD, int F>
+int launch_format(const TunerLaunch& L, int n_streams, int max_n, const MonoTaps& taps, hipStream_t s) {
+    hipLaunchKernelGGL((tuner_kernel<T, D, R, PD, F>), dim3(n_streams * L.segs), dim3(kNT),
                        sizeof(float2) * (size_t)max_n, s, L, taps);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+template <int T, int D, int R, int PD>
+int launch_variant(const TunerLaunch& L, int n_streams, int max_n, const MonoTaps& taps, hipStream_t s) {
+    switch (L.format) {
+        case kIqU8: return launch_format<T, D, R, PD, kIqU8>(L, n_streams, max_n, taps, s);
+        case kIqS8: return launch_format<T, D, R, PD, kIqS8>(L, n_streams, max_n, taps, s);
+        case kIqS16: return launch_format<T, D, R, PD, kIqS16>(L, n_streams, max_n, taps, s);
+        case kIqF32: return launch_format<T, D, R, PD, kIqF32>(L, n_streams, max_n, taps, s);
+    }
+    return -1;
 }
 
 // static LDS of a variant (the staged pairs) in bytes

@@ -21,6 +21,9 @@ HEADER = os.path.join(REPO, "include", "fmrx.h")
 
 FMRX_OK, FMRX_EINVAL, FMRX_EHIP, FMRX_ENOMEM, FMRX_ESTATE = 0, -1, -2, -3, -4
 MONO, STEREO = 1, 2
+# raw I/Q formats (include/fmrx.h FMRX_IQ_*)
+IQ_U8, IQ_S8, IQ_S16, IQ_F32 = 0, 1, 2, 3
+IQ_DTYPES = {IQ_U8: np.dtype(np.uint8), IQ_S8: np.dtype(np.int8), IQ_S16: np.dtype("<i2"), IQ_F32: np.dtype("<f4")}
 
 
 class FmrxError(RuntimeError):
@@ -89,6 +92,9 @@ PROTOTYPES = {
     "fmrx_tuner_info": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "fmrx_process_shared": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_process_shared_device": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_iq_pair_bytes": (C.c_int, [C.c_int]),
+    "fmrx_set_input_format": (C.c_int, [_vp, C.c_int]),
+    "fmrx_input_format": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "fmrx_scan_config_default": (C.c_int, [C.POINTER(ScanConfig)]),
     "fmrx_scan_spectrum": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, C.POINTER(_sz)]),
     "fmrx_scan_spectrum_device": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp]),
@@ -210,6 +216,32 @@ def tuner_design(rf_fs: int, offset_hz: int) -> tuple[int, int, np.ndarray]:
     return n.value, k.value, tab
 
 
+def iq_pair_bytes(fmt: int) -> int:
+    """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
+    n = lib().fmrx_iq_pair_bytes(fmt)
+    if n < 0:
+        _check(n)
+    return n
+
+
+def iq_format_of(a) -> int:
+    """The raw I/Q format an array's dtype stands for: uint8, int8, int16, float32, and complex64
+    (viewed as float32 pairs).  ValueError for anything else."""
+    dt = np.asarray(a).dtype
+    if dt == np.complex64:
+        return IQ_F32
+    for fmt, want in IQ_DTYPES.items():
+        if dt == want:
+            return fmt
+    raise ValueError(f"no raw I/Q format for dtype {dt} (uint8, int8, int16, float32, complex64)")
+
+
+def _iq_flat(a) -> np.ndarray:
+    """a as a contiguous array of its raw format's elements (complex64 as float32 pairs)."""
+    a = np.ascontiguousarray(a)
+    return a.view(np.float32) if a.dtype == np.complex64 else a
+
+
 MAX_STATIONS = 256  # stations a scan reports unless max_out says otherwise
 
 
@@ -243,12 +275,17 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none."""
-    iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+    fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
+    iq = _iq_flat(iq).reshape(-1)
     with Receiver(mode, channels, rf_taps=rf_taps) as rx:
+        if fmt != IQ_U8:
+            rx.set_input_format(fmt)
         stations = rx.scan(iq, **cfg)
     if not stations:
         return [], np.zeros((0, 0), np.int16)
     with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
+        if fmt != IQ_U8:
+            rx.set_input_format(fmt)
         rx.tune([s.offset_hz for s in stations])
         pcm = rx.process_shared(iq)
     return stations, pcm.reshape(len(stations), -1)
@@ -304,19 +341,50 @@ class Receiver:
     # ---- sizes
     @property
     def block_bytes(self) -> int:
-        return self.geo.block_bytes
+        """Bytes of a block of raw I/Q in the context's input format (geo.block_bytes for u8)."""
+        return self.geo.iq_pairs * self._pair_bytes
 
     def n_blocks(self, n_bytes_per_stream: int) -> int:
-        return n_bytes_per_stream // self.geo.block_bytes
+        return n_bytes_per_stream // self.block_bytes
+
+    # ---- raw I/Q format
+    _fmt, _pair_bytes = IQ_U8, 2
+
+    def set_input_format(self, fmt: int) -> None:
+        """fmrx_set_input_format: the raw format of every stream (IQ_U8 .. IQ_F32), then a reset."""
+        _check(lib().fmrx_set_input_format(self.h, int(fmt)))
+        self._fmt, self._pair_bytes = int(fmt), iq_pair_bytes(int(fmt))
+
+    @property
+    def input_format(self) -> int:
+        f = C.c_int()
+        _check(lib().fmrx_input_format(self.h, C.byref(f)))
+        return f.value
+
+    def _raw(self, iq) -> np.ndarray:
+        """iq as a contiguous array of the context's format's elements, two a pair.  u8 contexts
+        convert as they always did; any other format takes arrays of its own dtype only."""
+        if self._fmt == IQ_U8:
+            dt = getattr(iq, "dtype", None)
+            if dt is not None and dt != np.uint8 and (dt == np.complex64 or dt in IQ_DTYPES.values()):
+                raise FmrxError(FMRX_EINVAL, f"array of dtype {dt} for a u8 context (set_input_format first)")
+            return np.ascontiguousarray(iq, np.uint8)
+        a = _iq_flat(iq)
+        if a.dtype != IQ_DTYPES[self._fmt]:
+            raise FmrxError(FMRX_EINVAL, f"array of dtype {a.dtype} for input format {self._fmt} "
+                                         f"({IQ_DTYPES[self._fmt]})")
+        return a
 
     # ---- host entry points
     def _streams(self, iq: np.ndarray) -> tuple[np.ndarray, int]:
-        iq = np.ascontiguousarray(iq, np.uint8).reshape(self.n_streams, -1)
-        nb = iq.shape[1] // self.geo.block_bytes
-        return np.ascontiguousarray(iq[:, : nb * self.geo.block_bytes]), nb
+        iq = self._raw(iq).reshape(self.n_streams, -1)
+        per = 2 * self.geo.iq_pairs  # elements a block
+        nb = iq.shape[1] // per
+        return np.ascontiguousarray(iq[:, : nb * per]), nb
 
     def process(self, iq: np.ndarray) -> np.ndarray:
-        """Full blocks of u8 I/Q (per stream) -> S16 PCM (R,L interleaved for stereo)."""
+        """Full blocks of raw I/Q of the context's format (per stream; u8 unless set_input_format
+        said otherwise) -> S16 PCM (R,L interleaved for stereo)."""
         iq, nb = self._streams(iq)
         out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
         if nb:
@@ -404,11 +472,11 @@ class Receiver:
         return [int(v) for v in off], pos.value, bool(on.value)
 
     def process_shared(self, iq: np.ndarray) -> np.ndarray:
-        """One capture (one stream's whole blocks of u8 I/Q) decoded by every tuned stream:
+        """One capture (one stream's whole blocks of raw I/Q) decoded by every tuned stream:
         S16 PCM, n_streams rows."""
-        iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
-        nb = iq.size // self.geo.block_bytes
-        iq = np.ascontiguousarray(iq[: nb * self.geo.block_bytes])
+        iq = self._raw(iq).reshape(-1)
+        nb = iq.size // (2 * self.geo.iq_pairs)
+        iq = np.ascontiguousarray(iq[: nb * 2 * self.geo.iq_pairs])
         out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
         _check(lib().fmrx_process_shared(self.h, _np_ptr(iq), nb, _np_ptr(out)))
         return out if self.n_streams > 1 else out[0]
@@ -418,9 +486,9 @@ class Receiver:
 
     # ---- band scan: which offsets of a capture hold a station
     def scan_spectrum(self, iq: np.ndarray, fft_bins: int = 4096) -> tuple[np.ndarray, int]:
-        """Welch power spectrum of a u8 I/Q capture (fmrx_scan_spectrum): (power, n_segments), power
+        """Welch power spectrum of a raw I/Q capture (fmrx_scan_spectrum): (power, n_segments), power
         linear and FFT-shifted, bin j at (j - fft_bins / 2) * rf_fs / fft_bins Hz."""
-        iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+        iq = self._raw(iq).reshape(-1)
         power = np.zeros(max(fft_bins, 0), np.float32)
         nseg = _sz()
         _check(lib().fmrx_scan_spectrum(self.h, _np_ptr(iq), iq.size // 2, fft_bins, _np_ptr(power), C.byref(nseg)))
@@ -430,9 +498,9 @@ class Receiver:
         _check(lib().fmrx_scan_spectrum_device(self.h, d_iq, n_pairs, fft_bins, d_power))
 
     def scan(self, iq: np.ndarray, max_out: int = MAX_STATIONS, **cfg) -> list:
-        """fmrx_scan: the stations of a u8 I/Q capture, ascending by offset (settings: ScanConfig's
+        """fmrx_scan: the stations of a raw I/Q capture, ascending by offset (settings: ScanConfig's
         fields)."""
-        iq = np.ascontiguousarray(iq, np.uint8).reshape(-1)
+        iq = self._raw(iq).reshape(-1)
         out = (Station * max(max_out, 1))()
         n = C.c_int()
         _check(lib().fmrx_scan(self.h, _np_ptr(iq), iq.size // 2, C.byref(scan_config(**cfg)), out, max_out,
@@ -483,13 +551,13 @@ class Receiver:
 
     def seek(self, prev, n: int | None = None) -> None:
         """Continue, on the next call, a stream whose preceding bytes are `prev`: a host
-        array (n_streams x n u8, or 1-D for one stream) or, with `n` given, a device address
+        array (n_streams x n elements of the input format, or 1-D for one stream) or, with `n` given, a device address
         of n_streams x n bytes."""
         if n is not None:
             _check(lib().fmrx_seek(self.h, prev, n, 1))
             return
-        a = np.ascontiguousarray(np.asarray(prev, np.uint8).reshape(self.cfg.n_streams, -1))
-        _check(lib().fmrx_seek(self.h, a.ctypes.data, a.shape[1], 0))
+        a = np.ascontiguousarray(self._raw(prev).reshape(self.cfg.n_streams, -1))
+        _check(lib().fmrx_seek(self.h, a.ctypes.data, a.shape[1] * a.itemsize, 0))
 
     # ---- filter.h primitives on device pointers
     def resample(self, d_out, d_state, d_in, n_in, d_coeff, taps, up, down) -> int:
