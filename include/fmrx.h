@@ -245,6 +245,58 @@ int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_sca
 int fmrx_scan(fmrx_ctx* ctx, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg,
               fmrx_station* out, int max_out, int* n_found);
 
+/* ---- wide captures: a decimating down-converter ahead of the tuner ------------------------------- */
+/* A capture at cap_fs = decim * rf_fs (decim an integer in 2..10; the radios deliver 8-20 MS/s) goes
+ * through a per-station down-converter on the GPU (csrc/wide.hip) down to rf_fs, then
+ * through the tuned front end of fmrx_tune unchanged.  An offset f Hz (|f| < cap_fs / 2) splits into
+ *   q = sign(f) ((8 |f| + rf_fs) / (2 rf_fs)) (integer division), f_c = q rf_fs / 4, f_r = f - f_c,
+ * so |f_r| <= rf_fs / 8.  Wide pair n (absolute index; x_i, x_q the format's normalised samples) is
+ * rotated at the capture rate with N = 4 decim / gcd(|q|, 4 decim), k = (q / gcd) mod N, p = (k n) mod N
+ * and the table of fmrx_tuner_design's form: I' = fl(fl(x_i c[p]) + fl(x_q s[p])), Q' = fl(fl(x_q c[p]) -
+ * fl(x_i s[p])); then h = fmrx_impulse_response_lpf(cap_fs, 3 rf_fs / 8, 16 decim + 1, 1) and
+ *   y[m] = sum_k h[k] (I', Q')[decim m - k], acc = fl(acc + fl(h[k] x)) from 0 in ascending k,
+ * pairs in front of the stream being 0.  The pairs y[m] are a cf32 stream at rf_fs that takes the path
+ * of an FMRX_IQ_F32 stream tuned to f_r, pair m at absolute index first_pair / decim + m.
+ * fmrx_wide_design is host only: the split, N, k, the table (2 N <= 80 floats c0, s0, c1, s1, ...) and the
+ * taps (*taps = 16 decim + 1 floats in h); every output pointer may be NULL.  FMRX_EINVAL, nothing
+ * written: decim outside 2..10, rf_fs not a positive multiple of 4, |f| >= cap_fs / 2, a fine part
+ * fmrx_tuner_design refuses (every multiple of 1 kHz passes).                                        */
+int fmrx_wide_design(int rf_fs, int decim, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k,
+                     float* cos_sin, int* taps, float* h);
+/* decim = 1 (the default): no wide stage.  2..10: allocates the wide state (the last 16 decim raw pairs
+ * of the capture, the cf32 rows, an f32 halo for the narrow stage: all separate from what the ordinary
+ * calls use), then does what fmrx_reset does.  The input format stays the capture's; a later
+ * fmrx_set_input_format keeps decim.  FMRX_EINVAL: decim outside 1..10; no tuned kernel for the mode and
+ * tap count (rf_taps other than 51 and 101).  While decim > 1, fmrx_get_state, fmrx_set_state and
+ * fmrx_seek return FMRX_ESTATE; fmrx_reset clears the wide state too and keeps offsets and decim.
+ * Changing decim turns wide tuning off (fmrx_tune_wide again); back at 1 the tuner keeps the fine
+ * offsets fmrx_tune_wide gave it until the next fmrx_tune.                                           */
+int fmrx_set_capture_decim(fmrx_ctx* ctx, int decim);
+int fmrx_capture_decim(const fmrx_ctx* ctx, int* decim);
+/* n_streams offsets against cap_fs; first_pair: absolute wide-pair index of the next call's first pair,
+ * a multiple of decim (FMRX_EINVAL otherwise).  Stores the coarse tables and hands the fine parts and
+ * first_pair / decim to the tuner state of fmrx_tune (fmrx_tuner_info then shows them; a later fmrx_tune
+ * turns wide tuning off).  On any refusal nothing changes.  FMRX_ESTATE while decim is 1.             */
+int fmrx_tune_wide(fmrx_ctx* ctx, const int32_t* offsets_hz, uint64_t first_pair);
+/* read back: the wide offsets, the next absolute wide-pair index, 1/0 wide tuning (each may be NULL) */
+int fmrx_wide_info(fmrx_ctx* ctx, int32_t* offsets_hz, uint64_t* next_pair, int* enabled);
+/* ONE capture read by every stream: iq holds n_blocks blocks of decim * geo.iq_pairs wide pairs in the
+ * context's input format; pcm as fmrx_process.  Any split of a capture into calls gives the same bits.
+ * Long calls run in internal pieces of whole blocks, so the cf32 rows stay bounded.  Stereo contexts
+ * take the non-pipelined engine.  FMRX_ESTATE without fmrx_tune_wide.  The device form is asynchronous
+ * on the context stream; d_iq is aligned to two pairs of the format (FMRX_EINVAL and no launch
+ * otherwise).  fmrx_kernel_timing, when armed, times the down-converter's launches.                 */
+int fmrx_process_wide(fmrx_ctx* ctx, const uint8_t* iq, size_t n_blocks, int16_t* pcm);
+int fmrx_process_wide_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
+/* fmrx_scan_detect with rf_fs := decim * rf_fs (bin j at (j - N/2) cap_fs / N Hz) and "a candidate
+ * fmrx_wide_design refuses" in place of "fmrx_tuner_design refuses"; host only.                      */
+int fmrx_scan_detect_wide(const float* power, int fft_bins, int rf_fs, int decim, const fmrx_scan_config* cfg,
+                          fmrx_station* out, int max_out, int* n_found, float* floor_db);
+/* fmrx_scan on a wide capture: the same spectrum kernel, then fmrx_scan_detect_wide with the context's
+ * rf_fs and decim; every reported offset can go straight into fmrx_tune_wide.  FMRX_ESTATE at decim 1. */
+int fmrx_scan_wide(fmrx_ctx* ctx, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg,
+                   fmrx_station* out, int max_out, int* n_found);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

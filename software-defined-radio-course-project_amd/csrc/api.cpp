@@ -20,6 +20,7 @@
 #include "scan.h"
 #include "synth.h"
 #include "tuner.h"
+#include "wide.h"
 
 using namespace fmrx;
 
@@ -184,6 +185,19 @@ struct fmrx_ctx {
     DevBuf<float> d_scan_part;                // the launch's partial rows (scan_workgroups x N)
     DevBuf<float> d_scan_power;               // the host entry points' result, N floats
     DevBuf<uint8_t> d_scan_in;                // the host entry points' capture
+    // wide captures (fmrx_set_capture_decim): the down-converter in front of the tuner (wide.hip);
+    // its history, rows and narrow halo are its own, nothing the ordinary calls read
+    int wide_decim = 1;                       // cap_fs / rf_fs; 1: no wide stage
+    bool wide_tuned = false;                  // fmrx_tune_wide accepted (fmrx_tune turns it off)
+    std::vector<int32_t> wide_offsets;        // n_streams, against cap_fs
+    DevBuf<uint8_t> d_wide_hist;              // the 16 decim raw pairs of the capture in front of the next call
+    DevBuf<float> d_wide_taps;                // the 16 decim + 1 taps of the low-pass
+    DevBuf<float> d_wide_tab;                 // n_streams x kWideMaxN (c, s) pairs: the coarse tables
+    DevBuf<uint32_t> d_wide_streams;          // WideStream per stream
+    DevBuf<float> d_wide_y;                   // n_streams x wide_y_stride floats: one piece's cf32 rows at rf_fs
+    size_t wide_y_stride = 0;
+    DevBuf<uint8_t> d_wide_halo[2];           // the narrow stage's f32 halo (halo_pairs x 8 B a stream)
+    int wide_halo_cur = 0;
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -260,8 +274,8 @@ size_t iq_block_bytes(const fmrx_ctx* c) { return c->geo.iq_pairs * c->pair_byte
 bool front_tuned(const fmrx_ctx* c) { return c->tuned || c->iq_format != kIqU8; }
 // n_streams rows of n_blocks blocks in format bytes must fit size_t with room to spare (a block of
 // f32 is four times a block of u8)
-int check_call_size(const fmrx_ctx* c, size_t n_blocks) {
-    const size_t per_block = (size_t)c->cfg.n_streams * c->geo.iq_pairs * 8;
+int check_call_size(const fmrx_ctx* c, size_t n_blocks, size_t decim = 1) {
+    const size_t per_block = (size_t)c->cfg.n_streams * c->geo.iq_pairs * 8 * decim;  // decim: a wide block
     if (n_blocks > (std::numeric_limits<size_t>::max() / 4) / per_block)
         return fail(FMRX_EINVAL, "%zu blocks: the call's byte count overflows", n_blocks);
     return 0;
@@ -280,6 +294,13 @@ int reset_state(fmrx_ctx* c) {
     HIPCHK(hipMemsetAsync(c->d_halo[0].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     HIPCHK(hipMemsetAsync(c->d_halo[1].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     c->halo_cur = 0;
+    if (c->wide_decim > 1) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
+        const size_t nh = c->halo_pairs * 8 * ns;
+        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), 16 * (size_t)c->wide_decim * c->pair_bytes, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_wide_halo[0].p, 0, nh, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_wide_halo[1].p, 0, nh, c->stream));
+        c->wide_halo_cur = 0;
+    }
     HIPCHK(hipMemsetAsync(c->d_audio_hist.p, 0, sizeof(float) * c->audio_hist * ns, c->stream));
     c->audio_hist_stale = false;
     if (c->d_demod.p)  // the history in front of each stream (every call overwrites the rest)
@@ -914,6 +935,87 @@ int tuner_upload(fmrx_ctx* c, const int32_t* offsets_hz) {
     return FMRX_OK;
 }
 
+// y rows of one internal piece of a wide call: at most this many bytes over all streams (a piece
+// is a whole number of blocks, at least one)
+constexpr size_t kWidePieceBytes = (size_t)128 << 20;
+
+// A wide call (fmrx_process_wide_device; arguments checked, device set): per piece of whole blocks
+// the down-converter (wide.hip) into the y rows, then the tuned front end reading them as an f32
+// stream with the wide stage's own halo; the demod rows of the whole call then take the audio stage
+// a tuned call takes.  A piece past the first finds its history in the capture itself.
+int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    const int ns = c->cfg.n_streams, D = c->wide_decim;
+    const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples;
+    const size_t wide_block = (size_t)D * iq_block_bytes(c), hb = 16 * (size_t)D * c->pair_bytes;
+    int rc = ensure_demod(c, n_if);
+    if (rc) return rc;
+    const size_t piece = std::min(n_blocks, std::max<size_t>(1, kWidePieceBytes / ((size_t)ns * ip * 8)));
+    if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->wide_y_stride = 0;
+        if ((rc = c->d_wide_y.ensure((size_t)ns * piece * ip * 2))) return rc;
+        c->wide_y_stride = piece * ip * 2;
+    }
+    const size_t nhb = c->halo_pairs * 8;
+    for (size_t b0 = 0; b0 < n_blocks; b0 += piece) {
+        const size_t nb = std::min(piece, n_blocks - b0);
+        WideLaunch W{};
+        W.iq = d_iq + b0 * wide_block;
+        W.hist = b0 == 0 ? c->d_wide_hist.p : W.iq - hb;
+        W.stream_bytes = nb * wide_block;
+        W.y = c->d_wide_y.p;
+        W.y_stride = c->wide_y_stride;
+        W.n_out = (long long)(nb * ip);
+        W.segs = wide_segments(W.n_out, D, ns, c->n_simd / 4);
+        W.format = c->iq_format;
+        W.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
+        W.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
+        W.h = c->d_wide_taps.p;
+        W.first_pair = c->tune_pos * (uint64_t)D;
+        std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+        if (c->timing) {  // fmrx_kernel_timing: the down-converter's launches
+            if (c->ev_used == c->evs.size()) {
+                std::pair<hipEvent_t, hipEvent_t> e{nullptr, nullptr};
+                HIPCHK(hipEventCreate(&e.first));
+                HIPCHK(hipEventCreate(&e.second));
+                c->evs.push_back(e);
+            }
+            ev = &c->evs[c->ev_used++];
+            HIPCHK(hipEventRecord(ev->first, c->stream));
+        }
+        rc = launch_wide_ddc(W, ns, D, c->stream);
+        if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "down-converter launch failed (%d)", rc);
+        if (ev) HIPCHK(hipEventRecord(ev->second, c->stream));
+        TunerLaunch L{};
+        L.iq = reinterpret_cast<const uint8_t*>(c->d_wide_y.p);
+        L.iq_stride = c->wide_y_stride * sizeof(float);
+        L.halo = c->d_wide_halo[c->wide_halo_cur].p;
+        L.halo_next = c->d_wide_halo[c->wide_halo_cur ^ 1].p;
+        L.halo_bytes = nhb;
+        L.stream_bytes = nb * ip * 8;
+        L.format = kIqF32;
+        L.demod = c->d_demod.p + b0 * c->geo.if_samples;
+        L.demod_stride = c->demod_stride;
+        L.demod_hist = kDemodHist;
+        L.pre_tail = 0;
+        L.n_if = (long long)(nb * c->geo.if_samples);
+        L.segs = tuner_segments(L.n_if, c->geo.rf_taps, c->geo.rf_decim, ns, c->n_simd / 4, c->tune_max_n);
+        L.streams = reinterpret_cast<const TunerStream*>(c->d_tune_streams.p);
+        L.tables = reinterpret_cast<const float2*>(c->d_tune_tab.p);
+        L.first_pair = c->tune_pos;
+        const int st_t = c->stage_timer.begin(c->stream);
+        rc = launch_tuner(L, ns, c->geo.rf_taps, c->geo.rf_decim, c->tune_max_n, c->mono_taps, c->stream);
+        c->stage_timer.end(st_t, kStFront, 0.0, c->stream);
+        if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "tuned front end launch failed (%d)", rc);
+        c->wide_halo_cur ^= 1;
+        c->tune_pos += (uint64_t)nb * ip;
+    }
+    // the next call's history: the capture's last 16 decim pairs (a block holds more than that)
+    HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + n_blocks * wide_block - hb, hb, hipMemcpyDeviceToDevice, c->stream));
+    if (c->cfg.channels != FMRX_MONO) return run_stereo_audio(c, n_blocks, d_pcm, nullptr);
+    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1150,6 +1252,7 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
             return cleanup(fail(FMRX_EHIP, "tap upload failed"));
     }
     c->tune_offsets.assign((size_t)ns, 0);
+    c->wide_offsets.assign((size_t)ns, 0);
     if ((rc = reset_state(c))) return cleanup(rc);
     *out = c;
     return FMRX_OK;
@@ -1169,6 +1272,8 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_rds_pll.release();
     c->d_tune_tab.release(); c->d_tune_streams.release();
     c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
+    c->d_wide_hist.release(); c->d_wide_taps.release(); c->d_wide_tab.release(); c->d_wide_streams.release();
+    c->d_wide_y.release(); c->d_wide_halo[0].release(); c->d_wide_halo[1].release();
     for (auto& e : c->evs) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -1198,6 +1303,7 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     CtxLock lock_(c);
     if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
+    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
     if (n % c->pair_bytes != 0)
         return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
     int rc = set_device(c);
@@ -1305,12 +1411,14 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
 int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
 
 int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
     if (rc == 0) {
@@ -1395,6 +1503,7 @@ int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
             if (rc) return rc;
         }
         c->tuned = false;
+        c->wide_tuned = false;
         c->tune_pos = first_pair;
         return FMRX_OK;
     }
@@ -1403,6 +1512,7 @@ int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
     c->tune_offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
     c->tune_pos = first_pair;
     c->tuned = true;
+    c->wide_tuned = false;  // the tables are no longer the fine offsets of fmrx_tune_wide
     return FMRX_OK;
 }
 
@@ -1430,6 +1540,7 @@ int fmrx_set_input_format(fmrx_ctx* c, int format) {
             if ((rc = tuner_upload(c, zeros.data()))) return rc;
         }
         if ((rc = c->d_halo[0].ensure(hb * ns)) || (rc = c->d_halo[1].ensure(hb * ns))) return rc;
+        if (c->wide_decim > 1 && (rc = c->d_wide_hist.ensure(16 * (size_t)c->wide_decim * (size_t)pb))) return rc;
         c->iq_format = format;
         c->pair_bytes = (size_t)pb;
         c->halo_bytes = hb;
@@ -1451,6 +1562,116 @@ int fmrx_tuner_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* 
     if (next_pair) *next_pair = c->tune_pos;
     if (enabled) *enabled = c->tuned ? 1 : 0;
     return FMRX_OK;
+}
+
+// ---- wide captures: the decimating down-converter ahead of the tuner ------------------------------
+int fmrx_wide_design(int rf_fs, int decim, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k, float* cos_sin,
+                     int* taps, float* h) {
+    if (decim < kWideMinDecim || decim > kWideMaxDecim)
+        return fail(FMRX_EINVAL, "capture decimation %d outside %d..%d", decim, kWideMinDecim, kWideMaxDecim);
+    if (rf_fs <= 0 || rf_fs % 4 != 0) return fail(FMRX_EINVAL, "rf_fs %d is not a positive multiple of 4", rf_fs);
+    int fc = 0, fr = 0, n = 0, kk = 0;
+    if (!wide_split(rf_fs, decim, offset_hz, &fc, &fr, &n, &kk, nullptr))
+        return fail(FMRX_EINVAL, "offset %d Hz outside (-%d %d/2, %d %d/2)", offset_hz, decim, rf_fs, decim, rf_fs);
+    int tn = 0, tk = 0;
+    const int rc = fmrx_tuner_design(rf_fs, fr, &tn, &tk, nullptr);  // the fine part goes to the tuner
+    if (rc) return rc;
+    if (coarse_hz) *coarse_hz = fc;
+    if (fine_hz) *fine_hz = fr;
+    if (N) *N = n;
+    if (k) *k = kk;
+    if (cos_sin) wide_split(rf_fs, decim, offset_hz, nullptr, nullptr, nullptr, nullptr, cos_sin);
+    if (taps) *taps = wide_taps(decim);
+    if (h) design_lpf(h, (float)rf_fs * (float)decim, (float)(3.0 * rf_fs / 8.0), wide_taps(decim), 1);
+    return FMRX_OK;
+}
+
+int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (decim != 1 && (decim < kWideMinDecim || decim > kWideMaxDecim))
+        return fail(FMRX_EINVAL, "capture decimation %d outside 1..%d", decim, kWideMaxDecim);
+    if (decim == 1 && c->wide_decim == 1) return FMRX_OK;  // the default: nothing anywhere changes
+    if (decim > 1 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
+                    c->geo.rf_decim);
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the wide state
+    if (decim > 1) {
+        const size_t ns = c->cfg.n_streams;
+        std::vector<float> h((size_t)wide_taps(decim));
+        design_lpf(h.data(), (float)c->geo.rf_fs * (float)decim, (float)(3.0 * c->geo.rf_fs / 8.0), wide_taps(decim), 1);
+        if ((rc = c->d_wide_hist.ensure(16 * (size_t)decim * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(h.size())) ||
+            (rc = c->d_wide_tab.ensure(2 * (size_t)kWideMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
+            (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
+            return rc;
+        HIPCHK(hipMemcpy(c->d_wide_taps.p, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+    }
+    c->wide_decim = decim;
+    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
+    return reset_state(c);
+}
+
+int fmrx_capture_decim(const fmrx_ctx* c, int* decim) {
+    CtxLock lock_(c);
+    if (!c || !decim) return fail(FMRX_EINVAL, "null argument");
+    *decim = c->wide_decim;
+    return FMRX_OK;
+}
+
+int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    CtxLock lock_(c);
+    if (!c || !offsets_hz) return fail(FMRX_EINVAL, "null argument");
+    const int D = c->wide_decim;
+    if (D == 1) return fail(FMRX_ESTATE, "fmrx_tune_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
+    if (first_pair % (uint64_t)D != 0)
+        return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of the decimation %d",
+                    (unsigned long long)first_pair, D);
+    const size_t ns = c->cfg.n_streams;
+    std::vector<int32_t> fine(ns);
+    std::vector<WideStream> ws(ns);
+    std::vector<float> tab(2 * (size_t)kWideMaxN * ns, 0.0f);
+    int rc;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int fr = 0, n = 0, k = 0;
+        if ((rc = fmrx_wide_design(c->geo.rf_fs, D, offsets_hz[s], nullptr, &fr, &n, &k, tab.data() + 2 * kWideMaxN * s,
+                                   nullptr, nullptr)))
+            return rc;
+        fine[s] = fr;
+        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
+    }
+    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
+    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
+    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
+    c->tune_pos = first_pair / (uint64_t)D;
+    c->tuned = true;
+    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
+    c->wide_tuned = true;
+    return FMRX_OK;
+}
+
+int fmrx_wide_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (offsets_hz) std::copy(c->wide_offsets.begin(), c->wide_offsets.end(), offsets_hz);
+    if (next_pair) *next_pair = c->tune_pos * (uint64_t)c->wide_decim;
+    if (enabled) *enabled = c->wide_tuned ? 1 : 0;
+    return FMRX_OK;
+}
+
+int fmrx_process_wide_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    CtxLock lock_(c);
+    if (!c || !d_iq || !d_pcm) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim == 1 || !c->wide_tuned)
+        return fail(FMRX_ESTATE, "fmrx_process_wide_device: wide tuning is off (fmrx_set_capture_decim, fmrx_tune_wide first)");
+    if (n_blocks == 0) return FMRX_OK;
+    if (reinterpret_cast<uintptr_t>(d_iq) % (2 * c->pair_bytes) != 0)
+        return fail(FMRX_EINVAL, "wide calls need a %zu-byte aligned capture", 2 * c->pair_bytes);
+    int rc = check_call_size(c, n_blocks, (size_t)c->wide_decim);
+    if (rc || (rc = set_device(c))) return rc;
+    return run_wide(c, d_iq, n_blocks, d_pcm);
 }
 
 int fmrx_synchronize(fmrx_ctx* c) {
@@ -1550,6 +1771,26 @@ int fmrx_process(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) 
 
 int fmrx_process_shared(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) {
     return process_host(c, iq, n_blocks, pcm, true);
+}
+
+// one wide capture (n_blocks * decim * iq_pairs pairs) read by every stream
+int fmrx_process_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm) {
+    CtxLock lock_(c);
+    if (!c || !iq || !pcm) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim == 1 || !c->wide_tuned)
+        return fail(FMRX_ESTATE, "fmrx_process_wide: wide tuning is off (fmrx_set_capture_decim, fmrx_tune_wide first)");
+    if (n_blocks == 0) return FMRX_OK;
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = check_call_size(c, n_blocks, (size_t)c->wide_decim))) return rc;
+    const size_t in_bytes = n_blocks * (size_t)c->wide_decim * iq_block_bytes(c);
+    const size_t out_n = (size_t)c->cfg.n_streams * n_blocks * c->geo.pcm_samples;
+    if ((rc = c->d_in.ensure(in_bytes)) || (rc = c->d_out.ensure(out_n))) return rc;
+    HIPCHK(hipMemcpyAsync(c->d_in.p, iq, in_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = fmrx_process_wide_device(c, c->d_in.p, n_blocks, c->d_out.p))) return rc;
+    HIPCHK(hipMemcpyAsync(pcm, c->d_out.p, out_n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FMRX_OK;
 }
 
 // rf_thread body (project.cpp:48-70): u8 blocks -> demod floats.
@@ -1800,8 +2041,11 @@ int fmrx_scan_spectrum(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int fft_b
     return FMRX_OK;
 }
 
-int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_scan_config* cfg_in, fmrx_station* out,
-                     int max_out, int* n_found, float* floor_db) {
+namespace {
+// The detector of fmrx_scan_detect (decim = 1) and fmrx_scan_detect_wide (decim > 1: rf_fs is then the
+// capture's rate, and a candidate is checked by fmrx_wide_design instead of fmrx_tuner_design).
+int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, const fmrx_scan_config* cfg_in, fmrx_station* out,
+                    int max_out, int* n_found, float* floor_db) {
     fmrx_scan_config cfg;
     (void)fmrx_scan_config_default(&cfg);
     if (cfg_in) cfg = *cfg_in;
@@ -1831,7 +2075,9 @@ int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_sca
     for (long long m = m_lo; m <= m_hi; m++) {
         const long long f = org + m * ras;
         int tn = 0, tk = 0;
-        const int rc = fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr);  // every reported offset can be tuned to
+        // every reported offset can be tuned to
+        const int rc = decim == 1 ? fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr)
+                                  : fmrx_wide_design(rf_fs / decim, decim, (int)f, nullptr, nullptr, &tn, &tk, nullptr, nullptr, nullptr);
         if (rc) return rc;
         cands.push_back(Cand{f, 0.0, 0, 0.0});
     }
@@ -1882,24 +2128,53 @@ int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_sca
     return FMRX_OK;
 }
 
-int fmrx_scan(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
+// fmrx_scan and fmrx_scan_wide: spectrum + detect at the rate of the capture
+int scan_both(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int decim, const fmrx_scan_config* cfg_in, fmrx_station* out,
               int max_out, int* n_found) {
-    CtxLock lock_(c);
-    if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
     fmrx_scan_config cfg;
     (void)fmrx_scan_config_default(&cfg);
     if (cfg_in) cfg = *cfg_in;
+    const int fs = c->geo.rf_fs * decim;
     int rc = scan_check_size(cfg.fft_bins, n_pairs);
     if (rc) return rc;
     {  // refuse a bad detector configuration before any GPU work
         std::vector<float> flat((size_t)cfg.fft_bins, 1.0f);
         std::vector<fmrx_station> tmp((size_t)std::max(max_out, 0));
         int n = 0;
-        if ((rc = fmrx_scan_detect(flat.data(), cfg.fft_bins, c->geo.rf_fs, &cfg, tmp.data(), max_out, &n, nullptr))) return rc;
+        if ((rc = scan_detect_run(flat.data(), cfg.fft_bins, fs, decim, &cfg, tmp.data(), max_out, &n, nullptr))) return rc;
     }
     std::vector<float> power((size_t)cfg.fft_bins);
     if ((rc = fmrx_scan_spectrum(c, iq, n_pairs, cfg.fft_bins, power.data(), nullptr))) return rc;
-    return fmrx_scan_detect(power.data(), cfg.fft_bins, c->geo.rf_fs, &cfg, out, max_out, n_found, nullptr);
+    return scan_detect_run(power.data(), cfg.fft_bins, fs, decim, &cfg, out, max_out, n_found, nullptr);
+}
+}  // namespace
+
+int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_scan_config* cfg_in, fmrx_station* out,
+                     int max_out, int* n_found, float* floor_db) {
+    return scan_detect_run(power, fft_bins, rf_fs, 1, cfg_in, out, max_out, n_found, floor_db);
+}
+
+int fmrx_scan_detect_wide(const float* power, int fft_bins, int rf_fs, int decim, const fmrx_scan_config* cfg_in,
+                          fmrx_station* out, int max_out, int* n_found, float* floor_db) {
+    if (decim < kWideMinDecim || decim > kWideMaxDecim)
+        return fail(FMRX_EINVAL, "capture decimation %d outside %d..%d", decim, kWideMinDecim, kWideMaxDecim);
+    if (rf_fs <= 0 || rf_fs % 4 != 0) return fail(FMRX_EINVAL, "rf_fs %d is not a positive multiple of 4", rf_fs);
+    return scan_detect_run(power, fft_bins, rf_fs * decim, decim, cfg_in, out, max_out, n_found, floor_db);
+}
+
+int fmrx_scan_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
+                   int max_out, int* n_found) {
+    CtxLock lock_(c);
+    if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim == 1) return fail(FMRX_ESTATE, "fmrx_scan_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
+    return scan_both(c, iq, n_pairs, c->wide_decim, cfg_in, out, max_out, n_found);
+}
+
+int fmrx_scan(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
+              int max_out, int* n_found) {
+    CtxLock lock_(c);
+    if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
+    return scan_both(c, iq, n_pairs, 1, cfg_in, out, max_out, n_found);
 }
 
 // ---- filter.h primitives ---------------------------------------------------------------

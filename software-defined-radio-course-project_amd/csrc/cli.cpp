@@ -1,5 +1,5 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
-// [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32]`:
+// [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -20,6 +20,10 @@
 //     int16 or float32 pairs (fmrx_set_input_format), in blocks of iq_pairs times the pair's bytes;
 //     with a format other than u8 and no --offset-hz the station at offset 0 is decoded; --scan-bytes
 //     counts bytes of that format.  Without the flag nothing differs from before.
+//   * --capture-decim D (an fmrx extension, D in 1..10, default 1) reads stdin as a capture at D times
+//     the mode's rate (fmrx_set_capture_decim): blocks of D * iq_pairs pairs, --offset-hz against that
+//     rate (fmrx_tune_wide; without it offset 0), decoded by fmrx_process_wide_device; --scan then runs
+//     fmrx_scan_wide.  D = 1 is the same as no flag; anything else outside 2..10: message, exit 1.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -89,6 +93,8 @@ void usage(const char* argv0) {
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
                  "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
+                 "                [--capture-decim D]  stdin runs at D (2..10) times the mode's rate; --offset-hz and\n"
+                 "                                     --scan then refer to that rate (default 1)\n"
                  "                [--scan [--scan-bytes B]]  list the stations of the first B bytes (default 16777216)\n"
                  "                                           as `offset_hz power_db snr_db` lines; no PCM\n",
                  argv0, argv0);
@@ -101,7 +107,7 @@ void usage(const char* argv0) {
 }
 
 // --scan: the stations in the first max_bytes of stdin, one line each
-int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes) {
+int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
     fmrx_scan_config sc;
     (void)fmrx_scan_config_default(&sc);
     std::vector<uint8_t> iq(max_bytes);
@@ -119,7 +125,7 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes) {
     constexpr int kMaxStations = 256;
     fmrx_station st[kMaxStations];
     int n = 0;
-    if (fmrx_scan(ctx, iq.data(), got / pair_bytes, &sc, st, kMaxStations, &n) != FMRX_OK) {
+    if ((wide ? fmrx_scan_wide : fmrx_scan)(ctx, iq.data(), got / pair_bytes, &sc, st, kMaxStations, &n) != FMRX_OK) {
         std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
         return 1;
     }
@@ -141,7 +147,7 @@ int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
     bool mono_product = false, tuned = false, scan = false;
     long offset_hz = 0;
-    int iq_format = FMRX_IQ_U8;
+    int iq_format = FMRX_IQ_U8, capture_decim = 1;
     const char* bad_format = nullptr;
     long long scan_bytes = 1ll << 24;
     std::vector<const char*> pos;
@@ -160,6 +166,7 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(f, "f32")) iq_format = FMRX_IQ_F32;
             else bad_format = f;
         }
+        else if (!std::strcmp(argv[i], "--capture-decim") && i + 1 < argc) capture_decim = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) {
             offset_hz = std::atol(argv[++i]);
             tuned = true;
@@ -184,6 +191,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "fmrx: --iq-format %s: expected u8, s8, s16 or f32\n", bad_format);
         return 1;
     }
+    if (capture_decim < 1 || capture_decim > 10) {
+        std::fprintf(stderr, "fmrx: --capture-decim %d: expected 1 to 10\n", capture_decim);
+        return 1;
+    }
+    const bool wide = capture_decim > 1;
     if (batch < 1) batch = 1;
     std::fprintf(stderr, "Operating in mode %d, %s\n", mode, channels == 1 ? "mono" : "stereo");
 
@@ -207,17 +219,22 @@ int main(int argc, char** argv) {
         fmrx_destroy(ctx);
         return 1;
     }
+    if (wide && fmrx_set_capture_decim(ctx, capture_decim) != FMRX_OK) {
+        std::fprintf(stderr, "fmrx: --capture-decim: %s\n", fmrx_last_error());
+        fmrx_destroy(ctx);
+        return 1;
+    }
     const size_t pair_bytes = (size_t)fmrx_iq_pair_bytes(iq_format);
-    const size_t block_bytes = geo.iq_pairs * pair_bytes;  // geo.block_bytes for u8
+    const size_t block_bytes = geo.iq_pairs * pair_bytes * (size_t)capture_decim;  // geo.block_bytes for u8
     if (scan) {
-        const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes, pair_bytes) : 1;
+        const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes, pair_bytes, wide) : 1;
         if (scan_bytes <= 0) std::fprintf(stderr, "fmrx: --scan-bytes must be positive\n");
         fmrx_destroy(ctx);
         return rc;
     }
-    if (tuned) {  // out of range (or no 32-bit value) -> message, exit 1
+    if (tuned || wide) {  // out of range (or no 32-bit value) -> message, exit 1
         const int32_t f = (int32_t)offset_hz;
-        if ((long)f != offset_hz || fmrx_tune(ctx, &f, 0) != FMRX_OK) {
+        if ((long)f != offset_hz || (wide ? fmrx_tune_wide : fmrx_tune)(ctx, &f, 0) != FMRX_OK) {
             std::fprintf(stderr, "fmrx: --offset-hz %ld: %s\n", offset_hz,
                          (long)f != offset_hz ? "out of range" : fmrx_last_error());
             fmrx_destroy(ctx);
@@ -282,7 +299,7 @@ int main(int argc, char** argv) {
             CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks * block_bytes, hipMemcpyHostToDevice, up));
             CLI_HIP(hipEventRecord(s.uploaded, up));
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
-            if (fmrx_process_device(ctx, s.d_in, s.blocks, s.d_out) != FMRX_OK) {
+            if ((wide ? fmrx_process_wide_device : fmrx_process_device)(ctx, s.d_in, s.blocks, s.d_out) != FMRX_OK) {
                 std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
                 std::fflush(stdout);
                 std::_Exit(1);

@@ -101,6 +101,17 @@ PROTOTYPES = {
     "fmrx_scan_detect": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int,
                                    C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "fmrx_scan": (C.c_int, [_vp, _vp, _sz, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int, C.POINTER(C.c_int)]),
+    "fmrx_wide_design": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), _vp, C.POINTER(C.c_int), _vp]),
+    "fmrx_set_capture_decim": (C.c_int, [_vp, C.c_int]),
+    "fmrx_capture_decim": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "fmrx_tune_wide": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "fmrx_wide_info": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "fmrx_process_wide": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_process_wide_device": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_scan_detect_wide": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "fmrx_scan_wide": (C.c_int, [_vp, _vp, _sz, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int, C.POINTER(C.c_int)]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -216,6 +227,18 @@ def tuner_design(rf_fs: int, offset_hz: int) -> tuple[int, int, np.ndarray]:
     return n.value, k.value, tab
 
 
+def wide_design(rf_fs: int, decim: int, offset_hz: int) -> dict:
+    """fmrx_wide_design: how an offset against a capture at decim * rf_fs splits and what the
+    down-converter runs with.  A dict: coarse_hz, fine_hz, N, k, table (N x 2 float32: c[p], s[p]),
+    h (the 16 decim + 1 float32 taps)."""
+    fc, fr, n, k, t = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    _check(lib().fmrx_wide_design(rf_fs, decim, offset_hz, C.byref(fc), C.byref(fr), C.byref(n), C.byref(k), None,
+                                  C.byref(t), None))
+    tab, h = np.zeros((n.value, 2), np.float32), np.zeros(t.value, np.float32)
+    _check(lib().fmrx_wide_design(rf_fs, decim, offset_hz, None, None, None, None, _np_ptr(tab), None, _np_ptr(h)))
+    return {"coarse_hz": fc.value, "fine_hz": fr.value, "N": n.value, "k": k.value, "table": tab, "h": h}
+
+
 def iq_pair_bytes(fmt: int) -> int:
     """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
     n = lib().fmrx_iq_pair_bytes(fmt)
@@ -271,12 +294,44 @@ def scan_detect(power: np.ndarray, rf_fs: int, max_out: int = MAX_STATIONS, **cf
     return _stations(out, min(n.value, max_out)), fl.value
 
 
-def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, **cfg):
+def scan_detect_wide(power: np.ndarray, rf_fs: int, decim: int, max_out: int = MAX_STATIONS, **cfg):
+    """fmrx_scan_detect_wide: scan_detect on the spectrum of a capture at decim * rf_fs; every reported
+    offset is one fmrx_wide_design accepts.  Host only."""
+    p = np.ascontiguousarray(power, np.float32).reshape(-1)
+    out = (Station * max(max_out, 1))()
+    n, fl = C.c_int(), C.c_float()
+    _check(lib().fmrx_scan_detect_wide(_np_ptr(p), p.size, rf_fs, decim, C.byref(scan_config(**cfg)), out, max_out,
+                                       C.byref(n), C.byref(fl)))
+    return _stations(out, min(n.value, max_out)), fl.value
+
+
+def _decode_stations_wide(iq, fmt, mode, channels, rf_taps, decim, cfg):
+    with Receiver(mode, channels, rf_taps=rf_taps) as rx:
+        if fmt != IQ_U8:
+            rx.set_input_format(fmt)
+        rx.set_capture_decim(decim)
+        stations = rx.scan_wide(iq, **cfg)
+    if not stations:
+        return [], np.zeros((0, 0), np.int16)
+    with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
+        if fmt != IQ_U8:
+            rx.set_input_format(fmt)
+        rx.set_capture_decim(decim)
+        rx.tune_wide([s.offset_hz for s in stations])
+        pcm = rx.process_wide(iq)
+    return stations, pcm.reshape(len(stations), -1)
+
+
+def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
+                    **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
-    ([], an empty array) when the scan finds none."""
+    ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
+    capture_decim times the mode's rate (scan_wide, tune_wide, process_wide)."""
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
     iq = _iq_flat(iq).reshape(-1)
+    if capture_decim != 1:
+        return _decode_stations_wide(iq, fmt, mode, channels, rf_taps, capture_decim, cfg)
     with Receiver(mode, channels, rf_taps=rf_taps) as rx:
         if fmt != IQ_U8:
             rx.set_input_format(fmt)
@@ -483,6 +538,58 @@ class Receiver:
 
     def process_shared_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
         _check(lib().fmrx_process_shared_device(self.h, d_iq, n_blocks, d_pcm))
+
+    # ---- wide captures: a capture at decim times the mode's rate
+    def set_capture_decim(self, decim: int) -> None:
+        """fmrx_set_capture_decim: 1 = no wide stage, 2..10 = the capture runs at decim * rf_fs; then a reset."""
+        _check(lib().fmrx_set_capture_decim(self.h, int(decim)))
+
+    @property
+    def capture_decim(self) -> int:
+        d = C.c_int()
+        _check(lib().fmrx_capture_decim(self.h, C.byref(d)))
+        return d.value
+
+    def tune_wide(self, offsets, first_pair: int = 0) -> None:
+        """fmrx_tune_wide: per-stream offsets in Hz against the capture's rate (an int for one stream);
+        first_pair is the absolute wide-pair index of the next call's first pair, a multiple of decim."""
+        off = np.ascontiguousarray(np.atleast_1d(np.asarray(offsets, dtype=np.int64)))
+        if off.size != self.n_streams:
+            raise ValueError(f"{off.size} offsets for {self.n_streams} streams")
+        if np.any(np.abs(off) >= 2 ** 31):
+            raise FmrxError(FMRX_EINVAL, "offset does not fit 32 bits")
+        off = off.astype(np.int32)
+        _check(lib().fmrx_tune_wide(self.h, _np_ptr(off), first_pair))
+
+    def wide_info(self) -> tuple[list[int], int, bool]:
+        """fmrx_wide_info: (wide offsets in Hz, next wide-pair index, wide tuning on)."""
+        off = np.zeros(self.n_streams, np.int32)
+        pos, on = C.c_uint64(), C.c_int()
+        _check(lib().fmrx_wide_info(self.h, _np_ptr(off), C.byref(pos), C.byref(on)))
+        return [int(v) for v in off], pos.value, bool(on.value)
+
+    def process_wide(self, iq: np.ndarray) -> np.ndarray:
+        """One wide capture (whole blocks of capture_decim * iq_pairs pairs) decoded by every stream
+        tuned with tune_wide: S16 PCM, n_streams rows."""
+        iq = self._raw(iq).reshape(-1)
+        per = 2 * self.geo.iq_pairs * self.capture_decim  # elements a wide block
+        nb = iq.size // per
+        iq = np.ascontiguousarray(iq[: nb * per])
+        out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
+        _check(lib().fmrx_process_wide(self.h, _np_ptr(iq), nb, _np_ptr(out)))
+        return out if self.n_streams > 1 else out[0]
+
+    def process_wide_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
+        _check(lib().fmrx_process_wide_device(self.h, d_iq, n_blocks, d_pcm))
+
+    def scan_wide(self, iq: np.ndarray, max_out: int = MAX_STATIONS, **cfg) -> list:
+        """fmrx_scan_wide: the stations of a wide capture, ascending by offset against its centre."""
+        iq = self._raw(iq).reshape(-1)
+        out = (Station * max(max_out, 1))()
+        n = C.c_int()
+        _check(lib().fmrx_scan_wide(self.h, _np_ptr(iq), iq.size // 2, C.byref(scan_config(**cfg)), out, max_out,
+                                    C.byref(n)))
+        return _stations(out, min(n.value, max_out))
 
     # ---- band scan: which offsets of a capture hold a station
     def scan_spectrum(self, iq: np.ndarray, fft_bins: int = 4096) -> tuple[np.ndarray, int]:
