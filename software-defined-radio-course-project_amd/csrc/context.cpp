@@ -1,0 +1,609 @@
+// context.cpp — the context of the C ABI (include/fmrx.h): error text, configuration and geometry,
+// knobs, creation and destruction, reset and seek, the state blob, synchronisation and the timing
+// read-outs.
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "ctx.h"
+
+using namespace fmrx;
+
+namespace {
+
+thread_local std::string g_err;
+
+constexpr uint32_t kStateMagic = 0x46524D58u;  // "FMRX"
+constexpr uint32_t kStateVersion = 2;  // 2: + flags word (bit 0: audio history stale after fmrx_seek)
+constexpr int kStateHdrWords = 10;  // magic, version, mode, channels, rf_taps, n_streams, halo, audio_hist, flags, 0
+
+bool fused_rf_supported(const fmrx_ctx* c) {
+    const int t = c->geo.rf_taps, d = c->geo.rf_decim;
+    return (t == 51 || t == 101) && (d == 10 || d == 4 || d == 9);
+}
+
+}  // namespace
+
+namespace fmrx {
+
+int fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+int timing_begin(fmrx_ctx* c, hipStream_t st, TimingPair** ev) {
+    if (!c->timing) return 0;
+    if (c->ev_used == c->evs.size()) {
+        TimingPair e{nullptr, nullptr};
+        HIPCHK(hipEventCreate(&e.first));
+        HIPCHK(hipEventCreate(&e.second));
+        c->evs.push_back(e);
+    }
+    *ev = &c->evs[c->ev_used++];
+    HIPCHK(hipEventRecord((*ev)->first, st));
+    return 0;
+}
+
+int reset_state(fmrx_ctx* c) {
+    const int ns = c->cfg.n_streams;
+    c->pll_trig = fmrx_ctx::TrigTrack{};
+    c->rds_trig = fmrx_ctx::TrigTrack{};
+    c->tune_pos = 0;  // the offsets stay (configuration)
+    HIPCHK(hipMemsetAsync(c->d_halo[0].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_halo[1].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
+    c->halo_cur = 0;
+    if (c->wide_decim > 1) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
+        const size_t nh = c->halo_pairs * 8 * ns;
+        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), 16 * (size_t)c->wide_decim * c->pair_bytes, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_wide_halo[0].p, 0, nh, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_wide_halo[1].p, 0, nh, c->stream));
+        c->wide_halo_cur = 0;
+    }
+    HIPCHK(hipMemsetAsync(c->d_audio_hist.p, 0, sizeof(float) * c->audio_hist * ns, c->stream));
+    c->audio_hist_stale = false;
+    if (c->d_demod.p)  // the history in front of each stream (every call overwrites the rest)
+        HIPCHK(hipMemset2DAsync(c->d_demod.p, c->demod_stride * sizeof(float), 0, sizeof(float) * kDemodHist, ns,
+                                c->stream));
+    // project.cpp:106-111: integrator 0, phaseEst 0, feedbackI 1, feedbackQ 0,
+    // ncoOut_state 1, trigOffset 0
+    std::vector<float> pll(8 * ns, 0.0f);
+    for (int s = 0; s < ns; s++) {
+        pll[8 * s + 2] = 1.0f;
+        pll[8 * s + 4] = 1.0f;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_pll.p, pll.data(), sizeof(float) * pll.size(),
+                          hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_mix_tail.p, 0, sizeof(float) * kMixTail * ns, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_mono_state.p, 0, sizeof(float) * 8 * ns, c->stream));
+    // RDS (project.cpp:206-226): zero histories, the same PLL start as the pilot PLL
+    HIPCHK(hipMemsetAsync(c->d_rds_dhist.p, 0, sizeof(float) * kRdsDemodHist * ns, c->stream));
+    if (c->d_rds_chan.p) HIPCHK(hipMemsetAsync(c->d_rds_chan.p, 0, sizeof(float) * c->d_rds_chan.n, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_rds_pll.p, pll.data(), sizeof(float) * pll.size(), hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // namespace fmrx
+
+extern "C" {
+
+const char* fmrx_last_error(void) { return g_err.c_str(); }
+const char* fmrx_version(void) { return "fmrx 0.1 (gfx950)"; }
+
+int fmrx_config_default(fmrx_config* cfg, int mode, int channels) {
+    if (!cfg) return fail(FMRX_EINVAL, "null config");
+    ModeConstants m;
+    if (!mode_constants(mode, &m)) return fail(FMRX_EINVAL, "invalid mode %d", mode);
+    if (channels != FMRX_MONO && channels != FMRX_STEREO)
+        return fail(FMRX_EINVAL, "invalid channels %d", channels);
+    cfg->mode = mode;
+    cfg->channels = channels;
+    cfg->rf_taps = 51;     // src/project.cpp:306
+    cfg->bp_taps = 51;     // src/project.cpp:307
+    cfg->audio_taps = 51;  // src/project.cpp:319
+    cfg->n_streams = 1;
+    cfg->device = 0;
+    return FMRX_OK;
+}
+
+int fmrx_geometry(const fmrx_config* cfg, fmrx_geometry_t* g) {
+    if (!cfg || !g) return fail(FMRX_EINVAL, "null argument");
+    ModeConstants m;
+    if (!mode_constants(cfg->mode, &m)) return fail(FMRX_EINVAL, "invalid mode %d", cfg->mode);
+    if (cfg->channels != FMRX_MONO && cfg->channels != FMRX_STEREO)
+        return fail(FMRX_EINVAL, "invalid channels %d", cfg->channels);
+    const int rf_taps = cfg->rf_taps ? cfg->rf_taps : 51;
+    const int bp_taps = cfg->bp_taps ? cfg->bp_taps : 51;
+    const int audio_taps = cfg->audio_taps ? cfg->audio_taps : 51;
+    if (rf_taps < 3 || rf_taps > kMaxRfTaps) return fail(FMRX_EINVAL, "rf_taps %d out of range", rf_taps);
+    if (bp_taps < 3 || bp_taps > 64) return fail(FMRX_EINVAL, "bp_taps %d out of range", bp_taps);
+    // The fused audio stages (mono window, rational resampler rows, stereo LPFs' shared
+    // 50-sample history) are compiled for the reference's 51 taps per phase (project.cpp:319).
+    if (audio_taps != 51) return fail(FMRX_EINVAL, "audio_taps %d unsupported (51 per phase)", audio_taps);
+    g->rf_fs = m.rf_fs;
+    g->rf_decim = m.rf_decim;
+    g->if_fs = m.if_fs;
+    g->bp_fs = m.bp_fs;
+    g->audio_up = m.audio_up;
+    g->audio_down = m.audio_down;
+    g->rf_taps = rf_taps;
+    g->bp_taps = bp_taps;
+    g->audio_taps_total = audio_taps * m.audio_up;  // project.cpp:347,356
+    g->block_bytes = (size_t)256 * m.rf_decim * m.audio_down;  // project.cpp:364
+    g->iq_pairs = g->block_bytes / 2;
+    g->if_samples = g->iq_pairs / m.rf_decim;
+    g->audio_frames = g->if_samples * m.audio_up / m.audio_down;
+    g->pcm_samples = g->audio_frames * cfg->channels;
+    if ((size_t)g->audio_taps_total - 1 > g->if_samples || (size_t)rf_taps - 1 > g->iq_pairs)
+        return fail(FMRX_EINVAL, "filter longer than a block");
+    return FMRX_OK;
+}
+
+// The tuning switches of a new context from the environment (A/B measurements: which runner or
+// kernel form runs, never what it computes).  The PLL test hooks are not read here: only
+// fmrx_debug_set_knob sets them, per context.
+// Every knob's accepted range (include/fmrx.h): a value outside it is refused (FMRX_EINVAL from
+// fmrx_debug_set_knob; fmrx_create refuses a bad environment variable), so no setting can reach
+// an untested kernel form.  Integer knobs take integer values only.
+struct KnobSpec {
+    int id;
+    const char* env;  // the tuning knobs' environment variable (null: test hooks, never from there)
+    double lo, hi;
+    bool integer;
+};
+constexpr KnobSpec kKnobs[] = {
+    {FMRX_KNOB_PLL_SPEC, "FMRX_PLL_SPEC", 0, 1, true},
+    {FMRX_KNOB_PLL_SAT, "FMRX_PLL_SAT", 0, 1, true},
+    {FMRX_KNOB_PLL_PRED, "FMRX_PLL_PRED", 0, 2, true},
+    {FMRX_KNOB_PLL_PIPE, "FMRX_PLL_PIPE", 0, 1, true},
+    {FMRX_KNOB_PLL_IDX, "FMRX_PLL_IDX", 0, 2, true},
+    {FMRX_KNOB_STEREO_CHUNKS, "FMRX_STEREO_CHUNKS", 0, 64, true},
+    {FMRX_KNOB_MONO_SPLIT, "FMRX_MONO_SPLIT", -1, 1023, true},
+    {FMRX_KNOB_BPF_TILE, "FMRX_BPF_TILE", 0, 1, true},
+    {FMRX_KNOB_HALO_KERNEL, "FMRX_HALO_KERNEL", 0, 1, true},
+    {FMRX_KNOB_PLL_INJECT, nullptr, -1, 1 << 30, true},
+    {FMRX_KNOB_PLL_PIPE_MISS, nullptr, -(1 << 30), 1 << 30, true},
+    {FMRX_KNOB_PLL_HINT_SKEW, nullptr, -16777216.0, 16777216.0, false},
+    {FMRX_KNOB_PLL_CNT, "FMRX_PLL_CNT", 0, 31, true},
+    {FMRX_KNOB_PLL_STICK, "FMRX_PLL_STICK", 0, 1, true},
+    {FMRX_KNOB_STEREO_HEAD, "FMRX_STEREO_HEAD", 1, 64, true},
+    {FMRX_KNOB_STEREO_LEAD, "FMRX_STEREO_LEAD", 0, 64, true},
+    {FMRX_KNOB_AUDIO_DEFER, "FMRX_AUDIO_DEFER", 0, 64, true},
+    {FMRX_KNOB_STEREO_TAIL, "FMRX_STEREO_TAIL", 1, 64, true},
+};
+
+const KnobSpec* knob_spec(int knob) {
+    for (const KnobSpec& k : kKnobs)
+        if (k.id == knob) return &k;
+    return nullptr;
+}
+
+// value into the context's knobs (range already checked)
+void knob_set(fmrx_ctx::Knobs& k, int knob, double value) {
+    const int v = (int)value;
+    switch (knob) {
+        case FMRX_KNOB_PLL_SPEC: k.pll.spec = v; break;
+        case FMRX_KNOB_PLL_SAT: k.pll.sat = v; break;
+        case FMRX_KNOB_PLL_PRED: k.pll.pred = v; break;
+        case FMRX_KNOB_PLL_PIPE: k.pll.pipe = v; break;
+        case FMRX_KNOB_PLL_IDX: k.pll.idx = v; break;
+        case FMRX_KNOB_STEREO_CHUNKS: k.stereo_chunks = v; break;
+        case FMRX_KNOB_STEREO_HEAD: k.stereo_head = v; break;
+        case FMRX_KNOB_STEREO_TAIL: k.stereo_tail = v; break;
+        case FMRX_KNOB_STEREO_LEAD: k.stereo_lead = v; break;
+        case FMRX_KNOB_AUDIO_DEFER: k.audio_defer = v; break;
+        case FMRX_KNOB_MONO_SPLIT: k.mono_split = v; break;
+        case FMRX_KNOB_BPF_TILE: k.bpf_tile = v; break;
+        case FMRX_KNOB_HALO_KERNEL: k.halo_kernel = v; break;
+        case FMRX_KNOB_PLL_INJECT: k.pll.inject = v; break;
+        case FMRX_KNOB_PLL_PIPE_MISS: k.pll.pipe_miss = v; break;
+        case FMRX_KNOB_PLL_HINT_SKEW: k.pll.skew = value; break;
+        case FMRX_KNOB_PLL_CNT: k.pll.cnt = v; break;
+        case FMRX_KNOB_PLL_STICK: k.pll.stick = v; break;
+        default: break;
+    }
+}
+
+bool knob_ok(const KnobSpec& s, double v) {
+    return v == v && v >= s.lo && v <= s.hi && (!s.integer || v == std::floor(v));
+}
+
+// the tuning knobs from the environment, read once by fmrx_create; a set variable must be an
+// integer in its knob's range (otherwise the context is refused, naming the variable)
+int knobs_from_env(fmrx_ctx::Knobs* out) {
+    fmrx_ctx::Knobs k;
+    for (const KnobSpec& s : kKnobs) {
+        if (!s.env) continue;
+        const char* e = std::getenv(s.env);
+        if (!e || !*e) continue;
+        char* end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (*end != '\0' || !knob_ok(s, (double)v))
+            return fail(FMRX_EINVAL, "%s=%s: not an integer in [%g, %g]", s.env, e, s.lo, s.hi);
+        knob_set(k, s.id, (double)v);
+    }
+    *out = k;
+    return FMRX_OK;
+}
+
+int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
+    if (!out) return fail(FMRX_EINVAL, "null output pointer");
+    *out = nullptr;
+    fmrx_geometry_t g;
+    int rc = fmrx_geometry(cfg, &g);
+    if (rc) return rc;
+    if (cfg->n_streams < 1) return fail(FMRX_EINVAL, "n_streams must be >= 1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(FMRX_EHIP, "no HIP device available (libfmrx has no CPU path)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(FMRX_EINVAL, "bad device %d", cfg->device);
+    // every per-stream launch puts the streams on grid.y (band-pass, PLL check / NCO / pre-pass,
+    // halo update, the multi-stream audio and copy kernels): refuse what cannot launch here
+    // rather than fail at the first call
+    int max_y = 0;
+    if (hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, cfg->device) == hipSuccess && max_y > 0 &&
+        cfg->n_streams > max_y)
+        return fail(FMRX_EINVAL, "n_streams %d exceeds the device's grid.y limit %d", cfg->n_streams, max_y);
+    fmrx_ctx* c = new fmrx_ctx();
+    c->cfg = *cfg;
+    c->cfg.rf_taps = g.rf_taps;
+    c->cfg.bp_taps = g.bp_taps;
+    c->geo = g;
+    mode_constants(cfg->mode, &c->mc);
+    if (!fused_rf_supported(c)) {
+        delete c;
+        return fail(FMRX_EINVAL, "no compiled RF kernel for rf_taps=%d rf_decim=%d", g.rf_taps,
+                    g.rf_decim);
+    }
+    if ((rc = set_device(c))) { delete c; return rc; }
+    if ((rc = knobs_from_env(&c->knobs))) {
+        delete c;
+        return rc;
+    }
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0)
+            c->n_simd = 4 * cus;
+    }
+    // taps, exactly as the reference designs them (project.cpp:37, 97, 104, 117)
+    c->rf.resize(g.rf_taps);
+    design_lpf(c->rf.data(), (float)g.rf_fs, (float)kRfFc, g.rf_taps, 1);
+    c->audio.resize(g.audio_taps_total);
+    design_lpf(c->audio.data(), (float)g.if_fs, (float)kAudioFc, g.audio_taps_total, g.audio_up);
+    c->ch.resize(g.bp_taps);
+    design_bpf(c->ch.data(), (float)g.bp_fs, 22000.0f, 54000.0f, g.bp_taps);
+    c->ca.resize(g.bp_taps);
+    design_bpf(c->ca.data(), (float)g.bp_fs, 18500.0f, 19500.0f, g.bp_taps);
+    std::memset(&c->mono_taps, 0, sizeof c->mono_taps);
+    std::copy(c->rf.begin(), c->rf.end(), c->mono_taps.rf);
+    if (g.audio_up == 1) std::copy(c->audio.begin(), c->audio.end(), c->mono_taps.audio);
+
+    const int ns = cfg->n_streams;
+    auto cleanup = [&](int code) { fmrx_destroy(c); return code; };
+    // the context stream at the highest priority (the serial PLL of the pipelined stereo engine
+    // runs on it, its stage streams at the lowest)
+    int prio_lo = 0, prio_hi = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
+        hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi) != hipSuccess)
+        return cleanup(fail(FMRX_EHIP, "hipStreamCreate failed"));
+    c->halo_bytes = mono_halo_bytes(g.rf_taps, g.rf_decim, g.audio_down);
+    c->halo_pairs = c->halo_bytes / 2;
+    c->audio_hist = g.audio_taps_total - 1;
+    if ((rc = c->d_halo[0].ensure(c->halo_bytes * ns)) || (rc = c->d_halo[1].ensure(c->halo_bytes * ns)) ||
+        (rc = c->d_audio_hist.ensure((size_t)c->audio_hist * ns)) ||
+        (rc = c->d_audio.ensure(c->audio.size())) || (rc = c->d_rf.ensure(c->rf.size())) ||
+        (rc = c->d_pll.ensure(8 * (size_t)ns)) || (rc = c->d_mix_tail.ensure((size_t)kMixTail * ns)) ||
+        (rc = c->d_mono_state.ensure(8 * (size_t)ns)) || (rc = c->d_sintab.ensure(kSinSize)) ||
+        (rc = c->d_rds_taps.ensure(2 * kRdsTaps)) || (rc = c->d_rds_dhist.ensure((size_t)kRdsDemodHist * ns)) ||
+        (rc = c->d_rds_pll.ensure(8 * (size_t)ns)))
+        return cleanup(rc);
+    // RDS taps, project.cpp:211 and :217 (bp_taps = 51 at bp_fs)
+    std::vector<float> rds_taps(2 * kRdsTaps);
+    design_bpf(rds_taps.data(), (float)g.bp_fs, 54000.0f, 60000.0f, kRdsTaps);
+    design_bpf(rds_taps.data() + kRdsTaps, (float)g.bp_fs, 113500.0f, 114500.0f, kRdsTaps);
+    if (hipMemcpy(c->d_rds_taps.p, rds_taps.data(), sizeof(float) * rds_taps.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return cleanup(fail(FMRX_EHIP, "RDS tap upload failed"));
+    if (hipMemcpy(c->d_audio.p, c->audio.data(), sizeof(float) * c->audio.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_rf.p, c->rf.data(), sizeof(float) * c->rf.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_sintab.p, synth_sintab(), sizeof(int16_t) * kSinSize, hipMemcpyHostToDevice) != hipSuccess)
+        return cleanup(fail(FMRX_EHIP, "tap upload failed"));
+    if (g.audio_up > 1) {
+        // the rational resampler's prototype by phase: row k0 holds the 51 taps an output of
+        // phase k0 reads, in the order filter.cpp:84 visits them (k = k0, k0 + up, ...)
+        const int up = g.audio_up;
+        std::vector<float> rows((size_t)up * kAudioRow, 0.0f);
+        for (int k0 = 0; k0 < up; k0++)
+            for (int i = 0; i < 51; i++) rows[(size_t)k0 * kAudioRow + i] = c->audio[(size_t)k0 + (size_t)i * up];
+        if ((rc = c->d_audio_rows.ensure(rows.size()))) return cleanup(rc);
+        if (hipMemcpy(c->d_audio_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return cleanup(fail(FMRX_EHIP, "tap upload failed"));
+    }
+    c->tune_offsets.assign((size_t)ns, 0);
+    c->wide_offsets.assign((size_t)ns, 0);
+    if ((rc = reset_state(c))) return cleanup(rc);
+    *out = c;
+    return FMRX_OK;
+}
+
+void fmrx_destroy(fmrx_ctx* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->cfg.device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    c->d_audio.release(); c->d_rf.release(); c->d_audio_rows.release(); c->d_halo[0].release(); c->d_halo[1].release();
+    c->d_audio_hist.release(); c->d_demod.release(); c->d_channel.release(); c->d_carrier.release();
+    c->d_pll.release(); c->d_mix_tail.release(); c->d_mono_state.release(); c->d_in.release();
+    c->d_out.release(); c->d_f32.release(); c->d_scratch.release(); c->d_sintab.release();
+    c->h_in.release(); c->h_out.release();
+    c->d_pll_side.release(); c->d_pll_side2.release();
+    c->d_rds_taps.release(); c->d_rds_dhist.release(); c->d_rds_chan.release(); c->d_rds_car.release();
+    c->d_rds_pll.release();
+    c->d_tune_tab.release(); c->d_tune_streams.release();
+    c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
+    c->d_wide_hist.release(); c->d_wide_taps.release(); c->d_wide_tab.release(); c->d_wide_streams.release();
+    c->d_wide_y.release(); c->d_wide_halo[0].release(); c->d_wide_halo[1].release();
+    for (auto& e : c->evs) {
+        (void)hipEventDestroy(e.first);
+        (void)hipEventDestroy(e.second);
+    }
+    c->stage_timer.release();
+    if (c->s_front) (void)hipStreamSynchronize(c->s_front);
+    if (c->s_audio) (void)hipStreamSynchronize(c->s_audio);
+    for (auto e : c->pipe_ev) (void)hipEventDestroy(e);
+    if (c->s_front) (void)hipStreamDestroy(c->s_front);
+    if (c->s_audio) (void)hipStreamDestroy(c->s_audio);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+int fmrx_history_bytes(const fmrx_ctx* c, size_t* bytes) {
+    CtxLock lock_(c);
+    if (!c || !bytes) return fail(FMRX_EINVAL, "null argument");
+    *bytes = c->halo_bytes;
+    return FMRX_OK;
+}
+
+// The fused kernel rebuilds every float state of the mono product from the raw bytes in the
+// halo by a pre-roll chunk (mono_fused.hip), so seeking is setting the halo: the last
+// halo_bytes of prev, the format's zero (0x80 for u8: x = 0.0, the reference's zero-initialised
+// state) in front of a shorter prev.  Bytes are the context's format's (fmrx_set_input_format).
+int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
+    CtxLock lock_(c);
+    if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
+    if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
+    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
+    if (n % c->pair_bytes != 0)
+        return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t ns = c->cfg.n_streams, hb = c->halo_bytes, m = std::min(n, hb);
+    uint8_t* h = c->d_halo[c->halo_cur].p;
+    if (m < hb) HIPCHK(hipMemset2DAsync(h, hb, iq_zero_byte(c), hb - m, ns, c->stream));
+    if (m > 0)
+        HIPCHK(hipMemcpy2DAsync(h + (hb - m), hb, prev + (n - m), n, m, ns,
+                                prev_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    if (!prev_on_device) HIPCHK(hipStreamSynchronize(c->stream));  // prev may be freed on return
+    c->audio_hist_stale = true;
+    return FMRX_OK;
+}
+
+int fmrx_reset(fmrx_ctx* c) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    int rc = set_device(c);
+    return rc ? rc : reset_state(c);
+}
+
+// ---- state blob: header + halo bytes + audio history + stereo state ------------------
+int fmrx_state_size(const fmrx_ctx* c, size_t* bytes) {
+    CtxLock lock_(c);
+    if (!c || !bytes) return fail(FMRX_EINVAL, "null argument");
+    const size_t ns = c->cfg.n_streams;
+    *bytes = kStateHdrWords * sizeof(uint32_t) + ns * (c->halo_bytes + sizeof(float) * (c->audio_hist + kDemodHist + 8 + kMixTail + 8));
+    return FMRX_OK;
+}
+
+namespace {
+struct BlobIO {
+    uint8_t* p;
+    bool put;
+    int io(fmrx_ctx* c, void* dev, size_t n) {
+        if (n == 0) return 0;
+        if (put) HIPCHK(hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemcpyAsync(p, dev, n, hipMemcpyDeviceToHost, c->stream));
+        p += n;
+        return 0;
+    }
+};
+
+int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
+    size_t need;
+    fmrx_state_size(c, &need);
+    if (bytes < need) return fail(FMRX_ESTATE, "state buffer too small (%zu < %zu)", bytes, need);
+    int rc = set_device(c);
+    if (rc) return rc;
+    // words 0-7 identify the context shape and must match; word 8 carries the audio-history
+    // staleness of a context taken between fmrx_seek and its next fused call (bit 0; restored with
+    // the blob, so fmrx_audio_block refuses the stale history there too) and the raw I/Q format
+    // (bits 8-15), which must match
+    uint32_t hdr[kStateHdrWords] = {kStateMagic, kStateVersion, (uint32_t)c->cfg.mode, (uint32_t)c->cfg.channels,
+                                    (uint32_t)c->geo.rf_taps, (uint32_t)c->cfg.n_streams, (uint32_t)c->halo_bytes,
+                                    (uint32_t)c->audio_hist,
+                                    (c->audio_hist_stale ? 1u : 0u) | ((uint32_t)c->iq_format << 8), 0u};
+    if (put) {
+        uint32_t got[kStateHdrWords];
+        std::memcpy(got, buf, sizeof got);
+        if (got[0] != kStateMagic) return fail(FMRX_ESTATE, "not an fmrx state blob (magic 0x%08x)", got[0]);
+        if (got[1] != kStateVersion)
+            return fail(FMRX_ESTATE, "state blob version %u, expected %u (INTEGRATION.md: blob versions)", got[1],
+                        kStateVersion);
+        // word 8, bits 8-15: the raw I/Q format of the halo bytes (0 = u8: the blobs from before the
+        // bits had a meaning carry 0 there and stay valid); checked before the shape, whose halo word
+        // the format changes
+        if ((got[8] & ~0xFF01u) == 0u && (got[8] >> 8) != (uint32_t)c->iq_format)
+            return fail(FMRX_ESTATE, "state blob holds input format %u, the context is set to %d", got[8] >> 8,
+                        c->iq_format);
+        if (std::memcmp(hdr + 2, got + 2, 6 * sizeof(uint32_t)) != 0)
+            return fail(FMRX_ESTATE, "state blob is for another context shape (mode %u, channels %u, rf_taps %u, "
+                        "%u streams)", got[2], got[3], got[4], got[5]);
+        if ((got[8] & ~0xFF01u) != 0u) return fail(FMRX_ESTATE, "state blob: unknown flags 0x%x", got[8]);
+        if (got[9] != 0u) return fail(FMRX_ESTATE, "state blob: reserved word 9 is 0x%x, must be 0", got[9]);
+    } else {
+        std::memcpy(buf, hdr, sizeof hdr);
+    }
+    const size_t ns = c->cfg.n_streams;
+    if (put && (rc = ensure_demod(c, 1))) return rc;
+    if (!put && !c->d_demod.p && (rc = ensure_demod(c, 1))) return rc;
+    BlobIO b{buf + sizeof hdr, put};
+    if ((rc = b.io(c, c->d_halo[c->halo_cur].p, ns * c->halo_bytes))) return rc;
+    if ((rc = b.io(c, c->d_audio_hist.p, ns * sizeof(float) * c->audio_hist))) return rc;
+    // demod history: kDemodHist floats in front of each stream's row (one 2-D copy)
+    {
+        const size_t w = sizeof(float) * kDemodHist, pitch = sizeof(float) * c->demod_stride;
+        if (put) HIPCHK(hipMemcpy2DAsync(c->d_demod.p, pitch, b.p, w, w, ns, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemcpy2DAsync(b.p, w, c->d_demod.p, pitch, w, ns, hipMemcpyDeviceToHost, c->stream));
+        b.p += w * ns;
+    }
+    if ((rc = b.io(c, c->d_pll.p, ns * sizeof(float) * 8))) return rc;
+    // (slots 6-7 of each stream's PLL state are the runners' hand-off within a call, 0 between
+    // calls: a blob's values there are not trusted)
+    if (put)
+        HIPCHK(hipMemset2DAsync(c->d_pll.p + 6, 8 * sizeof(float), 0, 2 * sizeof(float), ns, c->stream));
+    if ((rc = b.io(c, c->d_mix_tail.p, ns * sizeof(float) * kMixTail))) return rc;
+    if ((rc = b.io(c, c->d_mono_state.p, ns * sizeof(float) * 8))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+}  // namespace
+
+int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
+    CtxLock lock_(c);
+    if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
+    return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
+}
+
+int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
+    CtxLock lock_(c);
+    if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
+    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
+    const uint8_t* p = static_cast<const uint8_t*>(buf);
+    const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
+    if (rc == 0) {
+        uint32_t flags;
+        std::memcpy(&flags, p + 8 * sizeof(uint32_t), sizeof flags);
+        c->audio_hist_stale = (flags & 1u) != 0;
+        // the streams' trigOffsets (state_io order: halo, audio history, demod history, PLL x 8)
+        const size_t ns = c->cfg.n_streams;
+        const uint8_t* pll = p + kStateHdrWords * sizeof(uint32_t) +
+                             ns * (c->halo_bytes + sizeof(float) * (c->audio_hist + kDemodHist));
+        fmrx_ctx::TrigTrack t;
+        t.lo = 16777216.0;
+        t.hi = 0.0;
+        for (size_t s = 0; s < ns; s++) {
+            float v;
+            std::memcpy(&v, pll + (8 * s + 5) * sizeof(float), sizeof v);
+            if (!(v >= 0.0f && v <= 16777216.0f && v == std::floor(v))) t.known = false;
+            t.lo = std::min(t.lo, (double)v);
+            t.hi = std::max(t.hi, (double)v);
+        }
+        if (!t.known) t.lo = t.hi = 0.0;
+        c->pll_trig = t;
+    }
+    return rc;
+}
+
+int fmrx_synchronize(fmrx_ctx* c) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        // an asynchronous fault of an enqueued launch: the device state no longer follows the
+        // host's trigOffset bounds, so the runner choice falls back to "unknown" until a reset
+        c->pll_trig.known = false;
+        c->rds_trig.known = false;
+        return fail(FMRX_EHIP, "stream synchronize failed: %s", hipGetErrorString(e));
+    }
+    return FMRX_OK;
+}
+
+void* fmrx_stream(fmrx_ctx* c) { return c ? (void*)c->stream : nullptr; }
+
+int fmrx_kernel_timing(fmrx_ctx* c, int reset, double* avg_ms, long* launches) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    int rc = set_device(c);
+    if (rc) return rc;
+    double total = 0.0;
+    if (c->ev_used) HIPCHK(hipEventSynchronize(c->evs[c->ev_used - 1].second));
+    for (size_t i = 0; i < c->ev_used; i++) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, c->evs[i].first, c->evs[i].second));
+        total += ms;
+    }
+    if (avg_ms) *avg_ms = c->ev_used ? total / (double)c->ev_used : 0.0;
+    if (launches) *launches = (long)c->ev_used;
+    if (reset > 0) {  // reset > 0: clear and arm event timing of the fused kernel
+        c->ev_used = 0;
+        c->timing = true;
+    } else if (reset < 0) {  // reset < 0: clear and disarm
+        c->ev_used = 0;
+        c->timing = false;
+    }
+    return FMRX_OK;
+}
+
+// Diagnostic: per-stage device time of the stereo engine (StageTimer).  op 1 arms (and clears),
+// 0 reads, -1 reads and disarms; the read waits for the last recorded event.
+int fmrx_debug_stage_timing(fmrx_ctx* c, int op, double* ms, double* steps, long* launches, int n_kinds) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    int rc = set_device(c);
+    if (rc) return rc;
+    StageTimer& T = c->stage_timer;
+    if (op == 1) {
+        T.on = true;
+        T.used = 0;
+        return FMRX_OK;
+    }
+    if (n_kinds < 0 || (n_kinds > 0 && (!ms || !steps || !launches))) return fail(FMRX_EINVAL, "bad argument");
+    for (int k = 0; k < n_kinds; k++) {
+        ms[k] = steps[k] = 0.0;
+        launches[k] = 0;
+    }
+    if (T.used) HIPCHK(hipEventSynchronize(T.recs[T.used - 1].b));
+    for (size_t i = 0; i < T.used; i++) {
+        const StageTimer::Rec& r = T.recs[i];
+        if (r.kind >= n_kinds) continue;
+        float t = 0.0f;
+        HIPCHK(hipEventSynchronize(r.b));
+        HIPCHK(hipEventElapsedTime(&t, r.a, r.b));
+        ms[r.kind] += t;
+        steps[r.kind] += r.steps;
+        launches[r.kind] += 1;
+    }
+    if (op == -1) {
+        T.on = false;
+        T.used = 0;
+    }
+    return FMRX_OK;
+}
+
+int fmrx_debug_set_knob(fmrx_ctx* c, int knob, double value) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    const KnobSpec* s = knob_spec(knob);
+    if (!s) return fail(FMRX_EINVAL, "unknown knob %d", knob);
+    if (!knob_ok(*s, value)) return fail(FMRX_EINVAL, "knob %d: %g outside [%g, %g]", knob, value, s->lo, s->hi);
+    knob_set(c->knobs, knob, value);
+    return FMRX_OK;
+}
+
+}  // extern "C"

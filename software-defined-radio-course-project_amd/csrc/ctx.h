@@ -1,0 +1,297 @@
+// ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
+// functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
+// process.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// every numeric result comes from a GPU kernel.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <limits>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/fmrx.h"
+#include "fmrx_internal.h"
+#include "tuner.h"
+
+namespace fmrx {
+
+// sets the calling thread's fmrx_last_error() text and returns code (context.cpp)
+int fail(int code, const char* fmt, ...);
+
+#define HIPCHK(expr)                                                                   \
+    do {                                                                               \
+        hipError_t e_ = (expr);                                                        \
+        if (e_ != hipSuccess)                                                          \
+            return fail(FMRX_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_),     \
+                        __FILE__, __LINE__);                                           \
+    } while (0)
+
+constexpr int kDemodHist = 64;   // demod samples kept in front of each call (>= bp_taps-1)
+constexpr int kMixTail = 64;     // must match stereo.hip kTail
+constexpr int kAudioHist50 = 50;  // demod samples a resampler output reads before its base
+// calls up to this many input bytes go through the pinned staging (larger ones: device buffers
+// and hipMemcpyAsync, whose DMA beats kernels reading host memory at that size)
+constexpr size_t kPinnedCallBytes = (size_t)4 << 20;
+
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    int ensure(size_t count) {
+        if (count <= n) return 0;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+        if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
+            p = nullptr;
+            return fail(FMRX_ENOMEM, "hipMalloc of %zu bytes failed", count * sizeof(T));
+        }
+        n = count;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+// Pinned host memory, mapped into the device's address space (hipHostMalloc: kernels read and
+// write it through the same pointer): the staging of the host-buffer entry points' small calls
+// (the reference's per-block seam, project.cpp:48-84 / 132-196): the input goes to the device by
+// DMA from it, the kernels write their output into it in place -- one copy operation on the stream
+// and one host memcpy each way.
+template <class T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    int ensure(size_t count) {
+        if (count <= n) return 0;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault) !=
+            hipSuccess) {
+            p = nullptr;
+            return fail(FMRX_ENOMEM, "hipHostMalloc of %zu bytes failed", count * sizeof(T));
+        }
+        n = count;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+using TimingPair = std::pair<hipEvent_t, hipEvent_t>;
+
+// The members of fmrx_ctx (below: the ABI's opaque type lives outside the namespace).
+struct Ctx {
+    mutable std::recursive_mutex mu;  // every entry point holds it: one call on a context at a time
+    fmrx_config cfg{};
+    fmrx_geometry_t geo{};
+    ModeConstants mc{};
+    hipStream_t stream = nullptr;
+    // taps (host) and device copies
+    std::vector<float> rf, audio, ch, ca;
+    MonoTaps mono_taps{};
+    DevBuf<float> d_audio, d_rf;
+    DevBuf<float> d_audio_rows;   // modes 2/3: the audio prototype by phase (kAudioRow floats per row)
+    // RF state: the raw bytes preceding the next call, double-buffered
+    size_t halo_bytes = 0;                    // halo_pairs * pair_bytes
+    size_t halo_pairs = 0;
+    int iq_format = kIqU8;                    // fmrx_set_input_format: the raw I/Q format of every stream
+    size_t pair_bytes = 2;                    // bytes an I/Q pair of it
+    DevBuf<uint8_t> d_halo[2];
+    int halo_cur = 0;
+    // audio state of the mono product: last (audio_taps_total - 1) demod samples
+    int audio_hist = 0;
+    DevBuf<float> d_audio_hist;
+    bool audio_hist_stale = false;  // after fmrx_seek, until a fused call refreshes it
+    // stereo engine state
+    DevBuf<float> d_demod;        // n_streams x (kDemodHist + cap_if)
+    size_t demod_stride = 0;
+    DevBuf<float> d_channel, d_carrier;
+    DevBuf<float> d_pll;          // n_streams x 8
+    DevBuf<float> d_mix_tail;     // n_streams x kMixTail
+    DevBuf<float> d_mono_state;   // n_streams x 8
+    // RDS front half state (project.cpp:200-271; not part of the checkpoint blob)
+    DevBuf<float> d_rds_taps;     // 54-60 kHz taps, then 113.5-114.5 kHz taps
+    DevBuf<float> d_rds_dhist;    // n_streams x kRdsDemodHist
+    DevBuf<float> d_rds_chan;     // n_streams x (kRdsChanHist + cap)
+    size_t rds_chan_stride = 0;
+    DevBuf<float> d_rds_car;      // n_streams x cap
+    DevBuf<float> d_rds_pll;      // n_streams x 8
+    // staging for the host-buffer entry points
+    DevBuf<uint8_t> d_in;
+    DevBuf<int16_t> d_out;
+    PinnedBuf<uint8_t> h_in, h_out;  // the small host calls' staging (kPinnedCallBytes)
+    DevBuf<float> d_f32;
+    DevBuf<float> d_scratch;
+    DevBuf<double> d_pll_side;    // PLL side data of one segment (pll_side_doubles)
+    DevBuf<double> d_pll_side2;   // the pipelined engine's second one (odd chunks: their NCO runs
+                                  //   on the audio stream while the next chunk's PLL fills the first)
+    DevBuf<int16_t> d_sintab;
+    DevBuf<uint8_t> d_synth_params;  // fmrx_synth_device_streams: SynthParams per stream
+    // kernel timing: pairs of HIP events recorded around each fused-kernel launch on the
+    // context stream (no host sync inside the timed loop); read by fmrx_kernel_timing
+    std::vector<TimingPair> evs;
+    size_t ev_used = 0;
+    bool timing = false;
+    unsigned long long* stamps = nullptr;  // fmrx_debug_mono_stamps (diagnostic)
+    unsigned long long* pll_stats = nullptr;  // fmrx_debug_pll_stats (diagnostic)
+    unsigned* pll_redos = nullptr;            // fmrx_debug_pll_redos (diagnostic)
+    StageTimer stage_timer;                   // fmrx_debug_stage_timing (diagnostic)
+    // the pipelined stereo engine (run_stereo_pipelined): front-end / band-pass stream, audio
+    // stream and their events, created at the first pipelined call
+    hipStream_t s_front = nullptr, s_audio = nullptr;
+    std::vector<hipEvent_t> pipe_ev;
+    int n_simd = 1024;                        // SIMDs of cfg.device (4 per CU), set at creation
+    // off-centre tuning (fmrx_tune): configuration, not part of the state blob
+    bool tuned = false;
+    std::vector<int32_t> tune_offsets;        // n_streams (zeros until fmrx_tune sets them)
+    uint64_t tune_pos = 0;                    // absolute pair index of the next call's first I/Q pair
+    int tune_max_n = 1;                       // the longest rotator period among the streams
+    DevBuf<float> d_tune_tab;                 // the streams' (c, s) tables, one after the other
+    DevBuf<uint32_t> d_tune_streams;          // TunerStream per stream
+    // band scan (fmrx_scan*): scratch of its own, grown on demand; nothing the decode path reads
+    int scan_bins = 0;                        // the transform size d_scan_tab holds (0: none yet)
+    std::vector<float> scan_tab;              // host copy: 2 N twiddle floats, then N window floats
+    DevBuf<float> d_scan_tab;                 // the same on the device
+    DevBuf<float> d_scan_part;                // the launch's partial rows (scan_workgroups x N)
+    DevBuf<float> d_scan_power;               // the host entry points' result, N floats
+    DevBuf<uint8_t> d_scan_in;                // the host entry points' capture
+    // wide captures (fmrx_set_capture_decim): the down-converter in front of the tuner (wide.hip);
+    // its history, rows and narrow halo are its own, nothing the ordinary calls read
+    int wide_decim = 1;                       // cap_fs / rf_fs; 1: no wide stage
+    bool wide_tuned = false;                  // fmrx_tune_wide accepted (fmrx_tune turns it off)
+    std::vector<int32_t> wide_offsets;        // n_streams, against cap_fs
+    DevBuf<uint8_t> d_wide_hist;              // the 16 decim raw pairs of the capture in front of the next call
+    DevBuf<float> d_wide_taps;                // the 16 decim + 1 taps of the low-pass
+    DevBuf<float> d_wide_tab;                 // n_streams x kWideMaxN (c, s) pairs: the coarse tables
+    DevBuf<uint32_t> d_wide_streams;          // WideStream per stream
+    DevBuf<float> d_wide_y;                   // n_streams x wide_y_stride floats: one piece's cf32 rows at rf_fs
+    size_t wide_y_stride = 0;
+    DevBuf<uint8_t> d_wide_halo[2];           // the narrow stage's f32 halo (halo_pairs x 8 B a stream)
+    int wide_halo_cur = 0;
+    // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
+    // none of them changes the output (the PLL test hooks make the runners redo work)
+    struct Knobs {
+        PllKnobs pll;
+        int stereo_chunks = 0;  // 0: by stream count and call length; k: k chunks (1: serial engine)
+        int stereo_head = 8;    // the first chunk's blocks in 16ths of a middle chunk's
+        int stereo_tail = 8;    // the last chunk's blocks in 16ths of a middle chunk's
+        int stereo_lead = 0;    // n > 0: chunk k's front end waits for chunk k - n's PLL; 0: none
+        int audio_defer = 2;    // 2: chunks 0 .. K-2's audio beside the last PLL; 1: all after it; 0: beside the next
+                                // (2 + e: chunks 0 .. e-1 beside the PLL before the last)
+        int mono_split = -1;    // -1: kOlderShare; 0: equal spans; n: the older wave's n / 1024
+        int bpf_tile = 1;       // 0: the per-output band-pass kernel
+        int halo_kernel = 0;    // 1: the separate halo_kernel after the fused one
+    } knobs;
+    // bounds on the streams' trigOffset (PllHint) of the stereo and the RDS PLL: 0 after a reset,
+    // advanced by every call's samples (the float increments stick at 2^24), re-read from the
+    // blob by fmrx_set_state; unknown after a failed launch
+    struct TrigTrack {
+        bool known = true;
+        double lo = 0.0, hi = 0.0;
+        void advance(size_t n) {
+            lo = std::min(lo + (double)n, 16777216.0);
+            hi = std::min(hi + (double)n, 16777216.0);
+        }
+    } pll_trig, rds_trig;
+    PllHint hint(const TrigTrack& t) const {
+        PllHint h;
+        h.n_simd = n_simd;
+        h.knobs = knobs.pll;
+        h.redos = pll_redos;
+        h.known = t.known;
+        h.trig_lo = t.lo;
+        h.trig_hi = t.hi;
+        h.timer = stage_timer.on ? const_cast<StageTimer*>(&stage_timer) : nullptr;
+        return h;
+    }
+};
+
+}  // namespace fmrx
+
+struct fmrx_ctx : fmrx::Ctx {};
+
+namespace fmrx {
+
+// Serialises the entry points of one context (rf and audio stages may be driven from two
+// threads, as project.cpp does; they share the context's stream and scratch buffers).
+class CtxLock {
+  public:
+    explicit CtxLock(const fmrx_ctx* c) : c_(c) {
+        if (c_) c_->mu.lock();
+    }
+    ~CtxLock() {
+        if (c_) c_->mu.unlock();
+    }
+    CtxLock(const CtxLock&) = delete;
+    CtxLock& operator=(const CtxLock&) = delete;
+
+  private:
+    const fmrx_ctx* c_;
+};
+
+// The byte that fills a run of x = 0.0 samples of the context's format
+inline int iq_zero_byte(const fmrx_ctx* c) { return c->iq_format == kIqU8 ? 0x80 : 0; }
+// Bytes a block of one stream's raw I/Q takes in the context's format (geo.block_bytes for u8)
+inline size_t iq_block_bytes(const fmrx_ctx* c) { return c->geo.iq_pairs * c->pair_bytes; }
+// The calls that take raw I/Q run the tuned front end (tuner.hip) while tuning is on, and always
+// for a format other than u8 (the fused kernels read u8 only): with tuning off the context's
+// tables then hold zero offsets, which gives the untuned bits.
+inline bool front_tuned(const fmrx_ctx* c) { return c->tuned || c->iq_format != kIqU8; }
+// n_streams rows of n_blocks blocks in format bytes must fit size_t with room to spare (a block of
+// f32 is four times a block of u8)
+inline int check_call_size(const fmrx_ctx* c, size_t n_blocks, size_t decim = 1) {
+    const size_t per_block = (size_t)c->cfg.n_streams * c->geo.iq_pairs * 8 * decim;  // decim: a wide block
+    if (n_blocks > (std::numeric_limits<size_t>::max() / 4) / per_block)
+        return fail(FMRX_EINVAL, "%zu blocks: the call's byte count overflows", n_blocks);
+    return 0;
+}
+inline int set_device(const fmrx_ctx* c) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return 0;
+}
+
+// ---- context.cpp
+int reset_state(fmrx_ctx* c);
+// fmrx_kernel_timing around one launch on st: when timing is armed, begin takes the next event pair
+// and records its first event (*ev, null at the call, stays null otherwise); end records the second
+int timing_begin(fmrx_ctx* c, hipStream_t st, TimingPair** ev);
+inline int timing_end(TimingPair* ev, hipStream_t st) {
+    if (ev) HIPCHK(hipEventRecord(ev->second, st));
+    return 0;
+}
+
+// ---- engine.cpp
+// RF front end (+ the mono audio stage when `with_audio`); the chunk form serves the stereo pipeline
+int run_fused(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm, float* d_mono, float* d_demod,
+              size_t demod_stride, int demod_hist, bool with_audio, size_t b0 = 0, size_t call_blocks = 0,
+              hipStream_t st = nullptr, bool last = true);
+int run_mono_audio(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_if, int16_t* d_pcm, float* d_mono);
+int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono, const float* src = nullptr);
+int stereo_chunks(const fmrx_ctx* c, size_t n_blocks);
+int run_stereo_pipelined(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm, float* d_mono, int K);
+int run_rds(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_if, float* d_out, float* d_nco,
+            float* d_channel);
+int ensure_demod(fmrx_ctx* c, size_t n_if);
+
+// ---- front.cpp
+int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,
+                    size_t demod_stride, int demod_hist, bool pre_tail);
+int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, int16_t* d_pcm, float* d_mono);
+int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
+// decim within the down-converter's range (or_one: 1, no wide stage, passes too); rf_fs a positive multiple of 4
+int check_capture_decim(int decim, bool or_one);
+int check_wide_rf_fs(int rf_fs);
+
+}  // namespace fmrx

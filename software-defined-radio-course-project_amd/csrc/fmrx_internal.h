@@ -1,4 +1,4 @@
-// fmrx_internal.h — shared declarations between the host runtime (api.cpp) and the HIP
+// fmrx_internal.h — shared declarations between the host runtime (ctx.h and the .cpp files beside it) and the HIP
 // kernels (kernels.hip).  Not part of the public ABI (include/fmrx.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,7 +53,7 @@ int launch_bpf_pair(const StereoLaunch& L, int n_streams, hipStream_t s, bool ti
 // not verify to spec_stats[0] and the batches checked to spec_stats[1].
 constexpr size_t kPllSeg = (size_t)1 << 18;  // at most this many samples per stream per PLL segment
 size_t pll_side_doubles(int n, int n_streams);
-// What the host knows when it launches a PLL (api.cpp tracks it per context): the device's SIMD
+// What the host knows when it launches a PLL (ctx.h TrigTrack tracks it per context): the device's SIMD
 // count (streams per wave) and, when `known`, bounds on every stream's trigOffset at the call's
 // start (integer-valued, <= 2^24: the reference's float increments from a reset), so that
 // launch_pll enqueues only the runners some segment can use.  Unknown (the fmrx_pll primitive's
@@ -109,7 +109,7 @@ struct StageTimer {
 // three-wave runner (profiles/r05/rprof/).
 constexpr int kPllCntDefault = 12;
 
-// Per-context switches of the PLL launch (api.cpp fmrx_ctx::knobs; fmrx_debug_set_knob).  The
+// Per-context switches of the PLL launch (ctx.h fmrx_ctx::knobs; fmrx_debug_set_knob).  The
 // tuning ones pick which runners run (same bits either way) and are read from the environment
 // once, when the context is created; the test hooks make the runners do extra (redone) work --
 // the output stays the exact path's -- and are set only through fmrx_debug_set_knob.

@@ -1,0 +1,373 @@
+// front.cpp — the front ends ahead of the audio stages other than the fused kernel: the tuned front
+// end (tuner.hip) and the wide down-converter in front of it (wide.hip), with the calls that
+// configure them: tuning, the raw I/Q format and the capture decimation.
+#include "ctx.h"
+#include "wide.h"
+
+using namespace fmrx;
+
+namespace {
+
+// One launch of the tuner kernel over n_blocks blocks a stream: source rows of `format` (iq_stride
+// bytes apart, 0 for a shared capture), the halo pair `halo` of halo_bytes a stream with *cur the
+// one in front of the call, demod rows out.  Flips *cur and advances the position.
+int launch_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, int format, DevBuf<uint8_t>* halo, int* cur,
+                 size_t halo_bytes, size_t n_blocks, float* d_demod, size_t demod_stride, int demod_hist,
+                 bool pre_tail) {
+    const int ns = c->cfg.n_streams;
+    TunerLaunch L{};
+    L.iq = d_iq;
+    L.iq_stride = iq_stride;
+    L.halo = halo[*cur].p;
+    L.halo_next = halo[*cur ^ 1].p;
+    L.halo_bytes = halo_bytes;
+    L.stream_bytes = n_blocks * c->geo.iq_pairs * (size_t)iq_pair_bytes(format);
+    L.format = format;
+    L.demod = d_demod;
+    L.demod_stride = demod_stride;
+    L.demod_hist = demod_hist;
+    L.pre_tail = pre_tail ? 1 : 0;
+    L.n_if = (long long)(n_blocks * c->geo.if_samples);
+    L.segs = tuner_segments(L.n_if, c->geo.rf_taps, c->geo.rf_decim, ns, c->n_simd / 4, c->tune_max_n);
+    L.streams = reinterpret_cast<const TunerStream*>(c->d_tune_streams.p);
+    L.tables = reinterpret_cast<const float2*>(c->d_tune_tab.p);
+    L.first_pair = c->tune_pos;
+    const int st_t = c->stage_timer.begin(c->stream);
+    const int rc = launch_tuner(L, ns, c->geo.rf_taps, c->geo.rf_decim, c->tune_max_n, c->mono_taps, c->stream);
+    c->stage_timer.end(st_t, kStFront, 0.0, c->stream);
+    if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "tuned front end launch failed (%d)", rc);
+    *cur ^= 1;
+    c->tune_pos += (uint64_t)n_blocks * c->geo.iq_pairs;
+    return 0;
+}
+
+}  // namespace
+
+namespace fmrx {
+
+// The tuned front end over n_blocks blocks a stream of the context's format: demod rows out, the
+// halo moved, the position advanced.  iq_stride: bytes between the streams' rows, 0 for a shared
+// capture.  pre_tail: also the 50 demod samples in front of the call (at demod_hist - 50, from the
+// halo).
+int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,
+                    size_t demod_stride, int demod_hist, bool pre_tail) {
+    const size_t unit = 2 * c->pair_bytes;  // the kernel's staging unit: two pairs
+    if (reinterpret_cast<uintptr_t>(d_iq) % unit != 0 || iq_stride % unit != 0)
+        return fail(FMRX_EINVAL, "tuned calls need %zu-byte aligned I/Q rows", unit);
+    int rc_size = check_call_size(c, n_blocks);
+    if (rc_size) return rc_size;
+    return launch_front(c, d_iq, iq_stride, c->iq_format, c->d_halo, &c->halo_cur, c->halo_bytes, n_blocks, d_demod,
+                        demod_stride, demod_hist, pre_tail);
+}
+
+// A tuned call: the front end for the whole call into the context's demod rows, then the audio
+// stage fmrx_audio_block runs (mono: the polyphase stage; stereo: the non-pipelined engine).
+int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
+    const int ns = c->cfg.n_streams;
+    const size_t n_if = n_blocks * c->geo.if_samples;
+    int rc = ensure_demod(c, n_if);
+    if (rc) return rc;
+    if (c->cfg.channels != FMRX_MONO) {
+        if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, false)))
+            return rc;
+        return run_stereo_audio(c, n_blocks, d_pcm, d_mono);
+    }
+    // after fmrx_seek the audio history is rebuilt from the halo, as the fused kernel's pre-roll
+    // does: the 50 demod samples in front of the call (all a resampler output reads back)
+    const bool stale = c->audio_hist_stale;
+    if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, stale)))
+        return rc;
+    if (stale) {
+        if (launch_copy_streams(c->d_audio_hist.p + (c->audio_hist - kAudioHist50), c->audio_hist,
+                                c->d_demod.p + (kDemodHist - kAudioHist50), c->demod_stride, kAudioHist50, ns,
+                                c->stream))
+            return fail(FMRX_EHIP, "audio history copy failed");
+        c->audio_hist_stale = false;
+    }
+    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
+}
+
+}  // namespace fmrx
+
+namespace {
+
+// The streams' rotators for offsets_hz on the device (tables, TunerStream rows, tune_max_n);
+// FMRX_EINVAL with nothing changed for an offset fmrx_tuner_design refuses.
+int tuner_upload(fmrx_ctx* c, const int32_t* offsets_hz) {
+    if (!tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d", c->geo.rf_taps, c->geo.rf_decim);
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t ns = c->cfg.n_streams;
+    std::vector<TunerStream> ts(ns);
+    size_t entries = 0;
+    int max_n = 1;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int N = 0, k = 0;
+        if ((rc = fmrx_tuner_design(c->geo.rf_fs, offsets_hz[s], &N, &k, nullptr))) return rc;
+        ts[s] = TunerStream{(uint32_t)N, (uint32_t)k, (uint32_t)entries, 0u};
+        entries += (size_t)N;
+        max_n = std::max(max_n, N);
+    }
+    std::vector<float> tab(2 * entries);
+    for (size_t s = 0; s < ns; s++) tuner_design(c->geo.rf_fs, offsets_hz[s], nullptr, nullptr, tab.data() + 2 * ts[s].tab);
+    // a call in flight may still read the old tables: drain the stream before they are replaced
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = c->d_tune_tab.ensure(tab.size())) || (rc = c->d_tune_streams.ensure(4 * ns))) return rc;
+    HIPCHK(hipMemcpy(c->d_tune_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_tune_streams.p, ts.data(), sizeof(TunerStream) * ns, hipMemcpyHostToDevice));
+    c->tune_max_n = max_n;
+    return FMRX_OK;
+}
+
+// The tables of offset 0 for every stream: what the untuned calls of a format other than u8 run with
+// (no untuned kernel reads such a format: the tuned one at offset 0 gives the untuned bits)
+int upload_zero_offsets(fmrx_ctx* c) {
+    const std::vector<int32_t> zeros((size_t)c->cfg.n_streams, 0);
+    return tuner_upload(c, zeros.data());
+}
+
+// y rows of one internal piece of a wide call: at most this many bytes over all streams (a piece
+// is a whole number of blocks, at least one)
+constexpr size_t kWidePieceBytes = (size_t)128 << 20;
+
+}  // namespace
+
+namespace fmrx {
+
+int check_capture_decim(int decim, bool or_one) {
+    if ((decim >= kWideMinDecim && decim <= kWideMaxDecim) || (or_one && decim == 1)) return 0;
+    return fail(FMRX_EINVAL, "capture decimation %d outside %d..%d", decim, or_one ? 1 : kWideMinDecim, kWideMaxDecim);
+}
+
+int check_wide_rf_fs(int rf_fs) {
+    if (rf_fs <= 0 || rf_fs % 4 != 0) return fail(FMRX_EINVAL, "rf_fs %d is not a positive multiple of 4", rf_fs);
+    return 0;
+}
+
+// A wide call (fmrx_process_wide_device; arguments checked, device set): per piece of whole blocks
+// the down-converter (wide.hip) into the y rows, then the tuned front end reading them as an f32
+// stream with the wide stage's own halo; the demod rows of the whole call then take the audio stage
+// a tuned call takes.  A piece past the first finds its history in the capture itself.
+int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    const int ns = c->cfg.n_streams, D = c->wide_decim;
+    const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples;
+    const size_t wide_block = (size_t)D * iq_block_bytes(c), hb = 16 * (size_t)D * c->pair_bytes;
+    int rc = ensure_demod(c, n_if);
+    if (rc) return rc;
+    const size_t piece = std::min(n_blocks, std::max<size_t>(1, kWidePieceBytes / ((size_t)ns * ip * 8)));
+    if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->wide_y_stride = 0;
+        if ((rc = c->d_wide_y.ensure((size_t)ns * piece * ip * 2))) return rc;
+        c->wide_y_stride = piece * ip * 2;
+    }
+    const size_t nhb = c->halo_pairs * 8;
+    for (size_t b0 = 0; b0 < n_blocks; b0 += piece) {
+        const size_t nb = std::min(piece, n_blocks - b0);
+        WideLaunch W{};
+        W.iq = d_iq + b0 * wide_block;
+        W.hist = b0 == 0 ? c->d_wide_hist.p : W.iq - hb;
+        W.stream_bytes = nb * wide_block;
+        W.y = c->d_wide_y.p;
+        W.y_stride = c->wide_y_stride;
+        W.n_out = (long long)(nb * ip);
+        W.segs = wide_segments(W.n_out, D, ns, c->n_simd / 4);
+        W.format = c->iq_format;
+        W.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
+        W.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
+        W.h = c->d_wide_taps.p;
+        W.first_pair = c->tune_pos * (uint64_t)D;
+        TimingPair* ev = nullptr;  // fmrx_kernel_timing: the down-converter's launches
+        if ((rc = timing_begin(c, c->stream, &ev))) return rc;
+        rc = launch_wide_ddc(W, ns, D, c->stream);
+        if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "down-converter launch failed (%d)", rc);
+        if ((rc = timing_end(ev, c->stream))) return rc;
+        // the y rows as an f32 stream, the wide stage's own halo in front of them
+        if ((rc = launch_front(c, reinterpret_cast<const uint8_t*>(c->d_wide_y.p), c->wide_y_stride * sizeof(float), kIqF32,
+                               c->d_wide_halo, &c->wide_halo_cur, nhb, nb, c->d_demod.p + b0 * c->geo.if_samples,
+                               c->demod_stride, kDemodHist, false)))
+            return rc;
+    }
+    // the next call's history: the capture's last 16 decim pairs (a block holds more than that)
+    HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + n_blocks * wide_block - hb, hb, hipMemcpyDeviceToDevice, c->stream));
+    if (c->cfg.channels != FMRX_MONO) return run_stereo_audio(c, n_blocks, d_pcm, nullptr);
+    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, nullptr);
+}
+
+}  // namespace fmrx
+
+extern "C" {
+
+// ---- off-centre tuning ----------------------------------------------------------------------
+int fmrx_tuner_design(int rf_fs, int offset_hz, int* N, int* k, float* cos_sin) {
+    int why = 0;
+    if (tuner_design(rf_fs, offset_hz, N, k, cos_sin, &why)) return FMRX_OK;
+    if (why == 2)
+        return fail(FMRX_EINVAL, "offset %d Hz at %d S/s: rotator period above %d pairs (use a multiple of 1 kHz)",
+                    offset_hz, rf_fs, kTunerMaxN);
+    return fail(FMRX_EINVAL, "offset %d Hz outside (-%d/2, %d/2)", offset_hz, rf_fs, rf_fs);
+}
+
+int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (!offsets_hz) {  // tuning off: the untuned kernels, exactly as before
+        if (c->iq_format != kIqU8) {
+            const int rc = upload_zero_offsets(c);
+            if (rc) return rc;
+        }
+        c->tuned = false;
+        c->wide_tuned = false;
+        c->tune_pos = first_pair;
+        return FMRX_OK;
+    }
+    const int rc = tuner_upload(c, offsets_hz);
+    if (rc) return rc;
+    c->tune_offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
+    c->tune_pos = first_pair;
+    c->tuned = true;
+    c->wide_tuned = false;  // the tables are no longer the fine offsets of fmrx_tune_wide
+    return FMRX_OK;
+}
+
+// ---- raw I/Q formats ----------------------------------------------------------------------------
+int fmrx_iq_pair_bytes(int format) {
+    const int b = iq_pair_bytes(format);
+    return b > 0 ? b : fail(FMRX_EINVAL, "unknown I/Q format %d", format);
+}
+
+int fmrx_set_input_format(fmrx_ctx* c, int format) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    const int pb = iq_pair_bytes(format);
+    if (pb < 0) return fail(FMRX_EINVAL, "unknown I/Q format %d", format);
+    if (format != kIqU8 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: u8 input only", c->geo.rf_taps,
+                    c->geo.rf_decim);
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the halo
+    if (format != c->iq_format) {
+        const size_t ns = c->cfg.n_streams, hb = c->halo_pairs * (size_t)pb;
+        if (format != kIqU8 && !c->tuned && (rc = upload_zero_offsets(c))) return rc;
+        if ((rc = c->d_halo[0].ensure(hb * ns)) || (rc = c->d_halo[1].ensure(hb * ns))) return rc;
+        if (c->wide_decim > 1 && (rc = c->d_wide_hist.ensure(16 * (size_t)c->wide_decim * (size_t)pb))) return rc;
+        c->iq_format = format;
+        c->pair_bytes = (size_t)pb;
+        c->halo_bytes = hb;
+    }
+    return reset_state(c);
+}
+
+int fmrx_input_format(const fmrx_ctx* c, int* format) {
+    CtxLock lock_(c);
+    if (!c || !format) return fail(FMRX_EINVAL, "null argument");
+    *format = c->iq_format;
+    return FMRX_OK;
+}
+
+int fmrx_tuner_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (offsets_hz) std::copy(c->tune_offsets.begin(), c->tune_offsets.end(), offsets_hz);
+    if (next_pair) *next_pair = c->tune_pos;
+    if (enabled) *enabled = c->tuned ? 1 : 0;
+    return FMRX_OK;
+}
+
+// ---- wide captures: the decimating down-converter ahead of the tuner ------------------------------
+int fmrx_wide_design(int rf_fs, int decim, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k, float* cos_sin,
+                     int* taps, float* h) {
+    int rc = check_capture_decim(decim, false);
+    if (rc || (rc = check_wide_rf_fs(rf_fs))) return rc;
+    int fc = 0, fr = 0, n = 0, kk = 0;
+    if (!wide_split(rf_fs, decim, offset_hz, &fc, &fr, &n, &kk, nullptr))
+        return fail(FMRX_EINVAL, "offset %d Hz outside (-%d %d/2, %d %d/2)", offset_hz, decim, rf_fs, decim, rf_fs);
+    int tn = 0, tk = 0;
+    if ((rc = fmrx_tuner_design(rf_fs, fr, &tn, &tk, nullptr))) return rc;  // the fine part goes to the tuner
+    if (coarse_hz) *coarse_hz = fc;
+    if (fine_hz) *fine_hz = fr;
+    if (N) *N = n;
+    if (k) *k = kk;
+    if (cos_sin) wide_split(rf_fs, decim, offset_hz, nullptr, nullptr, nullptr, nullptr, cos_sin);
+    if (taps) *taps = wide_taps(decim);
+    if (h) design_lpf(h, (float)rf_fs * (float)decim, (float)(3.0 * rf_fs / 8.0), wide_taps(decim), 1);
+    return FMRX_OK;
+}
+
+int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    int rc = check_capture_decim(decim, true);
+    if (rc) return rc;
+    if (decim == 1 && c->wide_decim == 1) return FMRX_OK;  // the default: nothing anywhere changes
+    if (decim > 1 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
+                    c->geo.rf_decim);
+    if ((rc = set_device(c))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the wide state
+    if (decim > 1) {
+        const size_t ns = c->cfg.n_streams;
+        std::vector<float> h((size_t)wide_taps(decim));
+        design_lpf(h.data(), (float)c->geo.rf_fs * (float)decim, (float)(3.0 * c->geo.rf_fs / 8.0), wide_taps(decim), 1);
+        if ((rc = c->d_wide_hist.ensure(16 * (size_t)decim * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(h.size())) ||
+            (rc = c->d_wide_tab.ensure(2 * (size_t)kWideMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
+            (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
+            return rc;
+        HIPCHK(hipMemcpy(c->d_wide_taps.p, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+    }
+    c->wide_decim = decim;
+    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
+    return reset_state(c);
+}
+
+int fmrx_capture_decim(const fmrx_ctx* c, int* decim) {
+    CtxLock lock_(c);
+    if (!c || !decim) return fail(FMRX_EINVAL, "null argument");
+    *decim = c->wide_decim;
+    return FMRX_OK;
+}
+
+int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    CtxLock lock_(c);
+    if (!c || !offsets_hz) return fail(FMRX_EINVAL, "null argument");
+    const int D = c->wide_decim;
+    if (D == 1) return fail(FMRX_ESTATE, "fmrx_tune_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
+    if (first_pair % (uint64_t)D != 0)
+        return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of the decimation %d",
+                    (unsigned long long)first_pair, D);
+    const size_t ns = c->cfg.n_streams;
+    std::vector<int32_t> fine(ns);
+    std::vector<WideStream> ws(ns);
+    std::vector<float> tab(2 * (size_t)kWideMaxN * ns, 0.0f);
+    int rc;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int fr = 0, n = 0, k = 0;
+        if ((rc = fmrx_wide_design(c->geo.rf_fs, D, offsets_hz[s], nullptr, &fr, &n, &k, tab.data() + 2 * kWideMaxN * s,
+                                   nullptr, nullptr)))
+            return rc;
+        fine[s] = fr;
+        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
+    }
+    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
+    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
+    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
+    c->tune_pos = first_pair / (uint64_t)D;
+    c->tuned = true;
+    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
+    c->wide_tuned = true;
+    return FMRX_OK;
+}
+
+int fmrx_wide_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (offsets_hz) std::copy(c->wide_offsets.begin(), c->wide_offsets.end(), offsets_hz);
+    if (next_pair) *next_pair = c->tune_pos * (uint64_t)c->wide_decim;
+    if (enabled) *enabled = c->wide_tuned ? 1 : 0;
+    return FMRX_OK;
+}
+
+}  // extern "C"

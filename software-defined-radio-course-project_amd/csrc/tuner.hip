@@ -1,5 +1,5 @@
 // tuner.hip — the frequency-translating front end: raw I/Q -> rotate by a per-stream offset ->
-// RF LPF + decimate -> FM demod, one launch, demod rows out (the audio stages of api.cpp take them
+// RF LPF + decimate -> FM demod, one launch, demod rows out (the audio stages of engine.cpp take them
 // unchanged).  A stream tuned to +f Hz multiplies pair n by e^(-j 2 pi f n / rf_fs), so a station
 // at +f of the capture lands on 0 Hz; several streams may read ONE capture (iq_stride = 0).
 //

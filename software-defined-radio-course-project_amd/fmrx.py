@@ -283,43 +283,27 @@ def _stations(arr, n: int) -> list:
     return [Station(arr[i].offset_hz, arr[i].power_db, arr[i].snr_db) for i in range(n)]
 
 
+def _station_call(fn, args, max_out: int, cfg: dict, want_floor: bool = False):
+    """A call that fills a station list: fn(*args, scan config, list, max_out, &found[, &floor_db])."""
+    out = (Station * max(max_out, 1))()
+    n, fl = C.c_int(), C.c_float()
+    _check(fn(*args, C.byref(scan_config(**cfg)), out, max_out, C.byref(n), *([C.byref(fl)] if want_floor else [])))
+    found = _stations(out, min(n.value, max_out))
+    return (found, fl.value) if want_floor else found
+
+
 def scan_detect(power: np.ndarray, rf_fs: int, max_out: int = MAX_STATIONS, **cfg):
     """fmrx_scan_detect on an FFT-shifted linear power spectrum (Receiver.scan_spectrum): (stations
     ascending by offset -- the strongest max_out of those found --, floor_db).  Host only."""
     p = np.ascontiguousarray(power, np.float32).reshape(-1)
-    out = (Station * max(max_out, 1))()
-    n, fl = C.c_int(), C.c_float()
-    _check(lib().fmrx_scan_detect(_np_ptr(p), p.size, rf_fs, C.byref(scan_config(**cfg)), out, max_out,
-                                  C.byref(n), C.byref(fl)))
-    return _stations(out, min(n.value, max_out)), fl.value
+    return _station_call(lib().fmrx_scan_detect, (_np_ptr(p), p.size, rf_fs), max_out, cfg, True)
 
 
 def scan_detect_wide(power: np.ndarray, rf_fs: int, decim: int, max_out: int = MAX_STATIONS, **cfg):
     """fmrx_scan_detect_wide: scan_detect on the spectrum of a capture at decim * rf_fs; every reported
     offset is one fmrx_wide_design accepts.  Host only."""
     p = np.ascontiguousarray(power, np.float32).reshape(-1)
-    out = (Station * max(max_out, 1))()
-    n, fl = C.c_int(), C.c_float()
-    _check(lib().fmrx_scan_detect_wide(_np_ptr(p), p.size, rf_fs, decim, C.byref(scan_config(**cfg)), out, max_out,
-                                       C.byref(n), C.byref(fl)))
-    return _stations(out, min(n.value, max_out)), fl.value
-
-
-def _decode_stations_wide(iq, fmt, mode, channels, rf_taps, decim, cfg):
-    with Receiver(mode, channels, rf_taps=rf_taps) as rx:
-        if fmt != IQ_U8:
-            rx.set_input_format(fmt)
-        rx.set_capture_decim(decim)
-        stations = rx.scan_wide(iq, **cfg)
-    if not stations:
-        return [], np.zeros((0, 0), np.int16)
-    with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
-        if fmt != IQ_U8:
-            rx.set_input_format(fmt)
-        rx.set_capture_decim(decim)
-        rx.tune_wide([s.offset_hz for s in stations])
-        pcm = rx.process_wide(iq)
-    return stations, pcm.reshape(len(stations), -1)
+    return _station_call(lib().fmrx_scan_detect_wide, (_np_ptr(p), p.size, rf_fs, decim), max_out, cfg, True)
 
 
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
@@ -330,19 +314,24 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     capture_decim times the mode's rate (scan_wide, tune_wide, process_wide)."""
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
     iq = _iq_flat(iq).reshape(-1)
-    if capture_decim != 1:
-        return _decode_stations_wide(iq, fmt, mode, channels, rf_taps, capture_decim, cfg)
-    with Receiver(mode, channels, rf_taps=rf_taps) as rx:
+    wide = capture_decim != 1
+    scan, tune, process = ("scan_wide", "tune_wide", "process_wide") if wide else ("scan", "tune", "process_shared")
+
+    def configure(rx):
         if fmt != IQ_U8:
             rx.set_input_format(fmt)
-        stations = rx.scan(iq, **cfg)
+        if wide:
+            rx.set_capture_decim(capture_decim)
+
+    with Receiver(mode, channels, rf_taps=rf_taps) as rx:
+        configure(rx)
+        stations = getattr(rx, scan)(iq, **cfg)
     if not stations:
         return [], np.zeros((0, 0), np.int16)
     with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
-        if fmt != IQ_U8:
-            rx.set_input_format(fmt)
-        rx.tune([s.offset_hz for s in stations])
-        pcm = rx.process_shared(iq)
+        configure(rx)
+        getattr(rx, tune)([s.offset_hz for s in stations])
+        pcm = getattr(rx, process)(iq)
     return stations, pcm.reshape(len(stations), -1)
 
 
@@ -505,36 +494,50 @@ class Receiver:
         _check(lib().fmrx_process_device_ex(self.h, d_iq, n_blocks, d_pcm, d_mono))
 
     # ---- off-centre tuning (several stations from one capture)
-    def tune(self, offsets, first_pair: int = 0) -> None:
-        """fmrx_tune: per-stream offsets in Hz (an int for one stream), or None for tuning off;
-        first_pair is the absolute pair index of the next call's first I/Q pair."""
-        if offsets is None:
-            _check(lib().fmrx_tune(self.h, None, first_pair))
-            return
+    def _tune(self, fn, offsets, first_pair: int) -> None:
         off = np.ascontiguousarray(np.atleast_1d(np.asarray(offsets, dtype=np.int64)))
         if off.size != self.n_streams:
             raise ValueError(f"{off.size} offsets for {self.n_streams} streams")
         if np.any(np.abs(off) >= 2 ** 31):
             raise FmrxError(FMRX_EINVAL, "offset does not fit 32 bits")
         off = off.astype(np.int32)
-        _check(lib().fmrx_tune(self.h, _np_ptr(off), first_pair))
+        _check(fn(self.h, _np_ptr(off), first_pair))
+
+    def _info(self, fn) -> tuple[list[int], int, bool]:
+        off = np.zeros(self.n_streams, np.int32)
+        pos, on = C.c_uint64(), C.c_int()
+        _check(fn(self.h, _np_ptr(off), C.byref(pos), C.byref(on)))
+        return [int(v) for v in off], pos.value, bool(on.value)
+
+    def _capture_call(self, fn, iq, per: int) -> np.ndarray:
+        """One capture's whole blocks of `per` elements through fn: S16 PCM, n_streams rows."""
+        iq = self._raw(iq).reshape(-1)
+        nb = iq.size // per
+        iq = np.ascontiguousarray(iq[: nb * per])
+        out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
+        _check(fn(self.h, _np_ptr(iq), nb, _np_ptr(out)))
+        return out if self.n_streams > 1 else out[0]
+
+    def _scan(self, fn, iq, max_out: int, cfg: dict) -> list:
+        iq = self._raw(iq).reshape(-1)
+        return _station_call(fn, (self.h, _np_ptr(iq), iq.size // 2), max_out, cfg)
+
+    def tune(self, offsets, first_pair: int = 0) -> None:
+        """fmrx_tune: per-stream offsets in Hz (an int for one stream), or None for tuning off;
+        first_pair is the absolute pair index of the next call's first I/Q pair."""
+        if offsets is None:
+            _check(lib().fmrx_tune(self.h, None, first_pair))
+            return
+        self._tune(lib().fmrx_tune, offsets, first_pair)
 
     def tuner_info(self) -> tuple[list[int], int, bool]:
         """fmrx_tuner_info: (offsets in Hz, next pair index, tuned)."""
-        off = np.zeros(self.n_streams, np.int32)
-        pos, on = C.c_uint64(), C.c_int()
-        _check(lib().fmrx_tuner_info(self.h, _np_ptr(off), C.byref(pos), C.byref(on)))
-        return [int(v) for v in off], pos.value, bool(on.value)
+        return self._info(lib().fmrx_tuner_info)
 
     def process_shared(self, iq: np.ndarray) -> np.ndarray:
         """One capture (one stream's whole blocks of raw I/Q) decoded by every tuned stream:
         S16 PCM, n_streams rows."""
-        iq = self._raw(iq).reshape(-1)
-        nb = iq.size // (2 * self.geo.iq_pairs)
-        iq = np.ascontiguousarray(iq[: nb * 2 * self.geo.iq_pairs])
-        out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
-        _check(lib().fmrx_process_shared(self.h, _np_ptr(iq), nb, _np_ptr(out)))
-        return out if self.n_streams > 1 else out[0]
+        return self._capture_call(lib().fmrx_process_shared, iq, 2 * self.geo.iq_pairs)
 
     def process_shared_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
         _check(lib().fmrx_process_shared_device(self.h, d_iq, n_blocks, d_pcm))
@@ -553,43 +556,23 @@ class Receiver:
     def tune_wide(self, offsets, first_pair: int = 0) -> None:
         """fmrx_tune_wide: per-stream offsets in Hz against the capture's rate (an int for one stream);
         first_pair is the absolute wide-pair index of the next call's first pair, a multiple of decim."""
-        off = np.ascontiguousarray(np.atleast_1d(np.asarray(offsets, dtype=np.int64)))
-        if off.size != self.n_streams:
-            raise ValueError(f"{off.size} offsets for {self.n_streams} streams")
-        if np.any(np.abs(off) >= 2 ** 31):
-            raise FmrxError(FMRX_EINVAL, "offset does not fit 32 bits")
-        off = off.astype(np.int32)
-        _check(lib().fmrx_tune_wide(self.h, _np_ptr(off), first_pair))
+        self._tune(lib().fmrx_tune_wide, offsets, first_pair)
 
     def wide_info(self) -> tuple[list[int], int, bool]:
         """fmrx_wide_info: (wide offsets in Hz, next wide-pair index, wide tuning on)."""
-        off = np.zeros(self.n_streams, np.int32)
-        pos, on = C.c_uint64(), C.c_int()
-        _check(lib().fmrx_wide_info(self.h, _np_ptr(off), C.byref(pos), C.byref(on)))
-        return [int(v) for v in off], pos.value, bool(on.value)
+        return self._info(lib().fmrx_wide_info)
 
     def process_wide(self, iq: np.ndarray) -> np.ndarray:
         """One wide capture (whole blocks of capture_decim * iq_pairs pairs) decoded by every stream
         tuned with tune_wide: S16 PCM, n_streams rows."""
-        iq = self._raw(iq).reshape(-1)
-        per = 2 * self.geo.iq_pairs * self.capture_decim  # elements a wide block
-        nb = iq.size // per
-        iq = np.ascontiguousarray(iq[: nb * per])
-        out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
-        _check(lib().fmrx_process_wide(self.h, _np_ptr(iq), nb, _np_ptr(out)))
-        return out if self.n_streams > 1 else out[0]
+        return self._capture_call(lib().fmrx_process_wide, iq, 2 * self.geo.iq_pairs * self.capture_decim)
 
     def process_wide_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
         _check(lib().fmrx_process_wide_device(self.h, d_iq, n_blocks, d_pcm))
 
     def scan_wide(self, iq: np.ndarray, max_out: int = MAX_STATIONS, **cfg) -> list:
         """fmrx_scan_wide: the stations of a wide capture, ascending by offset against its centre."""
-        iq = self._raw(iq).reshape(-1)
-        out = (Station * max(max_out, 1))()
-        n = C.c_int()
-        _check(lib().fmrx_scan_wide(self.h, _np_ptr(iq), iq.size // 2, C.byref(scan_config(**cfg)), out, max_out,
-                                    C.byref(n)))
-        return _stations(out, min(n.value, max_out))
+        return self._scan(lib().fmrx_scan_wide, iq, max_out, cfg)
 
     # ---- band scan: which offsets of a capture hold a station
     def scan_spectrum(self, iq: np.ndarray, fft_bins: int = 4096) -> tuple[np.ndarray, int]:
@@ -607,12 +590,7 @@ class Receiver:
     def scan(self, iq: np.ndarray, max_out: int = MAX_STATIONS, **cfg) -> list:
         """fmrx_scan: the stations of a raw I/Q capture, ascending by offset (settings: ScanConfig's
         fields)."""
-        iq = self._raw(iq).reshape(-1)
-        out = (Station * max(max_out, 1))()
-        n = C.c_int()
-        _check(lib().fmrx_scan(self.h, _np_ptr(iq), iq.size // 2, C.byref(scan_config(**cfg)), out, max_out,
-                               C.byref(n)))
-        return _stations(out, min(n.value, max_out))
+        return self._scan(lib().fmrx_scan, iq, max_out, cfg)
 
     def synchronize(self) -> None:
         _check(lib().fmrx_synchronize(self.h))

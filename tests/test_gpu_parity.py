@@ -192,7 +192,7 @@ def test_state_blob_header_errors(fmrx):
 
 
 def test_trig_hint_after_set_state(fmrx, monkeypatch):
-    """The host-side trigOffset bounds that pick which PLL runners launch (api.cpp TrigTrack)
+    """The host-side trigOffset bounds that pick which PLL runners launch (ctx.h TrigTrack)
     follow a restored blob: a stream restored at 2^20 - 2,000 crosses into the predicted
     runner's range within the call and one at 2^24 - 3,000 into the saturated runner's; the PCM
     equals the lane runner's alone (knob pll_pred=0, knob pll_sat=0: every segment on it), and
@@ -494,7 +494,7 @@ def test_stereo_multistream(fmrx, orc):
                                                            (0, 70, 120, None, -3), (0, 70, 120, None, -4),
                                                            (0, 5, 48, "3", -4), (0, 5, 48, "2", -3)])
 def test_stereo_pipelined_chunks(fmrx, orc, monkeypatch, mode, n_streams, nb, chunks, lead):
-    """The pipelined stereo engine (api.cpp run_stereo_pipelined): a call's blocks in chunks,
+    """The pipelined stereo engine (engine.cpp run_stereo_pipelined): a call's blocks in chunks,
     front end + band-pass of chunk k + 1 and audio of chunk k - 1 on their own HIP streams beside
     the PLL of chunk k, every chunk reading the call's buffers at its offset (a chunk's RF halo
     is the call's own bytes in front of it).  knob stereo_chunks forces the chunk count (None: the
@@ -536,7 +536,7 @@ def test_stereo_pipelined_head_tail(fmrx, orc, monkeypatch, head, tail):
 
 def test_stereo_pipelined_checkpoint_resume(fmrx, orc, monkeypatch):
     """The pipelined engine's carried state (demod history, PLL with its trigOffset hint, mixer
-    tail, mono delay; api.cpp run_stereo_pipelined) through a checkpoint: 16 streams (the
+    tail, mono delay; engine.cpp run_stereo_pipelined) through a checkpoint: 16 streams (the
     engine's default threshold) in pipelined calls, the blob into a second context, which goes
     on pipelined, bit-exact against the oracle on three streams."""
     knobs(monkeypatch, fmrx, stereo_chunks=3)
@@ -605,7 +605,7 @@ def test_pll_speculation_fallbacks(fmrx, orc, monkeypatch, env, n_streams, nb):
 
 @pytest.mark.parametrize("skew", [4194304.0, 1048576.0, 16777216.0])
 def test_pll_wrong_hint_fails_safe(fmrx, orc, monkeypatch, skew):
-    """The host picks a segment's runners from its trigOffset bounds (api.cpp TrigTrack).  With
+    """The host picks a segment's runners from its trigOffset bounds (ctx.h TrigTrack).  With
     the bounds deliberately wrong (test hook knob pll_hint_skew: the host believes the streams
     are `skew` samples further on), the runners launched leave the streams alone; the pre-pass's
     fail[] sentinel (0) then makes pll_kernel resume each such stream's whole segment on the
@@ -699,7 +699,7 @@ def test_stereo_long_hash_three_streams(fmrx):
 
 
 def _stream_blob(multi: bytes, single_hdr: bytes, ns: int, s: int) -> bytes:
-    """Stream s's slice of an n_streams state blob, as a 1-stream blob (api.cpp state_io order:
+    """Stream s's slice of an n_streams state blob, as a 1-stream blob (context.cpp state_io order:
     halo, audio history, demod history, PLL, mixer tail, mono state)."""
     hdr = np.frombuffer(multi[:40], np.uint32)
     sizes = [int(hdr[6]), 4 * int(hdr[7]), 4 * 64, 4 * 8, 4 * 64, 4 * 8]
@@ -757,7 +757,7 @@ def _unlocked_input(rx, h):
 
 def _pll_floats(rx):
     """A 1-stream context's PLL state {integrator, phaseEst, fbI, fbQ, ncoOut_state, trigOffset}
-    from its state blob (api.cpp state_io order: halo, audio history, demod history, PLL)."""
+    from its state blob (context.cpp state_io order: halo, audio history, demod history, PLL)."""
     blob = rx.get_state()
     hdr = np.frombuffer(blob[:40], np.uint32)
     off = 40 + int(hdr[6]) + 4 * int(hdr[7]) + 4 * 64
@@ -1341,7 +1341,7 @@ def _recipe_bytes(recipe, n):
 
 
 def _pll_rows(rx, ns):
-    """Every stream's 8-float PLL row of a context's state blob (api.cpp state_io order)."""
+    """Every stream's 8-float PLL row of a context's state blob (context.cpp state_io order)."""
     blob = rx.get_state()
     hdr = np.frombuffer(blob[:40], np.uint32)
     off = 40 + ns * (int(hdr[6]) + 4 * int(hdr[7]) + 4 * 64)
@@ -1438,7 +1438,7 @@ _FORM_EDGES = [(262144.0, 16, 16), (524288.0, 16, 64), (1048576.0, 64, 128), (20
 
 
 def _chunk_begin(nb, k, K, head=8, tail=8):
-    """api.cpp chunk_begin: the first block of chunk k of K (the first chunk head / 16 of a middle
+    """engine.cpp chunk_begin: the first block of chunk k of K (the first chunk head / 16 of a middle
     one, the last tail / 16)."""
     if K <= 1 or k <= 0:
         return 0 if k <= 0 else nb
@@ -1448,7 +1448,7 @@ def _chunk_begin(nb, k, K, head=8, tail=8):
 
 
 def _default_chunks(nb, ns):
-    """api.cpp stereo_chunks without the knob: 8 from 16 streams, fewer until a chunk holds 2^14 steps."""
+    """engine.cpp stereo_chunks without the knob: 8 from 16 streams, fewer until a chunk holds 2^14 steps."""
     k = 8 if ns >= 16 else 1
     while k > 1 and nb * 640 // k < 16384:
         k -= 1
@@ -1487,7 +1487,7 @@ def test_demote_once_across_form_edges(fmrx, monkeypatch, edge, ni_front, ni_beh
     launch a chunk; the launch behind the edge only adds its steps to state slot 6), the first
     chunk two blocks (knobs stereo_head = 2, stereo_tail = 64).
       chunks None: the default chunk count, which is two at this length (_default_chunks mirrors
-    api.cpp): equal halves, the first a chunk in which the streams demote too; for the 2^22 and
+    engine.cpp): equal halves, the first a chunk in which the streams demote too; for the 2^22 and
     2^24 edges, whose last chunk needs more than a half, knob stereo_tail = 64.
     The PCM of every stream and the whole PLL state (8 floats a stream: slot 6 cleared) equal the
     same call on the plain certified launch (knob pll_spec = 0, which
@@ -2039,7 +2039,7 @@ def _at_trig(rx, ns, trig):
 
 
 def test_knob_sweep_bit_exact(fmrx, orc):
-    """Every tuning knob (api.cpp kKnobs) over its accepted range, one at a time, through
+    """Every tuning knob (context.cpp kKnobs) over its accepted range, one at a time, through
     fmrx_debug_set_knob: a 20-stream 40-block stereo call from power-on (the pipelined engine:
     chunking, deferral, band-pass form) against the oracle, the same call with every stream's PLL put
     at trigOffset 2^19 - 6,000 and at 2^22 - 6,000 (the count / index / three-wave runners, their

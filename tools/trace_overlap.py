@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Stage overlap inside one stereo call, from a rocprofv3 kernel trace (run_kernel_trace.csv).
 
-The pipelined engine (api.cpp run_stereo_pipelined) puts the front end + band-pass pair, the PLL
+The pipelined engine (engine.cpp run_stereo_pipelined) puts the front end + band-pass pair, the PLL
 and the audio stage on three HIP streams (three hardware queues).  A call ends with one
 stereo_state_kernel; this takes the LAST call in the trace (from the first kernel after the
 previous stereo_state_kernel to its own), and prints one JSON line: the call's device span, each
