@@ -297,6 +297,47 @@ int fmrx_scan_detect_wide(const float* power, int fft_bins, int rf_fs, int decim
 int fmrx_scan_wide(fmrx_ctx* ctx, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg,
                    fmrx_station* out, int max_out, int* n_found);
 
+/* ---- captures at a rational rate: a polyphase down-converter ahead of the tuner ------------------- */
+/* A capture at cap_fs Hz with rf_fs / cap_fs = L / M in lowest terms, 2 <= L <= 48, L < M <= 125,
+ * M <= 10 L (10, 8, 20, 6, 3, 2.5, 12.5, 2.56, 3.2 MS/s against 2.4 MS/s; 2.048 against 1.152; ...) goes
+ * through a rational down-converter on the GPU (csrc/rate.hip) down to rf_fs, then through
+ * the tuned front end unchanged.  An offset f Hz (2 |f| < cap_fs) splits as in the wide section (q, f_c =
+ * q rf_fs / 4, f_r = f - f_c).  Wide pair n is rotated at the capture rate with g = gcd(|q| L, 4 M),
+ * N = 4 M / g <= 500, k = (q L / g) mod N (q = 0: N = 1, k = 0), p = (k n) mod N and the wide section's
+ * formulas for I', Q'; then h = fmrx_impulse_response_lpf((float)rf_fs (float)M, 3 rf_fs / 8, 16 M + 1, L) and
+ *   y[m] = sum h[k] (I', Q')[(m M - k) / L] over the k in 0..16 M with k = m M (mod L), ascending,
+ *   acc = fl(acc + fl(h[k] x)) from 0, pairs in front of the stream being 0
+ * (fmrx_resample's definition with up = L, down = M).  The pairs y[m] are a cf32 stream at rf_fs that takes
+ * the path of an FMRX_IQ_F32 stream tuned to f_r, pair m at absolute index first_pair L / M + m.
+ * fmrx_rate_design is host only: *up = L, *down = M, the split, N, k, the table (2 N <= 1000 floats) and
+ * the taps (*taps = 16 M + 1 <= 2001 floats in h); every output pointer may be NULL.  An integer ratio
+ * D = 2..10 answers as fmrx_wide_design does, with *up = 1, *down = D.  FMRX_EINVAL, nothing written:
+ * rf_fs not a positive multiple of 4, cap_fs <= rf_fs, a ratio outside the limits, 2 |f| >= cap_fs, a fine
+ * part fmrx_tuner_design refuses.                                                                     */
+int fmrx_rate_design(int rf_fs, int cap_fs, int offset_hz, int* up, int* down, int* coarse_hz, int* fine_hz,
+                     int* N, int* k, float* cos_sin, int* taps, float* h);
+/* The capture's rate in Hz.  An integer ratio (L = 1; cap_fs = rf_fs is D = 1) does exactly what
+ * fmrx_set_capture_decim(ctx, D) does.  A rational one allocates the rational wide state (the last
+ * ceil(16 M / L) raw wide pairs, the taps, a 500-entry table a stream, and the cf32 rows and f32 halo of
+ * the wide stage), then does what fmrx_reset does.  While it is set: fmrx_capture_decim reports 0;
+ * fmrx_get_state, fmrx_set_state and fmrx_seek return FMRX_ESTATE; fmrx_set_input_format keeps the rate;
+ * fmrx_set_capture_decim leaves it; fmrx_tune_wide, fmrx_wide_info, fmrx_process_wide(_device) and
+ * fmrx_scan_wide serve it with their meanings, offsets against cap_fs and positions in wide pairs:
+ * first_pair of fmrx_tune_wide is a multiple of M, and n_blocks of a wide call (still narrow blocks of
+ * PCM out) a multiple of the granule's blocks (FMRX_EINVAL and no launch otherwise).  FMRX_EINVAL,
+ * nothing changed: a rate fmrx_rate_design refuses, no tuned kernel for the mode and tap count, a
+ * granule that is no whole number of two-pair staging units.                                          */
+int fmrx_set_capture_rate(fmrx_ctx* ctx, int cap_fs);
+/* read back (each may be NULL): the rate, L, M; an integer ratio D reads D rf_fs, 1, D */
+int fmrx_capture_rate(const fmrx_ctx* ctx, int* cap_fs, int* up, int* down);
+/* The unit of a wide call: B = L / gcd(L, geo.iq_pairs) narrow blocks = B geo.iq_pairs M / L wide pairs
+ * (mode 0 at 10 MS/s: 3 and 80000); an integer ratio D reads 1 and D geo.iq_pairs.                    */
+int fmrx_wide_granule(const fmrx_ctx* ctx, size_t* blocks, size_t* wide_pairs);
+/* fmrx_scan_detect with rf_fs := cap_fs and "a candidate fmrx_rate_design(rf_fs, cap_fs, ...) refuses"
+ * in place of "fmrx_tuner_design refuses"; host only.                                                 */
+int fmrx_scan_detect_rate(const float* power, int fft_bins, int rf_fs, int cap_fs, const fmrx_scan_config* cfg,
+                          fmrx_station* out, int max_out, int* n_found, float* floor_db);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

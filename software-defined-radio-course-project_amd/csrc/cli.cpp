@@ -1,5 +1,6 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
-// [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]`:
+// [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]
+// [--capture-rate HZ]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -24,6 +25,11 @@
 //     the mode's rate (fmrx_set_capture_decim): blocks of D * iq_pairs pairs, --offset-hz against that
 //     rate (fmrx_tune_wide; without it offset 0), decoded by fmrx_process_wide_device; --scan then runs
 //     fmrx_scan_wide.  D = 1 is the same as no flag; anything else outside 2..10: message, exit 1.
+//   * --capture-rate HZ (an fmrx extension) reads stdin as a capture at HZ samples a second
+//     (fmrx_set_capture_rate: HZ = rf_fs M / L, a rational ratio through the polyphase down-converter,
+//     an integer one as --capture-decim): stdin in whole granules (fmrx_wide_granule), --offset-hz and
+//     --scan against that rate.  With --capture-decim: message, exit 1; a rate the library refuses:
+//     message, exit 1.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -41,6 +47,7 @@
 // dropped, as in the reference.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -95,6 +102,8 @@ void usage(const char* argv0) {
                  "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
                  "                [--capture-decim D]  stdin runs at D (2..10) times the mode's rate; --offset-hz and\n"
                  "                                     --scan then refer to that rate (default 1)\n"
+                 "                [--capture-rate HZ]  stdin runs at HZ samples a second (10000000, 8000000, 2048000 ...),\n"
+                 "                                     read in whole granules; not with --capture-decim\n"
                  "                [--scan [--scan-bytes B]]  list the stations of the first B bytes (default 16777216)\n"
                  "                                           as `offset_hz power_db snr_db` lines; no PCM\n",
                  argv0, argv0);
@@ -148,6 +157,8 @@ int main(int argc, char** argv) {
     bool mono_product = false, tuned = false, scan = false;
     long offset_hz = 0;
     int iq_format = FMRX_IQ_U8, capture_decim = 1;
+    long capture_rate = 0;
+    bool have_decim = false, have_rate = false;
     const char* bad_format = nullptr;
     long long scan_bytes = 1ll << 24;
     std::vector<const char*> pos;
@@ -166,7 +177,14 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(f, "f32")) iq_format = FMRX_IQ_F32;
             else bad_format = f;
         }
-        else if (!std::strcmp(argv[i], "--capture-decim") && i + 1 < argc) capture_decim = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--capture-decim") && i + 1 < argc) {
+            capture_decim = std::atoi(argv[++i]);
+            have_decim = true;
+        }
+        else if (!std::strcmp(argv[i], "--capture-rate") && i + 1 < argc) {
+            capture_rate = std::atol(argv[++i]);
+            have_rate = true;
+        }
         else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) {
             offset_hz = std::atol(argv[++i]);
             tuned = true;
@@ -195,7 +213,15 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "fmrx: --capture-decim %d: expected 1 to 10\n", capture_decim);
         return 1;
     }
-    const bool wide = capture_decim > 1;
+    if (have_rate && have_decim) {
+        std::fprintf(stderr, "fmrx: --capture-rate and --capture-decim exclude each other\n");
+        return 1;
+    }
+    if (have_rate && (capture_rate < 1 || capture_rate > 2147483647l)) {
+        std::fprintf(stderr, "fmrx: --capture-rate %ld: expected a rate in Hz\n", capture_rate);
+        return 1;
+    }
+    bool wide = capture_decim > 1;
     if (batch < 1) batch = 1;
     std::fprintf(stderr, "Operating in mode %d, %s\n", mode, channels == 1 ? "mono" : "stereo");
 
@@ -224,8 +250,21 @@ int main(int argc, char** argv) {
         fmrx_destroy(ctx);
         return 1;
     }
+    // what one read unit is: a block, or with --capture-rate a granule of unit_blocks blocks
+    size_t unit_blocks = 1, unit_pairs = geo.iq_pairs * (size_t)capture_decim;
+    if (have_rate) {
+        int d = 1;
+        if (fmrx_set_capture_rate(ctx, (int)capture_rate) != FMRX_OK || fmrx_capture_decim(ctx, &d) != FMRX_OK ||
+            fmrx_wide_granule(ctx, &unit_blocks, &unit_pairs) != FMRX_OK) {
+            std::fprintf(stderr, "fmrx: --capture-rate: %s\n", fmrx_last_error());
+            fmrx_destroy(ctx);
+            return 1;
+        }
+        wide = d != 1;  // the mode's own rate is no wide capture
+    }
     const size_t pair_bytes = (size_t)fmrx_iq_pair_bytes(iq_format);
-    const size_t block_bytes = geo.iq_pairs * pair_bytes * (size_t)capture_decim;  // geo.block_bytes for u8
+    const size_t block_bytes = unit_pairs * pair_bytes;  // bytes a read unit; geo.block_bytes for u8 at the mode's rate
+    batch = (int)(std::max<size_t>(1, (size_t)batch / unit_blocks) * unit_blocks);  // whole units
     if (scan) {
         const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes, pair_bytes, wide) : 1;
         if (scan_bytes <= 0) std::fprintf(stderr, "fmrx: --scan-bytes must be positive\n");
@@ -241,7 +280,7 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const size_t in_cap = block_bytes * (size_t)batch;
+    const size_t in_cap = block_bytes * ((size_t)batch / unit_blocks);
     const size_t out_cap = geo.pcm_samples * (size_t)batch;
 
     CLI_HIP(hipSetDevice(device));
@@ -273,7 +312,7 @@ int main(int argc, char** argv) {
                 if (r == 0) break;
                 got += r;
             }
-            s.blocks = got / block_bytes;
+            s.blocks = got / block_bytes * unit_blocks;
             s.last = got < in_cap;
             filled_q.push(i);
             if (s.last) return;
@@ -296,7 +335,7 @@ int main(int argc, char** argv) {
         const int i = filled_q.pop();
         Slot& s = slots[i];
         if (s.blocks > 0) {
-            CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks * block_bytes, hipMemcpyHostToDevice, up));
+            CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks / unit_blocks * block_bytes, hipMemcpyHostToDevice, up));
             CLI_HIP(hipEventRecord(s.uploaded, up));
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
             if ((wide ? fmrx_process_wide_device : fmrx_process_device)(ctx, s.d_in, s.blocks, s.d_out) != FMRX_OK) {

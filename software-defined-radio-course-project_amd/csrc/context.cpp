@@ -59,9 +59,9 @@ int reset_state(fmrx_ctx* c) {
     HIPCHK(hipMemsetAsync(c->d_halo[0].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     HIPCHK(hipMemsetAsync(c->d_halo[1].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     c->halo_cur = 0;
-    if (c->wide_decim > 1) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
+    if (wide_on(c)) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
         const size_t nh = c->halo_pairs * 8 * ns;
-        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), 16 * (size_t)c->wide_decim * c->pair_bytes, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), wide_hist_pairs(c) * c->pair_bytes, c->stream));
         HIPCHK(hipMemsetAsync(c->d_wide_halo[0].p, 0, nh, c->stream));
         HIPCHK(hipMemsetAsync(c->d_wide_halo[1].p, 0, nh, c->stream));
         c->wide_halo_cur = 0;
@@ -378,7 +378,7 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     CtxLock lock_(c);
     if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
-    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
+    if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
     if (n % c->pair_bytes != 0)
         return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
     int rc = set_device(c);
@@ -486,14 +486,14 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
 int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
-    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
 
 int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
-    if (c->wide_decim > 1) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
     if (rc == 0) {

@@ -15,6 +15,7 @@
 
 #include "../../include/fmrx.h"
 #include "fmrx_internal.h"
+#include "rate.h"
 #include "tuner.h"
 
 namespace fmrx {
@@ -180,6 +181,11 @@ struct Ctx {
     size_t wide_y_stride = 0;
     DevBuf<uint8_t> d_wide_halo[2];           // the narrow stage's f32 halo (halo_pairs x 8 B a stream)
     int wide_halo_cur = 0;
+    // a capture at a rational rate (fmrx_set_capture_rate, rate.hip): cap_fs = rf_fs rate_down / rate_up
+    // in lowest terms.  rate_up = 0: none; otherwise wide_decim is 0 and the wide stage's buffers above
+    // hold the rational stage's history, taps by phase, tables (kRateMaxN a stream), rows and halo
+    int rate_up = 0, rate_down = 0, rate_cap_fs = 0;
+    size_t rate_blocks = 1;                   // narrow blocks a granule: rate_up / gcd(rate_up, iq_pairs)
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -257,6 +263,21 @@ inline int check_call_size(const fmrx_ctx* c, size_t n_blocks, size_t decim = 1)
         return fail(FMRX_EINVAL, "%zu blocks: the call's byte count overflows", n_blocks);
     return 0;
 }
+// The wide stage (integer or rational) is on
+inline bool wide_on(const fmrx_ctx* c) { return c->wide_decim != 1; }
+// Raw wide pairs of history the wide stage keeps in front of the next call
+inline size_t wide_hist_pairs(const fmrx_ctx* c) {
+    return c->rate_up ? (size_t)rate_hist_pairs(c->rate_up, c->rate_down) : 16 * (size_t)c->wide_decim;
+}
+// Wide pairs that n_blocks narrow blocks take (n_blocks a whole number of granules)
+inline size_t wide_pairs_of(const fmrx_ctx* c, size_t n_blocks) {
+    if (c->rate_up) return n_blocks * c->geo.iq_pairs / (size_t)c->rate_up * (size_t)c->rate_down;
+    return n_blocks * c->geo.iq_pairs * (size_t)c->wide_decim;
+}
+// check_call_size's factor of a wide call: wide pairs a narrow pair, rounded up
+inline size_t wide_size_factor(const fmrx_ctx* c) {
+    return c->rate_up ? (size_t)((c->rate_down + c->rate_up - 1) / c->rate_up) : (size_t)c->wide_decim;
+}
 inline int set_device(const fmrx_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     return 0;
@@ -293,5 +314,7 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
 // decim within the down-converter's range (or_one: 1, no wide stage, passes too); rf_fs a positive multiple of 4
 int check_capture_decim(int decim, bool or_one);
 int check_wide_rf_fs(int rf_fs);
+// n_blocks of a wide call: whole granules of a rational context (FMRX_EINVAL otherwise)
+int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks);
 
 }  // namespace fmrx

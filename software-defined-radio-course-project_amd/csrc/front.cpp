@@ -1,8 +1,11 @@
 // front.cpp — the front ends ahead of the audio stages other than the fused kernel: the tuned front
-// end (tuner.hip) and the wide down-converter in front of it (wide.hip), with the calls that
-// configure them: tuning, the raw I/Q format and the capture decimation.
+// end (tuner.hip) and the wide down-converters in front of it (wide.hip for an integer ratio, rate.hip
+// for a rational one), with the calls that configure them: tuning, the raw I/Q format, the capture
+// decimation and the capture rate.
 #include "ctx.h"
 #include "wide.h"
+
+#include <numeric>
 
 using namespace fmrx;
 
@@ -145,11 +148,70 @@ int check_wide_rf_fs(int rf_fs) {
     return 0;
 }
 
+int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks) {
+    if (c->rate_up && n_blocks % c->rate_blocks != 0)
+        return fail(FMRX_EINVAL, "%zu blocks: a call at %d S/s takes whole granules of %zu blocks", n_blocks, c->rate_cap_fs,
+                    c->rate_blocks);
+    return 0;
+}
+
+// run_wide at a rational rate (fmrx_set_capture_rate): the same steps with rate.hip's kernel, pieces of
+// whole granules, and the history of rate_hist_pairs raw pairs.
+static int run_rate(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    const int ns = c->cfg.n_streams, up = c->rate_up, down = c->rate_down;
+    const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples, gran = c->rate_blocks;
+    const size_t hb = wide_hist_pairs(c) * c->pair_bytes;
+    int rc = ensure_demod(c, n_if);
+    if (rc) return rc;
+    const size_t fit = kWidePieceBytes / ((size_t)ns * ip * 8);
+    const size_t piece = std::min(n_blocks, std::max(gran, fit / gran * gran));
+    if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->wide_y_stride = 0;
+        if ((rc = c->d_wide_y.ensure((size_t)ns * piece * ip * 2))) return rc;
+        c->wide_y_stride = piece * ip * 2;
+    }
+    const size_t nhb = c->halo_pairs * 8;
+    for (size_t b0 = 0; b0 < n_blocks; b0 += piece) {
+        const size_t nb = std::min(piece, n_blocks - b0);
+        RateLaunch R{};
+        R.iq = d_iq + wide_pairs_of(c, b0) * c->pair_bytes;
+        R.hist = b0 == 0 ? c->d_wide_hist.p : R.iq - hb;
+        R.stream_bytes = wide_pairs_of(c, nb) * c->pair_bytes;
+        R.y = c->d_wide_y.p;
+        R.y_stride = c->wide_y_stride;
+        R.n_out = (long long)(nb * ip);
+        R.segs = rate_segments(R.n_out, up, down, ns, c->n_simd / 4);
+        R.format = c->iq_format;
+        R.up = up;
+        R.down = down;
+        R.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
+        R.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
+        R.hp = reinterpret_cast<const RateTap*>(c->d_wide_taps.p);
+        R.first_pair = c->tune_pos / (uint64_t)up * (uint64_t)down;  // tune_pos is a multiple of up
+        TimingPair* ev = nullptr;  // fmrx_kernel_timing: the down-converter's launches
+        if ((rc = timing_begin(c, c->stream, &ev))) return rc;
+        rc = launch_rate_ddc(R, ns, c->stream);
+        if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "rational down-converter launch failed (%d)", rc);
+        if ((rc = timing_end(ev, c->stream))) return rc;
+        if ((rc = launch_front(c, reinterpret_cast<const uint8_t*>(c->d_wide_y.p), c->wide_y_stride * sizeof(float), kIqF32,
+                               c->d_wide_halo, &c->wide_halo_cur, nhb, nb, c->d_demod.p + b0 * c->geo.if_samples,
+                               c->demod_stride, kDemodHist, false)))
+            return rc;
+    }
+    // the next call's history: the capture's last raw pairs (a granule holds more than that)
+    HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + wide_pairs_of(c, n_blocks) * c->pair_bytes - hb, hb,
+                          hipMemcpyDeviceToDevice, c->stream));
+    if (c->cfg.channels != FMRX_MONO) return run_stereo_audio(c, n_blocks, d_pcm, nullptr);
+    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, nullptr);
+}
+
 // A wide call (fmrx_process_wide_device; arguments checked, device set): per piece of whole blocks
 // the down-converter (wide.hip) into the y rows, then the tuned front end reading them as an f32
 // stream with the wide stage's own halo; the demod rows of the whole call then take the audio stage
 // a tuned call takes.  A piece past the first finds its history in the capture itself.
 int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    if (c->rate_up) return run_rate(c, d_iq, n_blocks, d_pcm);
     const int ns = c->cfg.n_streams, D = c->wide_decim;
     const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples;
     const size_t wide_block = (size_t)D * iq_block_bytes(c), hb = 16 * (size_t)D * c->pair_bytes;
@@ -196,6 +258,40 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) 
 }
 
 }  // namespace fmrx
+
+namespace {
+
+// fmrx_tune_wide of a context at a rational rate: fmrx_rate_design in fmrx_wide_design's place
+int tune_rate(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    const int up = c->rate_up, down = c->rate_down;
+    if (first_pair % (uint64_t)down != 0)
+        return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of %d (the rate is %d/%d of the mode's)",
+                    (unsigned long long)first_pair, down, down, up);
+    const size_t ns = c->cfg.n_streams;
+    std::vector<int32_t> fine(ns);
+    std::vector<WideStream> ws(ns);
+    std::vector<float> tab(2 * (size_t)kRateMaxN * ns, 0.0f);
+    int rc;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int fr = 0, n = 0, k = 0;
+        if ((rc = fmrx_rate_design(c->geo.rf_fs, c->rate_cap_fs, offsets_hz[s], nullptr, nullptr, nullptr, &fr, &n, &k,
+                                   tab.data() + 2 * kRateMaxN * s, nullptr, nullptr)))
+            return rc;
+        fine[s] = fr;
+        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
+    }
+    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
+    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
+    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
+    c->tune_pos = first_pair / (uint64_t)down * (uint64_t)up;
+    c->tuned = true;
+    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
+    c->wide_tuned = true;
+    return FMRX_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -252,7 +348,7 @@ int fmrx_set_input_format(fmrx_ctx* c, int format) {
         const size_t ns = c->cfg.n_streams, hb = c->halo_pairs * (size_t)pb;
         if (format != kIqU8 && !c->tuned && (rc = upload_zero_offsets(c))) return rc;
         if ((rc = c->d_halo[0].ensure(hb * ns)) || (rc = c->d_halo[1].ensure(hb * ns))) return rc;
-        if (c->wide_decim > 1 && (rc = c->d_wide_hist.ensure(16 * (size_t)c->wide_decim * (size_t)pb))) return rc;
+        if (wide_on(c) && (rc = c->d_wide_hist.ensure(wide_hist_pairs(c) * (size_t)pb))) return rc;
         c->iq_format = format;
         c->pair_bytes = (size_t)pb;
         c->halo_bytes = hb;
@@ -301,7 +397,7 @@ int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
     if (!c) return fail(FMRX_EINVAL, "null context");
     int rc = check_capture_decim(decim, true);
     if (rc) return rc;
-    if (decim == 1 && c->wide_decim == 1) return FMRX_OK;  // the default: nothing anywhere changes
+    if (decim == 1 && c->wide_decim == 1) return FMRX_OK;  // the default: nothing anywhere changes (a rational rate: 0)
     if (decim > 1 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
         return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
                     c->geo.rf_decim);
@@ -318,6 +414,8 @@ int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
         HIPCHK(hipMemcpy(c->d_wide_taps.p, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
     }
     c->wide_decim = decim;
+    c->rate_up = c->rate_down = c->rate_cap_fs = 0;  // out of a rational rate
+    c->rate_blocks = 1;
     c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
     return reset_state(c);
 }
@@ -332,6 +430,7 @@ int fmrx_capture_decim(const fmrx_ctx* c, int* decim) {
 int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
     CtxLock lock_(c);
     if (!c || !offsets_hz) return fail(FMRX_EINVAL, "null argument");
+    if (c->rate_up) return tune_rate(c, offsets_hz, first_pair);
     const int D = c->wide_decim;
     if (D == 1) return fail(FMRX_ESTATE, "fmrx_tune_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
     if (first_pair % (uint64_t)D != 0)
@@ -361,11 +460,101 @@ int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) 
     return FMRX_OK;
 }
 
+// ---- captures at a rational rate: the polyphase down-converter ahead of the tuner -------------------
+int fmrx_rate_design(int rf_fs, int cap_fs, int offset_hz, int* up, int* down, int* coarse_hz, int* fine_hz, int* N, int* k,
+                     float* cos_sin, int* taps, float* h) {
+    int l = 0, m = 0;
+    const int kind = rate_ratio(rf_fs, cap_fs, &l, &m);
+    if (kind < 0 || (kind == 1 && m == 1))
+        return fail(FMRX_EINVAL, "capture rate %d S/s against %d S/s: need cap_fs / rf_fs = M / L with L <= %d, L < M <= %d, M <= 10 L",
+                    cap_fs, rf_fs, kRateMaxUp, kRateMaxDown);
+    if (kind == 1) {  // an integer ratio: the existing stage's design
+        const int rc = fmrx_wide_design(rf_fs, m, offset_hz, coarse_hz, fine_hz, N, k, cos_sin, taps, h);
+        if (rc) return rc;
+        if (up) *up = 1;
+        if (down) *down = m;
+        return FMRX_OK;
+    }
+    int fc = 0, fr = 0, n = 0, kk = 0;
+    if (!rate_split(rf_fs, l, m, offset_hz, &fc, &fr, &n, &kk, nullptr))
+        return fail(FMRX_EINVAL, "offset %d Hz outside (-%d/2, %d/2)", offset_hz, cap_fs, cap_fs);
+    int tn = 0, tk = 0, rc;
+    if ((rc = fmrx_tuner_design(rf_fs, fr, &tn, &tk, nullptr))) return rc;  // the fine part goes to the tuner
+    if (up) *up = l;
+    if (down) *down = m;
+    if (coarse_hz) *coarse_hz = fc;
+    if (fine_hz) *fine_hz = fr;
+    if (N) *N = n;
+    if (k) *k = kk;
+    if (cos_sin) rate_split(rf_fs, l, m, offset_hz, nullptr, nullptr, nullptr, nullptr, cos_sin);
+    if (taps) *taps = rate_taps(m);
+    if (h) design_lpf(h, (float)rf_fs * (float)m, (float)(3.0 * rf_fs / 8.0), rate_taps(m), l);
+    return FMRX_OK;
+}
+
+int fmrx_set_capture_rate(fmrx_ctx* c, int cap_fs) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    int up = 0, down = 0;
+    const int kind = rate_ratio(c->geo.rf_fs, cap_fs, &up, &down);
+    if (kind < 0)
+        return fail(FMRX_EINVAL, "capture rate %d S/s against %d S/s: need cap_fs / rf_fs = M / L with L <= %d, L < M <= %d, M <= 10 L",
+                    cap_fs, c->geo.rf_fs, kRateMaxUp, kRateMaxDown);
+    if (kind == 1) return fmrx_set_capture_decim(c, down);  // an integer ratio: the existing stage
+    if (!tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
+                    c->geo.rf_decim);
+    // the granule: the fewest narrow blocks that are a whole number of wide pairs (of staging units)
+    const size_t ip = c->geo.iq_pairs;
+    const size_t blocks = (size_t)up / std::gcd((size_t)up, ip), wide = blocks * ip / (size_t)up * (size_t)down;
+    if (wide % 2 != 0 || wide < (size_t)rate_hist_pairs(up, down))
+        return fail(FMRX_EINVAL, "capture rate %d S/s: a granule of %zu wide pairs is no whole number of staging units", cap_fs, wide);
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the wide state
+    const size_t ns = c->cfg.n_streams;
+    std::vector<float> h((size_t)rate_taps(down));
+    std::vector<RateTap> hp((size_t)up * rate_phase_stride(up, down));
+    design_lpf(h.data(), (float)c->geo.rf_fs * (float)down, (float)(3.0 * c->geo.rf_fs / 8.0), rate_taps(down), up);
+    rate_taps_by_phase(h.data(), up, down, hp.data());
+    if ((rc = c->d_wide_hist.ensure((size_t)rate_hist_pairs(up, down) * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(2 * hp.size())) ||
+        (rc = c->d_wide_tab.ensure(2 * (size_t)kRateMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
+        (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
+        return rc;
+    HIPCHK(hipMemcpy(c->d_wide_taps.p, hp.data(), sizeof(RateTap) * hp.size(), hipMemcpyHostToDevice));
+    c->wide_decim = 0;  // what fmrx_capture_decim reports at a rational rate
+    c->rate_up = up;
+    c->rate_down = down;
+    c->rate_cap_fs = cap_fs;
+    c->rate_blocks = blocks;
+    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
+    return reset_state(c);
+}
+
+int fmrx_capture_rate(const fmrx_ctx* c, int* cap_fs, int* up, int* down) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (cap_fs) *cap_fs = c->rate_up ? c->rate_cap_fs : c->wide_decim * c->geo.rf_fs;
+    if (up) *up = c->rate_up ? c->rate_up : 1;
+    if (down) *down = c->rate_up ? c->rate_down : c->wide_decim;
+    return FMRX_OK;
+}
+
+int fmrx_wide_granule(const fmrx_ctx* c, size_t* blocks, size_t* wide_pairs) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    const size_t b = c->rate_up ? c->rate_blocks : 1;
+    if (blocks) *blocks = b;
+    if (wide_pairs) *wide_pairs = wide_pairs_of(c, b);
+    return FMRX_OK;
+}
+
 int fmrx_wide_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
     if (offsets_hz) std::copy(c->wide_offsets.begin(), c->wide_offsets.end(), offsets_hz);
-    if (next_pair) *next_pair = c->tune_pos * (uint64_t)c->wide_decim;
+    if (next_pair)
+        *next_pair = c->rate_up ? c->tune_pos / (uint64_t)c->rate_up * (uint64_t)c->rate_down : c->tune_pos * (uint64_t)c->wide_decim;
     if (enabled) *enabled = c->wide_tuned ? 1 : 0;
     return FMRX_OK;
 }

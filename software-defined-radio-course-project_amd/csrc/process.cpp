@@ -138,7 +138,8 @@ int fmrx_process_wide_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, 
     if (n_blocks == 0) return FMRX_OK;
     if (reinterpret_cast<uintptr_t>(d_iq) % (2 * c->pair_bytes) != 0)
         return fail(FMRX_EINVAL, "wide calls need a %zu-byte aligned capture", 2 * c->pair_bytes);
-    if ((rc = check_call_size(c, n_blocks, (size_t)c->wide_decim)) || (rc = set_device(c))) return rc;
+    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, wide_size_factor(c))) || (rc = set_device(c)))
+        return rc;
     return run_wide(c, d_iq, n_blocks, d_pcm);
 }
 
@@ -159,8 +160,8 @@ int fmrx_process_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* 
     if (rc) return rc;
     if (n_blocks == 0) return FMRX_OK;
     if ((rc = set_device(c))) return rc;
-    if ((rc = check_call_size(c, n_blocks, (size_t)c->wide_decim))) return rc;
-    const size_t in_bytes = n_blocks * (size_t)c->wide_decim * iq_block_bytes(c);
+    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, wide_size_factor(c)))) return rc;
+    const size_t in_bytes = wide_pairs_of(c, n_blocks) * c->pair_bytes;
     const size_t out_n = (size_t)c->cfg.n_streams * n_blocks * c->geo.pcm_samples;
     return staged_call(c, iq, in_bytes, true, c->d_out, pcm, out_n, false, [&](const void* d_iq, int16_t* d_pcm, bool) {
         return fmrx_process_wide_device(c, static_cast<const uint8_t*>(d_iq), n_blocks, d_pcm);

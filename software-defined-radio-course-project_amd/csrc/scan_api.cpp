@@ -136,9 +136,10 @@ fmrx_scan_config scan_config_of(const fmrx_scan_config* cfg_in) {
 
 // The detector of fmrx_scan_detect (decim = 1) and fmrx_scan_detect_wide (decim > 1: rf_fs is then the
 // capture's rate, and a candidate is checked by fmrx_wide_design instead of fmrx_tuner_design).  Host
-// arrays in and out: nothing here touches the GPU.
+// arrays in and out: nothing here touches the GPU.  mode_fs > 0 (fmrx_scan_detect_rate): rf_fs is a
+// capture rate any ratio above the mode's rate mode_fs, and fmrx_rate_design checks a candidate.
 int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, const fmrx_scan_config& cfg, fmrx_station* out,
-                    int max_out, int* n_found, float* floor_db) {
+                    int max_out, int* n_found, float* floor_db, int mode_fs = 0) {
     if (!power || !n_found || max_out < 0 || (max_out > 0 && !out)) return fail(FMRX_EINVAL, "bad argument");
     const int N = fft_bins;
     if (!scan_bins_ok(N))
@@ -166,7 +167,8 @@ int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, cons
         const long long f = org + m * ras;
         int tn = 0, tk = 0;
         // every reported offset can be tuned to
-        const int rc = decim == 1 ? fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr)
+        const int rc = mode_fs > 0 ? fmrx_rate_design(mode_fs, rf_fs, (int)f, nullptr, nullptr, nullptr, nullptr, &tn, &tk, nullptr, nullptr, nullptr)
+                       : decim == 1 ? fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr)
                                   : fmrx_wide_design(rf_fs / decim, decim, (int)f, nullptr, nullptr, &tn, &tk, nullptr, nullptr, nullptr);
         if (rc) return rc;
         cands.push_back(Cand{f, 0.0, 0, 0.0});
@@ -222,18 +224,19 @@ int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, cons
 int scan_both(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int decim, const fmrx_scan_config* cfg_in, fmrx_station* out,
               int max_out, int* n_found) {
     const fmrx_scan_config cfg = scan_config_of(cfg_in);
-    const int fs = c->geo.rf_fs * decim;
+    const int mode_fs = c->rate_up ? c->geo.rf_fs : 0;  // a rational rate: decim is 0
+    const int fs = c->rate_up ? c->rate_cap_fs : c->geo.rf_fs * decim;
     int rc = scan_check_size(cfg.fft_bins, n_pairs);
     if (rc) return rc;
     {  // refuse a bad detector configuration before any GPU work
         std::vector<float> flat((size_t)cfg.fft_bins, 1.0f);
         std::vector<fmrx_station> tmp((size_t)std::max(max_out, 0));
         int n = 0;
-        if ((rc = scan_detect_run(flat.data(), cfg.fft_bins, fs, decim, cfg, tmp.data(), max_out, &n, nullptr))) return rc;
+        if ((rc = scan_detect_run(flat.data(), cfg.fft_bins, fs, decim, cfg, tmp.data(), max_out, &n, nullptr, mode_fs))) return rc;
     }
     std::vector<float> power((size_t)cfg.fft_bins);
     if ((rc = fmrx_scan_spectrum(c, iq, n_pairs, cfg.fft_bins, power.data(), nullptr))) return rc;
-    return scan_detect_run(power.data(), cfg.fft_bins, fs, decim, cfg, out, max_out, n_found, nullptr);
+    return scan_detect_run(power.data(), cfg.fft_bins, fs, decim, cfg, out, max_out, n_found, nullptr, mode_fs);
 }
 }  // namespace
 
@@ -247,6 +250,13 @@ int fmrx_scan_detect_wide(const float* power, int fft_bins, int rf_fs, int decim
     int rc = check_capture_decim(decim, false);
     if (rc || (rc = check_wide_rf_fs(rf_fs))) return rc;
     return scan_detect_run(power, fft_bins, rf_fs * decim, decim, scan_config_of(cfg_in), out, max_out, n_found, floor_db);
+}
+
+int fmrx_scan_detect_rate(const float* power, int fft_bins, int rf_fs, int cap_fs, const fmrx_scan_config* cfg_in,
+                          fmrx_station* out, int max_out, int* n_found, float* floor_db) {
+    int rc = fmrx_rate_design(rf_fs, cap_fs, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;  // the rate itself
+    return scan_detect_run(power, fft_bins, cap_fs, 0, scan_config_of(cfg_in), out, max_out, n_found, floor_db, rf_fs);
 }
 
 int fmrx_scan_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,

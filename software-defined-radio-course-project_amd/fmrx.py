@@ -112,6 +112,12 @@ PROTOTYPES = {
     "fmrx_scan_detect_wide": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "fmrx_scan_wide": (C.c_int, [_vp, _vp, _sz, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int, C.POINTER(C.c_int)]),
+    "fmrx_rate_design": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 6 + [_vp, C.POINTER(C.c_int), _vp]),
+    "fmrx_set_capture_rate": (C.c_int, [_vp, C.c_int]),
+    "fmrx_capture_rate": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "fmrx_wide_granule": (C.c_int, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "fmrx_scan_detect_rate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -239,6 +245,18 @@ def wide_design(rf_fs: int, decim: int, offset_hz: int) -> dict:
     return {"coarse_hz": fc.value, "fine_hz": fr.value, "N": n.value, "k": k.value, "table": tab, "h": h}
 
 
+def rate_design(rf_fs: int, cap_fs: int, offset_hz: int) -> dict:
+    """fmrx_rate_design: how an offset against a capture at cap_fs = rf_fs * down / up splits and what the
+    rational down-converter runs with.  A dict: up, down, coarse_hz, fine_hz, N, k, table (N x 2 float32:
+    c[p], s[p]), h (the 16 down + 1 float32 taps; an integer ratio reads up = 1 and wide_design's values)."""
+    v = [C.c_int() for _ in range(7)]  # up, down, coarse, fine, N, k, taps
+    _check(lib().fmrx_rate_design(rf_fs, cap_fs, offset_hz, *[C.byref(x) for x in v[:6]], None, C.byref(v[6]), None))
+    up, down, fc, fr, n, k, t = (x.value for x in v)
+    tab, h = np.zeros((n, 2), np.float32), np.zeros(t, np.float32)
+    _check(lib().fmrx_rate_design(rf_fs, cap_fs, offset_hz, None, None, None, None, None, None, _np_ptr(tab), None, _np_ptr(h)))
+    return {"up": up, "down": down, "coarse_hz": fc, "fine_hz": fr, "N": n, "k": k, "table": tab, "h": h}
+
+
 def iq_pair_bytes(fmt: int) -> int:
     """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
     n = lib().fmrx_iq_pair_bytes(fmt)
@@ -306,21 +324,34 @@ def scan_detect_wide(power: np.ndarray, rf_fs: int, decim: int, max_out: int = M
     return _station_call(lib().fmrx_scan_detect_wide, (_np_ptr(p), p.size, rf_fs, decim), max_out, cfg, True)
 
 
+def scan_detect_rate(power: np.ndarray, rf_fs: int, cap_fs: int, max_out: int = MAX_STATIONS, **cfg):
+    """fmrx_scan_detect_rate: scan_detect on the spectrum of a capture at cap_fs Hz for a mode at rf_fs;
+    every reported offset is one fmrx_rate_design accepts.  Host only."""
+    p = np.ascontiguousarray(power, np.float32).reshape(-1)
+    return _station_call(lib().fmrx_scan_detect_rate, (_np_ptr(p), p.size, rf_fs, cap_fs), max_out, cfg, True)
+
+
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
-                    **cfg):
+                    capture_rate: int | None = None, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
-    capture_decim times the mode's rate (scan_wide, tune_wide, process_wide)."""
+    capture_decim times the mode's rate (scan_wide, tune_wide, process_wide).  capture_rate=HZ: the
+    capture's rate in Hz instead (set_capture_rate; whole granules are decoded); giving both is a
+    ValueError."""
+    if capture_rate is not None and capture_decim != 1:
+        raise ValueError("capture_rate and capture_decim exclude each other")
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
     iq = _iq_flat(iq).reshape(-1)
-    wide = capture_decim != 1
+    wide = capture_decim != 1 or capture_rate is not None
     scan, tune, process = ("scan_wide", "tune_wide", "process_wide") if wide else ("scan", "tune", "process_shared")
 
     def configure(rx):
         if fmt != IQ_U8:
             rx.set_input_format(fmt)
-        if wide:
+        if capture_rate is not None:
+            rx.set_capture_rate(capture_rate)
+        elif wide:
             rx.set_capture_decim(capture_decim)
 
     with Receiver(mode, channels, rf_taps=rf_taps) as rx:
@@ -509,11 +540,11 @@ class Receiver:
         _check(fn(self.h, _np_ptr(off), C.byref(pos), C.byref(on)))
         return [int(v) for v in off], pos.value, bool(on.value)
 
-    def _capture_call(self, fn, iq, per: int) -> np.ndarray:
-        """One capture's whole blocks of `per` elements through fn: S16 PCM, n_streams rows."""
+    def _capture_call(self, fn, iq, per: int, blocks: int = 1) -> np.ndarray:
+        """One capture's whole units of `per` elements (`blocks` blocks each) through fn: S16 PCM, n_streams rows."""
         iq = self._raw(iq).reshape(-1)
-        nb = iq.size // per
-        iq = np.ascontiguousarray(iq[: nb * per])
+        nb = iq.size // per * blocks
+        iq = np.ascontiguousarray(iq[: nb // blocks * per])
         out = np.zeros((self.n_streams, nb * self.geo.pcm_samples), np.int16)
         _check(fn(self.h, _np_ptr(iq), nb, _np_ptr(out)))
         return out if self.n_streams > 1 else out[0]
@@ -553,6 +584,24 @@ class Receiver:
         _check(lib().fmrx_capture_decim(self.h, C.byref(d)))
         return d.value
 
+    def set_capture_rate(self, cap_fs: int) -> None:
+        """fmrx_set_capture_rate: the capture's rate in Hz, rf_fs * down / up (up = 1: set_capture_decim); then a reset."""
+        _check(lib().fmrx_set_capture_rate(self.h, int(cap_fs)))
+
+    @property
+    def capture_rate(self) -> tuple[int, int, int]:
+        """fmrx_capture_rate: (cap_fs, up, down)."""
+        v = [C.c_int() for _ in range(3)]
+        _check(lib().fmrx_capture_rate(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @property
+    def wide_granule(self) -> tuple[int, int]:
+        """fmrx_wide_granule: (narrow blocks, wide pairs) of the unit a wide call is a multiple of."""
+        b, w = _sz(), _sz()
+        _check(lib().fmrx_wide_granule(self.h, C.byref(b), C.byref(w)))
+        return b.value, w.value
+
     def tune_wide(self, offsets, first_pair: int = 0) -> None:
         """fmrx_tune_wide: per-stream offsets in Hz against the capture's rate (an int for one stream);
         first_pair is the absolute wide-pair index of the next call's first pair, a multiple of decim."""
@@ -563,9 +612,10 @@ class Receiver:
         return self._info(lib().fmrx_wide_info)
 
     def process_wide(self, iq: np.ndarray) -> np.ndarray:
-        """One wide capture (whole blocks of capture_decim * iq_pairs pairs) decoded by every stream
-        tuned with tune_wide: S16 PCM, n_streams rows."""
-        return self._capture_call(lib().fmrx_process_wide, iq, 2 * self.geo.iq_pairs * self.capture_decim)
+        """One wide capture (whole granules: blocks of capture_decim * iq_pairs pairs at an integer
+        ratio) decoded by every stream tuned with tune_wide: S16 PCM, n_streams rows."""
+        blocks, pairs = self.wide_granule
+        return self._capture_call(lib().fmrx_process_wide, iq, 2 * pairs, blocks)
 
     def process_wide_device(self, d_iq: int, n_blocks: int, d_pcm: int) -> None:
         _check(lib().fmrx_process_wide_device(self.h, d_iq, n_blocks, d_pcm))
