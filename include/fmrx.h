@@ -21,6 +21,8 @@
  *   fmrx_process_device        <- both bodies fused, device-resident buffers, async
  *   fmrx_rds_block / _device   <- rds_thread body      src/project.cpp:200-271 (RDS front half;
  *                                 never launched by the reference, :380-382)
+ *   fmrx_rds_bits / _device,      no counterpart: the RDS back half (symbol-rate resampler, bits,
+ *   fmrx_rds_parse, _decode ...   block syndromes, group parser), defined below
  *   fmrx_fm_demod_arctan       <- fmDemodArctan        model/fmSupportLib.py:34-63
  *   fmrx_estimate_psd          <- estimatePSD          include/fourier.h:27-31, src/fourier.cpp:35-117
  *   fmrx_psd_device               (model/fmSupportLib.py:83-157)
@@ -378,6 +380,70 @@ int fmrx_rds_block(fmrx_ctx* ctx, const float* demod, size_t n_blocks, float* rd
                    float* channel);
 int fmrx_rds_device(fmrx_ctx* ctx, const float* d_demod, size_t n_blocks, float* d_rds,
                     float* d_nco, float* d_channel);
+
+/* ---- RDS back half: bits, block sync and station name ------------------- */
+/* The reference stops at the mixer output; what follows has no counterpart there.  Per stream:
+ *   1. y = resample(rds, impulseResponseLPF(19 bp_fs, 3000, 101 x 19, 19), 19, bp_fs / 2000) from
+ *      zero state: 38,000 S/s in every mode (16 samples a biphase chip), the reference's own resample
+ *      and the only floating-point stage;
+ *   2. signs s[n] = (y[n] >= 0), 1 in front of the stream;
+ *   3. per window of 2432 samples (76 bits): sign changes counted by n mod 16, z the lowest index of
+ *      the largest bin, phase p = (z + 8) mod 16, chips c[j] = s[2432 w + p + 16 j], j < 152;
+ *   4. e = [the chip in front of the window (1 in front of the stream), c]: v0 equal pairs
+ *      (e[2i], e[2i+1]), v1 equal pairs (e[2i+1], e[2i+2]), i < 76; q = (v1 > v0); the symbols are
+ *      e[2i+1] for q = 0, e[2i] for q = 1;
+ *   5. bit[i] = d[i] ^ d[i-1] over the stream, d[-1] = 0;
+ *   6. code[i], i >= 25: the 26-bit word ending at bit i (first bit most significant), syndrome
+ *      crc10(word >> 10) ^ (word & 0x3FF) with generator 0x5B9; 1..5 where it equals the offset word
+ *      A 0x0FC, B 0x198, C 0x168, C' 0x350, D 0x1B4, else 0 (and 0 for i < 25).
+ * A call takes whole windows: n_blocks a multiple of fmrx_rds_granule's blocks (24, 24, 3, 1 in
+ * modes 0..3; with a capture rate set, the least common multiple with fmrx_wide_granule's), else
+ * FMRX_EINVAL and nothing runs.  rds: the mixer rows as fmrx_rds_device returns them.  Outputs, each
+ * may be NULL, per stream and W = windows of the call: bits and codes 76 W bytes each, win 2 W bytes
+ * (p, q), y 2432 W floats (the 38 kS/s samples; for tests).  The state (resampler history, last sign,
+ * chip and symbols) lives in the context beside the front half's, starts as above, is cleared by
+ * fmrx_reset and is not part of the fmrx_get_state blob.                                          */
+int fmrx_rds_granule(const fmrx_ctx* ctx, size_t* blocks);
+int fmrx_rds_bits(fmrx_ctx* ctx, const float* rds, size_t n_blocks, uint8_t* bits, uint8_t* codes,
+                  uint8_t* win, float* y);
+int fmrx_rds_bits_device(fmrx_ctx* ctx, const float* d_rds, size_t n_blocks, uint8_t* d_bits,
+                         uint8_t* d_codes, uint8_t* d_win, float* d_y);
+
+#define FMRX_RDS_TAIL 103  /* bits the parser carries: a group is judged when its 104th bit arrives */
+/* What the parser has read so far.  Plain data: copy it, compare it; fmrx_rds_info_init gives the
+ * start (characters not yet received are spaces, ps and rt are NUL-terminated).                   */
+typedef struct {
+    uint64_t bits;      /* bits seen                                                               */
+    uint64_t blocks;    /* of them, ends of a word with a valid offset word (code != 0)            */
+    uint64_t groups;    /* groups accepted                                                         */
+    uint16_t pi;        /* block A of the last group                                               */
+    uint8_t pty, tp;    /* block B of the last group                                               */
+    uint8_t rt_ab;      /* RadioText A/B flag of the last 2A/2B group                              */
+    uint8_t tail_n;     /* the carried tail: the last min(bits, FMRX_RDS_TAIL) bits and codes      */
+    char ps[9];
+    char rt[65];
+    uint8_t tail_bits[FMRX_RDS_TAIL];
+    uint8_t tail_codes[FMRX_RDS_TAIL];
+} fmrx_rds_info;
+int fmrx_rds_info_init(fmrx_rds_info* io);
+/* Host only, no context.  n bits and their codes (one byte each, as fmrx_rds_bits writes them) in
+ * stream order, in pieces of any size: the result depends on the bits, not on how they were cut.
+ * A group is accepted where codes A, B, C or C', D end 26 bits apart; no error correction.  Every
+ * group sets pi, pty, tp; 0A/0B set two characters of ps at 2 (B & 3) from block D; 2A sets four of
+ * rt at 4 (B & 15) from blocks C and D, 2B two at 2 (B & 15) from block D, and a change of the A/B
+ * flag (B bit 4) first clears rt.  Bytes outside 0x20..0x7E are stored as spaces.                 */
+int fmrx_rds_parse(fmrx_rds_info* io, const uint8_t* bits, const uint8_t* codes, size_t n);
+/* Front half, bits and parse of n_blocks demod blocks (as fmrx_rf_block returns them; whole RDS
+ * granules) into the context's per-stream info, which fmrx_rds_info_get copies out.              */
+int fmrx_rds_decode(fmrx_ctx* ctx, const float* demod, size_t n_blocks);
+int fmrx_rds_decode_device(fmrx_ctx* ctx, const float* d_demod, size_t n_blocks);
+int fmrx_rds_info_get(const fmrx_ctx* ctx, int stream, fmrx_rds_info* out);
+/* on != 0: the calls whose front end writes demod rows (tuned fmrx_process / _device / _device_ex,
+ * fmrx_process_shared / _device, fmrx_process_wide / _device) also run fmrx_rds_decode_device on
+ * those rows, on the same stream after the front end, and return after the parse (a host
+ * synchronisation).  Such a call must be whole RDS granules (FMRX_EINVAL and nothing runs
+ * otherwise).  The PCM is the same either way.  Off (the default): no call does anything more.    */
+int fmrx_set_rds(fmrx_ctx* ctx, int on);
 
 /* ---- arctan demodulator and PSD estimate (floating-point diagnostics) ------ */
 /* fmDemodArctan: out[k] = atan2(Q,I) phase difference to the previous sample, wrapped into

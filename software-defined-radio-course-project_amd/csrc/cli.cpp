@@ -1,6 +1,6 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
 // [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]
-// [--capture-rate HZ]`:
+// [--capture-rate HZ] [--rds]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -30,6 +30,10 @@
 //     an integer one as --capture-decim): stdin in whole granules (fmrx_wide_granule), --offset-hz and
 //     --scan against that rate.  With --capture-decim: message, exit 1; a rate the library refuses:
 //     message, exit 1.
+//   * --rds (an fmrx extension) also decodes the station's RDS (fmrx_set_rds): the batch is rounded up to
+//     whole RDS granules (fmrx_rds_granule), the tuned front end runs (offset 0 without --offset-hz), and
+//     at end of input one line goes to stderr, `rds pi=%04X pty=%d ps="........" groups=%d`.  stdout is
+//     unchanged: blocks past the last whole granule are decoded without RDS.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -99,6 +103,7 @@ void usage(const char* argv0) {
                  "Usage: %s\nor \nUsage %s <mode> <channels>\n"
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
+                 "                [--rds]  decode the station's RDS too; at end of input print its PI, PTY and name to stderr\n"
                  "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
                  "                [--capture-decim D]  stdin runs at D (2..10) times the mode's rate; --offset-hz and\n"
                  "                                     --scan then refer to that rate (default 1)\n"
@@ -154,7 +159,7 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
 
 int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false, tuned = false, scan = false;
+    bool mono_product = false, tuned = false, scan = false, rds = false;
     long offset_hz = 0;
     int iq_format = FMRX_IQ_U8, capture_decim = 1;
     long capture_rate = 0;
@@ -168,6 +173,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rf-taps") && i + 1 < argc) rf_taps = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
         else if (!std::strcmp(argv[i], "--scan")) scan = true;
+        else if (!std::strcmp(argv[i], "--rds")) rds = true;
         else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
         else if (!std::strcmp(argv[i], "--iq-format") && i + 1 < argc) {
             const char* f = argv[++i];
@@ -271,7 +277,17 @@ int main(int argc, char** argv) {
         fmrx_destroy(ctx);
         return rc;
     }
-    if (tuned || wide) {  // out of range (or no 32-bit value) -> message, exit 1
+    // --rds: whole RDS granules a batch (rounded up), decoded by the tuned front end
+    size_t rds_unit = unit_blocks;
+    if (rds) {
+        if (fmrx_rds_granule(ctx, &rds_unit) != FMRX_OK || fmrx_set_rds(ctx, 1) != FMRX_OK) {
+            std::fprintf(stderr, "fmrx: --rds: %s\n", fmrx_last_error());
+            fmrx_destroy(ctx);
+            return 1;
+        }
+        batch = (int)(((size_t)batch + rds_unit - 1) / rds_unit * rds_unit);
+    }
+    if (tuned || wide || rds) {  // out of range (or no 32-bit value) -> message, exit 1
         const int32_t f = (int32_t)offset_hz;
         if ((long)f != offset_hz || (wide ? fmrx_tune_wide : fmrx_tune)(ctx, &f, 0) != FMRX_OK) {
             std::fprintf(stderr, "fmrx: --offset-hz %ld: %s\n", offset_hz,
@@ -331,14 +347,20 @@ int main(int argc, char** argv) {
         }
     });
 
+    auto process = wide ? fmrx_process_wide_device : fmrx_process_device;
     for (;;) {
         const int i = filled_q.pop();
         Slot& s = slots[i];
         if (s.blocks > 0) {
+            // with --rds: the whole granules, then (end of input only) the blocks left over without RDS
+            const size_t head = s.blocks / rds_unit * rds_unit;
             CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks / unit_blocks * block_bytes, hipMemcpyHostToDevice, up));
             CLI_HIP(hipEventRecord(s.uploaded, up));
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
-            if ((wide ? fmrx_process_wide_device : fmrx_process_device)(ctx, s.d_in, s.blocks, s.d_out) != FMRX_OK) {
+            if ((head > 0 && process(ctx, s.d_in, head, s.d_out) != FMRX_OK) ||
+                (head < s.blocks && (fmrx_set_rds(ctx, 0) != FMRX_OK ||
+                                     process(ctx, s.d_in + head / unit_blocks * block_bytes, s.blocks - head,
+                                             s.d_out + head * geo.pcm_samples) != FMRX_OK))) {
                 std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
                 std::fflush(stdout);
                 std::_Exit(1);
@@ -366,6 +388,12 @@ int main(int argc, char** argv) {
     }
     (void)hipStreamDestroy(up);
     (void)hipStreamDestroy(down);
+    if (rds) {
+        fmrx_rds_info info;
+        if (fmrx_rds_info_get(ctx, 0, &info) == FMRX_OK)
+            std::fprintf(stderr, "rds pi=%04X pty=%d ps=\"%s\" groups=%d\n", (unsigned)info.pi, (int)info.pty, info.ps,
+                         (int)info.groups);
+    }
     fmrx_destroy(ctx);
     std::fprintf(stderr, "End of input stream reached!\n");
     return 0;

@@ -87,6 +87,8 @@ int reset_state(fmrx_ctx* c) {
     if (c->d_rds_chan.p) HIPCHK(hipMemsetAsync(c->d_rds_chan.p, 0, sizeof(float) * c->d_rds_chan.n, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_rds_pll.p, pll.data(), sizeof(float) * pll.size(), hipMemcpyHostToDevice,
                           c->stream));
+    int rc = reset_rds_bits(c);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -303,8 +305,15 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
         (rc = c->d_pll.ensure(8 * (size_t)ns)) || (rc = c->d_mix_tail.ensure((size_t)kMixTail * ns)) ||
         (rc = c->d_mono_state.ensure(8 * (size_t)ns)) || (rc = c->d_sintab.ensure(kSinSize)) ||
         (rc = c->d_rds_taps.ensure(2 * kRdsTaps)) || (rc = c->d_rds_dhist.ensure((size_t)kRdsDemodHist * ns)) ||
-        (rc = c->d_rds_pll.ensure(8 * (size_t)ns)))
+        (rc = c->d_rds_pll.ensure(8 * (size_t)ns)) || (rc = c->d_rdsb_taps.ensure(kRdsbTaps)) ||
+        (rc = c->d_rdsb_hist.ensure((size_t)kRdsbHist * ns)) || (rc = c->d_rdsb_state.ensure((size_t)kRdsbStateBytes * ns)))
         return cleanup(rc);
+    // the symbol-rate resampler's prototype: 101 taps a phase at 19 bp_fs, gain 19
+    std::vector<float> rdsb_taps(kRdsbTaps);
+    design_lpf(rdsb_taps.data(), (float)g.bp_fs * (float)kRdsbUp, 3000.0f, kRdsbTaps, kRdsbUp);
+    if (hipMemcpy(c->d_rdsb_taps.p, rdsb_taps.data(), sizeof(float) * rdsb_taps.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return cleanup(fail(FMRX_EHIP, "RDS tap upload failed"));
+    c->rds_info.resize((size_t)ns);
     // RDS taps, project.cpp:211 and :217 (bp_taps = 51 at bp_fs)
     std::vector<float> rds_taps(2 * kRdsTaps);
     design_bpf(rds_taps.data(), (float)g.bp_fs, 54000.0f, 60000.0f, kRdsTaps);
@@ -345,6 +354,8 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_pll_side.release(); c->d_pll_side2.release();
     c->d_rds_taps.release(); c->d_rds_dhist.release(); c->d_rds_chan.release(); c->d_rds_car.release();
     c->d_rds_pll.release();
+    c->d_rdsb_taps.release(); c->d_rdsb_hist.release(); c->d_rdsb_state.release(); c->d_rdsb_work.release();
+    c->d_rdsb_mix.release(); c->d_rdsb_out.release();
     c->d_tune_tab.release(); c->d_tune_streams.release();
     c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
     c->d_wide_hist.release(); c->d_wide_taps.release(); c->d_wide_tab.release(); c->d_wide_streams.release();

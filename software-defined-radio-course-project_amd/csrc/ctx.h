@@ -1,6 +1,6 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -129,6 +129,17 @@ struct Ctx {
     size_t rds_chan_stride = 0;
     DevBuf<float> d_rds_car;      // n_streams x cap
     DevBuf<float> d_rds_pll;      // n_streams x 8
+    // RDS back half state (rds_bits.hip; not part of the checkpoint blob either)
+    DevBuf<float> d_rdsb_taps;    // kRdsbTaps: impulseResponseLPF(19 bp_fs, 3000, 1919, 19)
+    DevBuf<float> d_rdsb_hist;    // n_streams x kRdsbHist mixer samples in front of the next call
+    DevBuf<uint8_t> d_rdsb_state; // n_streams x kRdsbStateBytes
+    DevBuf<uint8_t> d_rdsb_work;  // a call's signs, phases, last chips and symbols
+    DevBuf<float> d_rdsb_mix;     // fmrx_rds_decode*: the front half's mixer rows
+    DevBuf<uint8_t> d_rdsb_out;   // fmrx_rds_decode*: bits, then codes
+    std::vector<uint8_t> rdsb_host;       // their host copy, read by the parser
+    size_t rdsb_pending = 0;              // symbols a stream of a decode enqueued and not yet parsed
+    std::vector<fmrx_rds_info> rds_info;  // n_streams
+    bool rds_on = false;                  // fmrx_set_rds
     // staging for the host-buffer entry points
     DevBuf<uint8_t> d_in;
     DevBuf<int16_t> d_out;
@@ -305,6 +316,16 @@ int run_stereo_pipelined(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int1
 int run_rds(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_if, float* d_out, float* d_nco,
             float* d_channel);
 int ensure_demod(fmrx_ctx* c, size_t n_if);
+
+// ---- rds_api.cpp
+// blocks of an RDS granule (with a capture rate set: the least common multiple with the wide granule's)
+size_t rds_granule_blocks(const fmrx_ctx* c);
+int check_rds_blocks(const fmrx_ctx* c, size_t n_blocks);
+int reset_rds_bits(fmrx_ctx* c);  // the back half's start state, enqueued on the context stream
+// front half, bits and codes of the rows at d_demod (whole granules), and their copy to the host, enqueued;
+// rds_decode_finish waits for the stream and parses them into rds_info
+int rds_decode_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
+int rds_decode_finish(fmrx_ctx* c);
 
 // ---- front.cpp
 int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,

@@ -274,6 +274,37 @@ struct RdsLaunch {
 };
 int launch_rds(const RdsLaunch& L, int n_streams, hipStream_t s);
 
+// ---- RDS back half (rds_bits.hip) ------------------------------------------
+constexpr int kRdsbUp = 19;          // the symbol-rate resampler: 19 / (bp_fs / 2000), 38 kS/s out
+constexpr int kRdsbPhaseTaps = 101;
+constexpr int kRdsbTaps = kRdsbPhaseTaps * kRdsbUp;
+constexpr int kRdsbWin = 2432;       // outputs a window: 152 chips of 16, 76 bits of 32
+constexpr int kRdsbChips = 152;
+constexpr int kRdsbSyms = 76;
+constexpr int kRdsbHist = 128;       // mixer samples carried in front of a call (>= 100)
+constexpr int kRdsbTail = 26;        // symbols carried: 25 bits in front of a call's first
+// a stream's carried bytes: [0] last sign, [1] last chip, [2] bits seen so far (saturates at 25),
+// [4 .. 4 + kRdsbTail) the last symbols, oldest first
+constexpr int kRdsbStateBytes = 32;
+struct RdsBitsLaunch {
+    const float* mix;       // n_streams x n_if (stride mix_stride): the 57 kHz mixer output
+    size_t mix_stride;
+    float* hist;            // n_streams x kRdsbHist: mixer samples before this call
+    uint8_t* state;         // n_streams x kRdsbStateBytes
+    const float* taps;      // kRdsbTaps
+    uint8_t* sign;          // scratch, n_streams x n_out
+    uint8_t* winp;          // scratch, n_streams x n_win: the windows' phases
+    uint8_t* lastchip;      // scratch, n_streams x n_win: the windows' last chips
+    uint8_t* sym;           // scratch, n_streams x n_sym: the differential symbols
+    uint8_t* bits;          // optional outputs: n_streams x n_sym, n_streams x n_sym,
+    uint8_t* codes;         //   n_streams x 2 n_win (p, q), n_streams x n_out
+    uint8_t* win;
+    float* y;
+    int down;               // bp_fs / 2000
+    int n_if, n_out, n_win, n_sym;  // n_out = 2432 n_win = n_if 19 / down, n_sym = 76 n_win
+};
+int launch_rds_bits(const RdsBitsLaunch& L, int n_streams, hipStream_t s);
+
 // ---- spectrum tooling and the arctan demodulator ------------------
 constexpr int kPsdMaxBins = 8192;  // N complex doubles in LDS per segment
 int launch_demod_arctan(float* out, double* prev, const float* i, const float* q, int n, hipStream_t s);

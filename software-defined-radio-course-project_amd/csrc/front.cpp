@@ -63,17 +63,33 @@ int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n
                         demod_stride, demod_hist, pre_tail);
 }
 
+// The audio stage of a call whose front end filled the context's demod rows (mono: the polyphase
+// stage; stereo: the non-pipelined engine).  With fmrx_set_rds on, the RDS decode of the same rows
+// goes on the stream in front of it (the audio stage moves the rows' tail afterwards) and is parsed
+// once the call's work is done; the audio stage reads and writes nothing the decode touches.
+static int run_audio_stage(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
+    const size_t n_if = n_blocks * c->geo.if_samples;
+    int rc;
+    if (c->rds_on && (rc = rds_decode_enqueue(c, c->d_demod.p + kDemodHist, c->demod_stride, n_blocks))) return rc;
+    if (c->cfg.channels != FMRX_MONO)
+        rc = run_stereo_audio(c, n_blocks, d_pcm, d_mono);
+    else
+        rc = run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
+    if (rc) return rc;
+    return c->rds_on ? rds_decode_finish(c) : 0;
+}
+
 // A tuned call: the front end for the whole call into the context's demod rows, then the audio
 // stage fmrx_audio_block runs (mono: the polyphase stage; stereo: the non-pipelined engine).
 int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
     const int ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;
-    int rc = ensure_demod(c, n_if);
-    if (rc) return rc;
+    int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
+    if (rc || (rc = ensure_demod(c, n_if))) return rc;
     if (c->cfg.channels != FMRX_MONO) {
         if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, false)))
             return rc;
-        return run_stereo_audio(c, n_blocks, d_pcm, d_mono);
+        return run_audio_stage(c, n_blocks, d_pcm, d_mono);
     }
     // after fmrx_seek the audio history is rebuilt from the halo, as the fused kernel's pre-roll
     // does: the 50 demod samples in front of the call (all a resampler output reads back)
@@ -87,7 +103,7 @@ int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_block
             return fail(FMRX_EHIP, "audio history copy failed");
         c->audio_hist_stale = false;
     }
-    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
+    return run_audio_stage(c, n_blocks, d_pcm, d_mono);
 }
 
 }  // namespace fmrx
@@ -161,8 +177,8 @@ static int run_rate(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* 
     const int ns = c->cfg.n_streams, up = c->rate_up, down = c->rate_down;
     const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples, gran = c->rate_blocks;
     const size_t hb = wide_hist_pairs(c) * c->pair_bytes;
-    int rc = ensure_demod(c, n_if);
-    if (rc) return rc;
+    int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
+    if (rc || (rc = ensure_demod(c, n_if))) return rc;
     const size_t fit = kWidePieceBytes / ((size_t)ns * ip * 8);
     const size_t piece = std::min(n_blocks, std::max(gran, fit / gran * gran));
     if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
@@ -202,8 +218,7 @@ static int run_rate(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* 
     // the next call's history: the capture's last raw pairs (a granule holds more than that)
     HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + wide_pairs_of(c, n_blocks) * c->pair_bytes - hb, hb,
                           hipMemcpyDeviceToDevice, c->stream));
-    if (c->cfg.channels != FMRX_MONO) return run_stereo_audio(c, n_blocks, d_pcm, nullptr);
-    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, nullptr);
+    return run_audio_stage(c, n_blocks, d_pcm, nullptr);
 }
 
 // A wide call (fmrx_process_wide_device; arguments checked, device set): per piece of whole blocks
@@ -215,8 +230,8 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) 
     const int ns = c->cfg.n_streams, D = c->wide_decim;
     const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples;
     const size_t wide_block = (size_t)D * iq_block_bytes(c), hb = 16 * (size_t)D * c->pair_bytes;
-    int rc = ensure_demod(c, n_if);
-    if (rc) return rc;
+    int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
+    if (rc || (rc = ensure_demod(c, n_if))) return rc;
     const size_t piece = std::min(n_blocks, std::max<size_t>(1, kWidePieceBytes / ((size_t)ns * ip * 8)));
     if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -253,8 +268,7 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) 
     }
     // the next call's history: the capture's last 16 decim pairs (a block holds more than that)
     HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + n_blocks * wide_block - hb, hb, hipMemcpyDeviceToDevice, c->stream));
-    if (c->cfg.channels != FMRX_MONO) return run_stereo_audio(c, n_blocks, d_pcm, nullptr);
-    return run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, nullptr);
+    return run_audio_stage(c, n_blocks, d_pcm, nullptr);
 }
 
 }  // namespace fmrx

@@ -61,6 +61,34 @@ class Station(C.Structure):
         return f"Station(offset_hz={self.offset_hz}, power_db={self.power_db:.2f}, snr_db={self.snr_db:.2f})"
 
 
+RDS_TAIL = 103  # include/fmrx.h FMRX_RDS_TAIL
+RDS_WINDOW, RDS_BITS_PER_WINDOW = 2432, 76  # 38 kS/s samples and bits a window of the RDS back half
+
+
+class RdsInfo(C.Structure):
+    """Mirror of fmrx_rds_info: what the RDS group parser has read so far."""
+    _fields_ = [("bits", C.c_uint64), ("blocks", C.c_uint64), ("groups", C.c_uint64), ("pi", C.c_uint16),
+                ("pty", C.c_uint8), ("tp", C.c_uint8), ("rt_ab", C.c_uint8), ("tail_n", C.c_uint8),
+                ("ps_raw", C.c_char * 9), ("rt_raw", C.c_char * 65), ("tail_bits", C.c_uint8 * RDS_TAIL),
+                ("tail_codes", C.c_uint8 * RDS_TAIL)]
+
+    def __init__(self):
+        super().__init__()
+        _check(lib().fmrx_rds_info_init(C.byref(self)))
+
+    @property
+    def ps(self) -> str:
+        return self.ps_raw.decode("ascii")
+
+    @property
+    def rt(self) -> str:
+        return self.rt_raw.decode("ascii")
+
+    def as_dict(self) -> dict:
+        return {"pi": self.pi, "pty": self.pty, "tp": self.tp, "ps": self.ps, "rt": self.rt, "bits": self.bits,
+                "blocks": self.blocks, "groups": self.groups}
+
+
 _vp, _sz, _fp, _i16p, _u8p = C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every function declared in include/fmrx.h
@@ -82,6 +110,15 @@ PROTOTYPES = {
     "fmrx_audio_block": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_rds_block": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "fmrx_rds_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmrx_rds_granule": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "fmrx_rds_bits": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmrx_rds_bits_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmrx_rds_info_init": (C.c_int, [C.POINTER(RdsInfo)]),
+    "fmrx_rds_parse": (C.c_int, [C.POINTER(RdsInfo), _vp, _vp, _sz]),
+    "fmrx_rds_decode": (C.c_int, [_vp, _vp, _sz]),
+    "fmrx_rds_decode_device": (C.c_int, [_vp, _vp, _sz]),
+    "fmrx_rds_info_get": (C.c_int, [_vp, C.c_int, C.POINTER(RdsInfo)]),
+    "fmrx_set_rds": (C.c_int, [_vp, C.c_int]),
     "fmrx_fm_demod_arctan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "fmrx_estimate_psd": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_float, _vp, _vp]),
     "fmrx_psd_device": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_float, _vp]),
@@ -331,14 +368,27 @@ def scan_detect_rate(power: np.ndarray, rf_fs: int, cap_fs: int, max_out: int = 
     return _station_call(lib().fmrx_scan_detect_rate, (_np_ptr(p), p.size, rf_fs, cap_fs), max_out, cfg, True)
 
 
+def rds_parse(bits, codes, info: RdsInfo | None = None) -> RdsInfo:
+    """fmrx_rds_parse (host only): feed bits and their codes, in pieces of any size, into info (a new
+    RdsInfo when None) and return it."""
+    info = RdsInfo() if info is None else info
+    b = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+    c = np.ascontiguousarray(codes, np.uint8).reshape(-1)
+    if b.size != c.size:
+        raise ValueError("bits and codes differ in length")
+    _check(lib().fmrx_rds_parse(C.byref(info), _np_ptr(b), _np_ptr(c), b.size))
+    return info
+
+
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
-                    capture_rate: int | None = None, **cfg):
+                    capture_rate: int | None = None, rds: bool = False, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
     capture_decim times the mode's rate (scan_wide, tune_wide, process_wide).  capture_rate=HZ: the
     capture's rate in Hz instead (set_capture_rate; whole granules are decoded); giving both is a
-    ValueError."""
+    ValueError.  rds=True: the capture is trimmed to whole RDS granules and the result is
+    (stations, pcm, infos), infos one dict a station (pi, pty, tp, ps, rt and the parser's counters)."""
     if capture_rate is not None and capture_decim != 1:
         raise ValueError("capture_rate and capture_decim exclude each other")
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
@@ -358,12 +408,19 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
         configure(rx)
         stations = getattr(rx, scan)(iq, **cfg)
     if not stations:
-        return [], np.zeros((0, 0), np.int16)
+        return ([], np.zeros((0, 0), np.int16), []) if rds else ([], np.zeros((0, 0), np.int16))
     with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
         configure(rx)
         getattr(rx, tune)([s.offset_hz for s in stations])
+        if rds:
+            rx.set_rds(True)
+            blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
+            per = rx.rds_granule // blocks * pairs * 2  # elements of the capture an RDS granule takes
+            iq = iq[: iq.size // per * per]
         pcm = getattr(rx, process)(iq)
-    return stations, pcm.reshape(len(stations), -1)
+        infos = [rx.rds_info(k).as_dict() for k in range(len(stations))] if rds else None
+    pcm = pcm.reshape(len(stations), -1)
+    return (stations, pcm, infos) if rds else (stations, pcm)
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:
@@ -504,6 +561,57 @@ class Receiver:
     def rds_device(self, d_demod: int, n_blocks: int, d_rds: int, d_nco: int | None = None,
                    d_channel: int | None = None) -> None:
         _check(lib().fmrx_rds_device(self.h, d_demod, n_blocks, d_rds, d_nco, d_channel))
+
+    # ---- RDS back half
+    @property
+    def rds_granule(self) -> int:
+        """fmrx_rds_granule: the blocks an RDS call takes whole multiples of."""
+        b = _sz()
+        _check(lib().fmrx_rds_granule(self.h, C.byref(b)))
+        return b.value
+
+    def rds_bits(self, rds: np.ndarray, want_y: bool = False) -> dict:
+        """fmrx_rds_bits: the mixer rows (rds_block's "rds"; whole RDS granules) -> a dict of bits and codes
+        (76 a window, one byte each), win (windows x (p, q)) and, with want_y, the 38 kS/s samples y."""
+        d = np.ascontiguousarray(rds, np.float32).reshape(self.n_streams, -1)
+        nb = d.shape[1] // self.geo.if_samples
+        if nb * self.geo.if_samples != d.shape[1]:
+            raise FmrxError(FMRX_EINVAL, "rds_bits takes whole blocks")
+        n_out = d.shape[1] * 19 // (self.geo.bp_fs // 2000)
+        nw = n_out // RDS_WINDOW
+        out = {"bits": np.zeros((self.n_streams, nw * RDS_BITS_PER_WINDOW), np.uint8),
+               "codes": np.zeros((self.n_streams, nw * RDS_BITS_PER_WINDOW), np.uint8),
+               "win": np.zeros((self.n_streams, nw, 2), np.uint8)}
+        if want_y:
+            out["y"] = np.zeros((self.n_streams, n_out), np.float32)
+        _check(lib().fmrx_rds_bits(self.h, _np_ptr(d), nb, _np_ptr(out["bits"]), _np_ptr(out["codes"]),
+                                   _np_ptr(out["win"]), _np_ptr(out["y"]) if want_y else None))
+        return {k: (v if self.n_streams > 1 else v[0]) for k, v in out.items()}
+
+    def rds_bits_device(self, d_rds: int, n_blocks: int, d_bits: int | None, d_codes: int | None,
+                        d_win: int | None = None, d_y: int | None = None) -> None:
+        _check(lib().fmrx_rds_bits_device(self.h, d_rds, n_blocks, d_bits, d_codes, d_win, d_y))
+
+    def rds_decode(self, demod: np.ndarray) -> None:
+        """fmrx_rds_decode: demod blocks (whole RDS granules) through the front half, the bits and the
+        parser into the streams' info (rds_info)."""
+        d = np.ascontiguousarray(demod, np.float32).reshape(self.n_streams, -1)
+        nb = d.shape[1] // self.geo.if_samples
+        if nb * self.geo.if_samples != d.shape[1]:
+            raise FmrxError(FMRX_EINVAL, "rds_decode takes whole blocks")
+        _check(lib().fmrx_rds_decode(self.h, _np_ptr(d), nb))
+
+    def rds_decode_device(self, d_demod: int, n_blocks: int) -> None:
+        _check(lib().fmrx_rds_decode_device(self.h, d_demod, n_blocks))
+
+    def set_rds(self, on: bool) -> None:
+        """fmrx_set_rds: the tuned, shared and wide process calls also decode RDS (whole RDS granules)."""
+        _check(lib().fmrx_set_rds(self.h, int(bool(on))))
+
+    def rds_info(self, stream: int = 0) -> RdsInfo:
+        info = RdsInfo()
+        _check(lib().fmrx_rds_info_get(self.h, int(stream), C.byref(info)))
+        return info
 
     def estimate_psd(self, samples: np.ndarray, freq_bins: int, fs: float):
         """estimatePSD (fourier.cpp:35-117) on the GPU: (freq, psd_db)."""
