@@ -66,6 +66,9 @@ namespace {
 // stereo calls of up to this many blocks a stream take launch_stereo_audio_small (modes 0/1)
 constexpr int kSmallAudioBlocks = 4;
 
+// project.cpp:166: PLL(carrier, 19000, if_fs, 2, 0, 0.01, ...), the stereo pilot's loop
+PllLoop pilot_loop(const fmrx_ctx* c) { return PllLoop{19000.0f, (float)c->geo.if_fs, 2.0f, 0.0f, 0.01f}; }
+
 // Segments per stream for the fused kernel: enough workgroups to fill the chip
 // (2 resident per CU on 256 CUs) without making segments so short that the pre-roll chunk
 // dominates.
@@ -224,13 +227,13 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
     const int t_bp = c->stage_timer.begin(c->stream);
     if (launch_bpf_pair(S, ns, c->stream, c->knobs.bpf_tile != 0)) return fail(FMRX_EHIP, "band-pass launch failed");
     c->stage_timer.end(t_bp, kStBpf, 0.0, c->stream);
-    // project.cpp:166: PLL(carrier, 19000, if_fs, 2, 0, 0.01, ...)
+    const PllLoop pilot = pilot_loop(c);
     if ((rc = c->d_pll_side.ensure(pll_side_doubles((int)n_if, ns)))) return rc;
     // a call of a few blocks (the per-block seam): the NCO, audio, state carry and demod history in
     // one launch after the PLL (launch_stereo_audio_small); longer calls: the parallel kernels
     const bool small = c->geo.audio_up == 1 && n_blocks <= (size_t)kSmallAudioBlocks;
-    if (launch_pll(c->d_carrier.p, (int)n_if, ns, n_if, 19000.0f, (float)c->geo.if_fs, 2.0f, 0.0f,
-                   0.01f, c->d_pll.p, c->d_pll_side.p, c->stream, c->hint(c->pll_trig), c->pll_stats, !small)) {
+    if (launch_pll(c->d_carrier.p, (int)n_if, ns, n_if, pilot, c->d_pll.p, c->d_pll_side.p, c->stream,
+                   c->hint(c->pll_trig), c->pll_stats, !small)) {
         c->pll_trig.known = false;
         return fail(FMRX_EHIP, "PLL launch failed");
     }
@@ -254,8 +257,8 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
     A.audio_c = c->d_audio.p;
     const int t_au = c->stage_timer.begin(c->stream);
     if (small) {
-        if (launch_stereo_audio_small(A, ns, pll_trig_args(c->d_pll_side.p, (int)n_if, ns), n_if, 2.0f, 0.0f,
-                                      c->d_pll.p, kDemodHist, c->stream))
+        if (launch_stereo_audio_small(A, ns, pll_scratch(c->d_pll_side.p, (int)n_if, ns).args, n_if, pilot.nco_scale,
+                                      pilot.phase_adjust, c->d_pll.p, kDemodHist, c->stream))
             return fail(FMRX_EHIP, "stereo audio launch failed");
         c->stage_timer.end(t_au, kStAudio, 0.0, c->stream);
         return 0;
@@ -407,12 +410,12 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
     // context stream goes on to the next chunk's runners; chunk k's trigArgs stay in side buffer
     // k & 1 until that NCO has read them (the context stream waits for it before chunk k + 2)
     auto side_of = [&](int k) { return (k & 1) ? c->d_pll_side2.p : c->d_pll_side.p; };
+    const PllLoop pilot = pilot_loop(c);
     auto pll = [&](size_t off, size_t m, double* side, bool nco) -> int {
         if (m == 0) return 0;
         PllHint h = c->hint(c->pll_trig);
         h.demote_once = true;  // one demoted-kernel launch a chunk (beside the stage kernels)
-        if (launch_pll(c->d_carrier.p + off, (int)m, ns, n_if, 19000.0f, (float)c->geo.if_fs, 2.0f, 0.0f, 0.01f,
-                       c->d_pll.p, side, c->stream, h, c->pll_stats, nco)) {
+        if (launch_pll(c->d_carrier.p + off, (int)m, ns, n_if, pilot, c->d_pll.p, side, c->stream, h, c->pll_stats, nco)) {
             c->pll_trig.known = false;
             return fail(FMRX_EHIP, "PLL launch failed");
         }
@@ -465,8 +468,7 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
         // s_audio: the NCO and the audio stage of chunk k (and the state carry after the last)
         HIPCHK(hipStreamWaitEvent(c->s_audio, ev_pll(k), 0));
         const int t_nco = c->stage_timer.begin(c->s_audio);
-        if (launch_pll_nco(c->d_carrier.p + off + m0, (int)(m - m0), ns, n_if, 2.0f, 0.0f, c->d_pll.p, side_of(k),
-                           c->s_audio))
+        if (launch_pll_nco(c->d_carrier.p + off + m0, (int)(m - m0), ns, n_if, pilot, c->d_pll.p, side_of(k), c->s_audio))
             return fail(FMRX_EHIP, "NCO launch failed");
         c->stage_timer.end(t_nco, kStNco, 0.0, c->s_audio);
         HIPCHK(hipEventRecord(ev_nco(k), c->s_audio));

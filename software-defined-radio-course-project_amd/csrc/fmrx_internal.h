@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mono_launch.h"
+#include "pll_plan.h"
 #include "synth.h"
 
 namespace fmrx {
@@ -47,26 +48,21 @@ struct StereoLaunch {
 };
 // tiled = false: the per-output kernel (A/B measurements; same bits)
 int launch_bpf_pair(const StereoLaunch& L, int n_streams, hipStream_t s, bool tiled = true);
-// PLL over n samples of n_streams streams (state st, 8 floats per stream), then the NCO
-// (filter.cpp:136-174).  side: device scratch of pll_side_doubles(n, n_streams) doubles.
-// spec_stats (diagnostic, may be null): the speculative path adds the runner batches that did
-// not verify to spec_stats[0] and the batches checked to spec_stats[1].
-constexpr size_t kPllSeg = (size_t)1 << 18;  // at most this many samples per stream per PLL segment
-size_t pll_side_doubles(int n, int n_streams);
-// What the host knows when it launches a PLL (ctx.h TrigTrack tracks it per context): the device's SIMD
-// count (streams per wave) and, when `known`, bounds on every stream's trigOffset at the call's
-// start (integer-valued, <= 2^24: the reference's float increments from a reset), so that
-// launch_pll enqueues only the runners some segment can use.  Unknown (the fmrx_pll primitive's
-// state lives in caller memory): every runner is launched and each takes its own waves.
-// Per-stage device time of the stereo engine (fmrx_debug_stage_timing; diagnostic): HIP event
-// pairs recorded on the stream each stage is launched on, read after the call.  Runner records
-// carry the serial steps they ran when they were the only runner of their segment (the host's
-// trigOffset bounds put every stream in that runner's regime), so ns per step per regime is
-// measured, not modelled.
-enum StageKind {
-    kStFront, kStBpf, kStPrep, kStLane, kStPred, kStSat, kStPipe20, kStPipe21, kStPipe22, kStCheck, kStTail,
-    kStNco, kStAudio, kStIdx17, kStIdx18, kStIdx19, kStCnt17, kStCnt18, kStCnt19, kStCnt20, kStCnt21, kStStick, kStKinds
+// ---- the PLL (pll.hip; its launch plan pll_plan.h, its forms pll_forms.h) ---------------------
+// The scratch of a launch_pll call: `side` (pll_side_doubles(n, n_streams) doubles of device
+// memory) and where its parts lie in it (pll_plan.h PllLayout, the one definition of the layout):
+// one segment's side data at its start, the call's trigArgs (n floats a stream), the speculative
+// runners' batch records (rb a stream) and fail[] (an int a stream).
+struct PllScratch {
+    double* side;
+    float* args;
+    float2* rec;
+    int* fail;
+    size_t seg, rb;
 };
+PllScratch pll_scratch(double* side, int n, int n_streams);
+size_t pll_side_doubles(int n, int n_streams);
+
 struct StageTimer {
     bool on = false;
     struct Rec {
@@ -102,29 +98,11 @@ struct StageTimer {
     }
 };
 
-// The count runner's forms by default: [2^19, 2^20) and [2^20, 2^21) (bits 2, 3).  Same-box A/B,
-// two alternating rounds (profiles/r05/ab_cnt12/): one 10 s stream 0.1093 -> 0.0923 s, configs[4]
-// 0.430 -> 0.418 s, configs[2] 1.240 -> 1.222 s.  [2^17, 2^19) stay on the index runner (the
-// count form's 31-candidate evaluators bound it: 68-73 ns a step against 55), [2^21, 2^22) on the
-// three-wave runner (profiles/r05/rprof/).
-constexpr int kPllCntDefault = 12;
-
-// Per-context switches of the PLL launch (ctx.h fmrx_ctx::knobs; fmrx_debug_set_knob).  The
-// tuning ones pick which runners run (same bits either way) and are read from the environment
-// once, when the context is created; the test hooks make the runners do extra (redone) work --
-// the output stays the exact path's -- and are set only through fmrx_debug_set_knob.
-struct PllKnobs {
-    int spec = 1;        // 0: the plain certified launch (FMRX_PLL_SPEC)
-    int sat = 1;         // 0: no saturated-segment runner (FMRX_PLL_SAT)
-    int pred = 1;        // 0: no predicted runners; 2: the two-wave one even where waves share SIMDs
-    int pipe = 1;        // 0: no three-wave runner (FMRX_PLL_PIPE)
-    int idx = 2;         // index runner from 2^17 (2), from 2^18 (1), off (0) (FMRX_PLL_IDX)
-    int cnt = kPllCntDefault;  // bit f - 17: the count runner takes form f's range (FMRX_PLL_CNT)
-    int stick = 1;       // the three-candidate runner's stick form past trigOffset 2^24 (FMRX_PLL_STICK)
-    int inject = -1;     // test hook: the runners corrupt batch 1 + (k + s) % (nb - 1) of stream s
-    int pipe_miss = -1;  // test hook: the self-certifying runners report interval k as missed
-    double skew = 0.0;   // test hook: the host's trigOffset bounds shifted by this many samples
-};
+// What the host knows when it launches a PLL (ctx.h TrigTrack tracks it per context): the device's SIMD
+// count (streams per wave) and, when `known`, bounds on every stream's trigOffset at the call's
+// start (integer-valued, <= 2^24: the reference's float increments from a reset), so that
+// launch_pll enqueues only the runners some segment can use.  Unknown (the fmrx_pll primitive's
+// state lives in caller memory): every runner is launched and each takes its own waves.
 struct PllHint {
     int n_simd = 1024;
     PllKnobs knobs;
@@ -137,13 +115,22 @@ struct PllHint {
     // launches waited ~0.3 ms for CUs the stage kernels beside the chains hold
     bool demote_once = false;
 };
+// The PLL `loop` over n samples of n_streams streams (state st, 8 floats per stream), then the NCO
+// (filter.cpp:136-174), in place.  side: device scratch of pll_side_doubles(n, n_streams) doubles.
+// spec_stats (diagnostic, may be null): the speculative path adds the runner batches that did
+// not verify to spec_stats[0] and the batches checked to spec_stats[1].
 // nco = false: the NCO pass is left to the caller (launch_pll_nco with the same io, n, stride,
-// side and st, on any stream ordered after this launch and before `side` is reused).
-int launch_pll(float* io, int n, int n_streams, size_t stride, float freq, float fs,
-               float nco_scale, float phase_adjust, float norm_bw, float* st, double* side, hipStream_t s,
-               const PllHint& hint, unsigned long long* spec_stats = nullptr, bool nco = true);
-int launch_pll_nco(float* io, int n, int n_streams, size_t stride, float nco_scale, float phase_adjust, float* st,
-                   const double* side, hipStream_t s);
+// loop, side and st, on any stream ordered after this launch and before `side` is reused).
+int launch_pll(float* io, int n, int n_streams, size_t stride, const PllLoop& loop, float* st, double* side,
+               hipStream_t s, const PllHint& hint, unsigned long long* spec_stats = nullptr, bool nco = true);
+int launch_pll_nco(float* io, int n, int n_streams, size_t stride, const PllLoop& loop, float* st, double* side,
+                   hipStream_t s);
+// stereo.hip: the NCO pass alone (filter.cpp:170, parallel over samples): io[i] = cos(args[i] nco_scale +
+// phase_adjust) per stream (args rows astride floats apart) and the ncoOut_state carry; the kernel
+// sits beside the small audio kernel, which inlines the same arithmetic.  Enqueues only: the caller
+// reads the launch status (launch_pll, launch_pll_nco).
+void launch_nco_pass(float* io, int n, int n_streams, size_t stride, const float* args, size_t astride,
+                     const PllLoop& loop, float* st, hipStream_t s);
 
 // pll_sat.hip: the saturated-segment runner over a launch_pll segment (pll_spec_lane_kernel's grid
 // and arguments; it runs the streams that one leaves to it)
@@ -160,9 +147,11 @@ void launch_pll_pred(int waves, hipStream_t s, const float* io, int n, int n_str
 // pll_pred.hip: the three-wave runner for one stream a workgroup (spw == 1) from trigOffset 2^20,
 // the stick included (pll_pipe_stream), self-certifying (no check / resume kernel): one launch runs
 // samples [0, n) of io (stream stride `stride`) from the state st and writes their trigArgs to out
-// (stride ostride) and the exact end state to st.  form 22: 3 candidates, 64-step intervals
-// (trigOffset from 2^22); 21: 5 candidates, 64 steps ([2^21, 2^22)); 20: 5 candidates, 16 steps
-// ([2^20, 2^21)).  A stream whose trigOffset is outside the form's domain runs the range on the
+// (stride ostride) and the exact end state to st.  Its forms (pll_forms.h kPllForms: domains and
+// interval lengths), by default: 22, 3 candidates, 256-step intervals (trigOffset from 2^22); 23,
+// the same at the stuck trigOffset 2^24; 25, the same in 128-step intervals (short calls); 21, 5
+// candidates, 128 steps ([2^21, 2^22)); 20, 5 candidates, 16 steps ([2^20, 2^21)); 24, the same
+// from 2^20 to the stick.  A stream whose trigOffset is outside the form's domain runs the range on the
 // exact path (a wrong host hint costs speed, not bits).  miss >= 1 / inject >= 0 (test hooks):
 // a forced miss on interval `miss` / interval 1 + (inject + s) % intervals, so the exact redo
 // runs.  stats (may be null): += batches redone exactly, batches run.
@@ -182,8 +171,8 @@ int launch_pll_idx(hipStream_t s, const float* io, int n, int n_streams, size_t 
 // pll_pred.hip: the count runner (pll_cnt_kernel: the chain picks each step's e by one compare of
 // the phase against a row of exact thresholds and a bit count), one stream a workgroup of five
 // waves (a CU), self-certifying, same arguments as launch_pll_idx; form 17 / 18: [2^17, 2^18) /
-// [2^18, 2^19), 31 candidates, 16-step intervals; 19: [2^19, 2^20), 15, 32 steps; 20: [2^20,
-// 2^21), 15, 64 steps; 21: [2^21, 2^22), 7, 64 steps.
+// [2^18, 2^19), 31 candidates, 16-step intervals; 19: [2^19, 2^20), 15, 64 steps; 20: [2^20,
+// 2^21), 15, 128 steps; 21: [2^21, 2^22), 7, 64 steps (pll_forms.h kPllForms, by default).
 int launch_pll_cnt(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step, float norm_bw,
                    float* st, float* out, size_t ostride, int inject, int miss, int form, unsigned long long* stats,
                    unsigned* redos = nullptr);
@@ -193,14 +182,8 @@ int launch_pll_cnt(hipStream_t s, const float* io, int n, int n_streams, size_t 
 // not demoted), which this kernel clears.  One stream a workgroup: a speculative chain
 // (pll_spec_lane_kernel's step) checked a sub-segment behind by the other waves, which also form
 // its side data; a batch that does not verify is recomputed exactly and the chain resumes after it.
-// steps an interval of launch_pll's form (17-23) on the count runner (cnt) or the index / three-wave
-// runner: a range of fewer than 24 intervals cannot demote (launch_pll skips pll_demoted_kernel)
-int pll_form_interval(int form, bool cnt);
-// launch_pll: a range of fewer than kPllShortIntervals of its form's long intervals runs on the
-// 16-step forms (in a call of fewer than kPllShortCall steps a stream, to the call's end); a long
-// form's tail past its last whole interval of at least kPllShortTail steps runs on the 16-step form
-// (three 16-step intervals; a long launch needs two whole intervals or it runs exactly)
-constexpr size_t kPllShortCall = 4096, kPllShortIntervals = 2, kPllShortTail = 48;
+// Only a range of at least kPllDemoteMinIntervals of its form's intervals can demote: the plan
+// queues pll_demoted_kernel after exactly those (PllStep::demote_after, or once a call).
 int launch_pll_demoted(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step,
                        float norm_bw, float* st, float* out, size_t ostride, int inject, unsigned long long* stats);
 // fmrx_debug_pll_redos: per stream kPllRedoSlots u32, by the trigOffset range r of the runner's
@@ -211,13 +194,6 @@ int launch_pll_demoted(hipStream_t s, const float* io, int n, int n_streams, siz
 // a later launch that only adds its steps to the hand-off (PllHint::demote_once) files them in
 // that slot too, also past a range boundary; a stream's slots 4 .. 7 sum to its demoted steps
 constexpr int kPllRedoSlots = 8;
-constexpr int kPllIdxSimds = 4;  // SIMDs a stream takes: one CU (launch_pll admits n_simd / 4 streams)
-// the index runner's lowest trigOffset: 2^17 (kPllIdxMin64; 2^18, kPllIdxMin, with FMRX_PLL_IDX=1).  In
-// [2^17, 2^18) 32 candidates (c0 - 16 .. c0 + 15) run 62 ns a step with their misses redone,
-// against the lane runner's 75; 64 took 113 (1,024 candidate evaluations an interval on three
-// evaluator waves, profiles/r04/val/stages.json; profiles/r04/ab_idx17_nc32/)
-constexpr float kPllIdxMin = 262144.0f;
-constexpr float kPllIdxMin64 = 131072.0f;
 
 // test hook: the PLL's fallback libm on device (kind 0 sincos, 1 atan2, 2 NCO cos)
 int launch_pll_fallback_test(int kind, const float* a, const float* b, size_t n, float* out, hipStream_t s);
@@ -242,10 +218,9 @@ struct AudioLaunch {
 int launch_stereo_audio_range(const AudioLaunch& L, int b0, int b1, bool last, int n_streams, hipStream_t s);
 int launch_stereo_audio(const AudioLaunch& L, int n_streams, hipStream_t s);
 // A few blocks a stream in ONE launch (modes 0/1, the per-block seam): the NCO from the PLL's
-// trigArgs (args, astride floats a stream: pll_trig_args of a launch_pll with nco = false), the audio
+// trigArgs (args, astride floats a stream: pll_scratch's of a launch_pll with nco = false), the audio
 // of every block in order, the state carry and the demod history move (the last demod_hist samples
 // of the call to the front of its buffer); -1 when the geometry does not fit the tile.
-const float* pll_trig_args(const double* side, int n, int n_streams);
 int launch_stereo_audio_small(const AudioLaunch& L, int n_streams, const float* args, size_t astride, float nco_scale,
                               float phase_adjust, float* pll_st, int demod_hist, hipStream_t s);
 

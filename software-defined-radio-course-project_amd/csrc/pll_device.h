@@ -1,12 +1,14 @@
 // pll_device.h — device pieces of the stereo pilot PLL (src/filter.cpp:136-174) shared by
-// stereo.hip (the runners, check and resume kernels) and pll_sat.hip (the saturated-segment
-// runner, built as its own translation unit: see the Makefile).
+// pll.hip (the runners, check and resume kernels) and pll_sat.hip (the saturated-segment
+// runner, built as its own translation unit: see the Makefile).  The regime boundaries and launch
+// constants the kernels share with the host's plan are pll_forms.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <utility>
 
 #include "pll_cr.h"
+#include "pll_forms.h"
 #include "pll_math.h"
 
 namespace fmrx {
@@ -68,10 +70,6 @@ __device__ __noinline__ PllPair pll_redo(PllState p, PllCtx ctx, const float* xb
     return PllPair{p, ctx};
 }
 
-// NB samples per optimistic batch.  Measured (10 s mode-0 stereo): NB = 16 beats 8 and 12.  The
-// certification is ~23 % of the step: without it the loop runs 0.31 s instead of 0.40 s.
-constexpr int kPllBatch = 16;
-
 // Demotion of a self-certifying runner's stream (pll_pred.hip): the chain keeps the verdicts of
 // its last 32 intervals as bits; past kPllDemoteMisses misses among them the trigArgs are not
 // where the candidates are predicted (an unlocked loop: no pilot, noise, mode 2/3's if_fs, whose
@@ -85,9 +83,7 @@ constexpr int kPllDemoteMisses = 24;
 // demoted steps ran after the runner launch (0.4206 vs 0.4098 s at 28, none demoted at 28 or 32;
 // profiles/r06/demote_probe/); the unlocked streams still demote within their first ~30 intervals
 constexpr int kPllDemoteMissesIdx = 28;
-// only a runner launch of at least this many intervals demotes (launch_pll queues the demoted kernel
-// after exactly those: a shorter range cannot pay for it, e.g. the per-block seam's 640 steps)
-constexpr int kPllDemoteMinIntervals = 64;
+// (only a runner launch of at least kPllDemoteMinIntervals intervals demotes: pll_forms.h)
 // test hook (knob pll_pipe_miss = m): m >= 1 a forced miss on interval m (past the last: the last),
 // m <= -2 on every interval from -m - 1 on (an unlocked loop's pattern: the demotion runs), -1 off
 __device__ inline bool pll_hook_miss(int i, int miss, int ni) {
@@ -124,7 +120,6 @@ __device__ inline bool pll_sat_segment(int spw, float trig0, double step) {
 // takes the predicted runner only if every stream of it qualifies (ballot: all lanes alike), and
 // pll_spec_lane_kernel makes the same test to leave exactly those waves to it; saturated waves go
 // to pll_sat_kernel first when it is launched.
-constexpr float kPllPredMin = 1048576.0f;  // 2^20
 __device__ inline bool pll_pred_wave(float trig0, double step) {
     const bool ok = trig0 >= kPllPredMin && trig0 <= kPllTrigStick && trig0 == floorf(trig0) &&
                     fabs(step * (double)kPllTrigStick) < kPllMaxPr;
@@ -137,9 +132,6 @@ __device__ inline bool pll_pred_wave(float trig0, double step) {
 // in 64-step intervals in [2^21, 2^22) (99.97 %), five in 16-step intervals in [2^20, 2^21)
 // (99.7 %; a miss costs an exact redo).  pll_pred_kernel and pll_sat_kernel leave these streams
 // to it when it is launched.
-constexpr float kPllPipeMin = 4194304.0f;     // 2^22
-constexpr float kPllPipeMin5 = 2097152.0f;    // 2^21
-constexpr float kPllPipeMinLow = 1048576.0f;  // 2^20
 __device__ inline bool pll_pipe_stream(float trig0, double step, float lo = kPllPipeMinLow,
                                        float hi = kPllTrigStick) {
     return trig0 >= lo && trig0 <= hi && trig0 == floorf(trig0) && fabs(step * (double)kPllTrigStick) < kPllMaxPr;

@@ -16,6 +16,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "pll_forms.h"
+
 #ifdef __HIPCC__
 #define FMRX_HD __host__ __device__ inline
 #else
@@ -314,10 +316,9 @@ FMRX_HD float pll_step(PllState& p, PllCtx& ctx, float v, float Ki, float Kp, do
 //          (filter.cpp:165-166).  From an integer-valued t0 in [0, 2^24] the float increments
 //          are exact up to 2^24 and then stick there, so trig_j = min(t0 + j + 1, 2^24); any
 //          other t0 (reachable only through fmrx_set_state) or |pr_j| >= kPllMaxPr gives NaN.
-constexpr double kPllMaxPr = 4.0e8;
+// (kPllMaxPr, the bound on |pr_j|, and kPllTrigStick, 2^24: pll_forms.h)
 constexpr float kPllMaxPhase = 5.0e8f;  // with |pr| < 4e8: |trigArg| < kPllMaxX over a batch
 constexpr float kPllMaxInteg = 1.0e6f;
-constexpr float kPllTrigStick = 16777216.0f;  // 2^24: trigOffset + 1.0f == trigOffset from here
 
 FMRX_HD bool pll_trig_domain(float t0) {
     return t0 >= 0.0f && t0 <= kPllTrigStick && t0 == floorf(t0);

@@ -2031,15 +2031,6 @@ void launch_pll_pred(int waves, hipStream_t s, const float* io, int n, int n_str
                        seg, step, norm_bw, st, out, ostride, fail, rec, rb, inject, sat_ok, pipe_on);
 }
 
-#ifndef FMRX_STICK_BPI
-#define FMRX_STICK_BPI 16  // batches an interval of the stick form: 256-step intervals (8: 128, 4: 64)
-#endif
-#ifndef FMRX_PIPE22_BPI
-#define FMRX_PIPE22_BPI 16  // batches an interval of the three-candidate form below the stick (256 steps)
-#endif
-#ifndef FMRX_PIPE21_BPI
-#define FMRX_PIPE21_BPI 8  // batches an interval of the five-candidate [2^21, 2^22) form (128 steps)
-#endif
 #ifndef FMRX_PIPE_RD
 #define FMRX_PIPE_RD 8  // intervals of step inputs in flight (the evaluators' loop is unrolled by it)
 #endif
@@ -2050,8 +2041,13 @@ void launch_pll_pipe(hipStream_t s, const float* io, int n, int n_streams, size_
     reg_pred_prof();
 #endif
     if (n <= 0) return;
+    // kPllForms' interval of the form, in batches: the kernel's BPI
+    constexpr auto bpi = [](int f) { return pll_form(f, false).interval / kPllBatch; };
+    static_assert(bpi(25) == FMRX_PIPE25_BPI && bpi(24) == 1 && bpi(23) == FMRX_STICK_BPI &&
+                      bpi(22) == FMRX_PIPE22_BPI && bpi(21) == FMRX_PIPE21_BPI && bpi(20) == 1,
+                  "the instantiations below run pll_forms.h's intervals");
     if (form == 25)  // short calls from 2^22: three candidates in 128-step intervals (640 = 5 of them)
-        hipLaunchKernelGGL((pll_pipe_kernel<kPllBatch, 8, FMRX_PIPE_RD, 3>), dim3(n_streams), dim3(192), 0, s, io, n,
+        hipLaunchKernelGGL((pll_pipe_kernel<kPllBatch, FMRX_PIPE25_BPI, FMRX_PIPE_RD, 3>), dim3(n_streams), dim3(192), 0, s, io, n,
                            n_streams, stride, step, norm_bw, st, out, ostride, inject, miss, stats, redos);
     else if (form == 24)  // the short-call form: any trigOffset from 2^20, 16-step intervals
         hipLaunchKernelGGL((pll_pipe_kernel<kPllBatch, 1, FMRX_PIPE_RD, 5, false, true>), dim3(n_streams), dim3(192), 0, s,
@@ -2086,7 +2082,7 @@ void launch_pll_pipe(hipStream_t s, const float* io, int n, int n_streams, size_
 // and LDS use, so a build that outgrows it fails loudly instead of serialising.
 template <int NC, int NW>
 static int idx_launch(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step,
-                      float norm_bw, float* st, float* out, size_t ostride, int inject, int miss, float lo, float hi,
+                      float norm_bw, float* st, float* out, size_t ostride, int inject, int miss, const PllForm& f,
                       unsigned long long* stats, unsigned* redos) {
     constexpr int threads = 64 * (1 + NW);
     static const int resident = [] {
@@ -2096,7 +2092,7 @@ static int idx_launch(hipStream_t s, const float* io, int n, int n_streams, size
     }();
     if (resident < 1) return -1;
     hipLaunchKernelGGL((pll_idx_kernel<NC, NW>), dim3(n_streams), dim3(threads), 0, s, io, n, n_streams, stride, step,
-                       norm_bw, st, out, ostride, inject, miss, lo, hi, stats, redos);
+                       norm_bw, st, out, ostride, inject, miss, f.lo, f.hi, stats, redos);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2107,21 +2103,22 @@ int launch_pll_idx(hipStream_t s, const float* io, int n, int n_streams, size_t 
     reg_pred_prof();
 #endif
     if (n <= 0) return 0;
+    const PllForm& f = pll_form(form, false);  // (the kernel's intervals are kPllBatch steps, as every index row's)
     if (form == 17)
         return idx_launch<FMRX_IDX17_NC, FMRX_IDX_NW>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride,
-                                                      inject, miss, 131072.0f, 262143.0f, stats, redos);
+                                                      inject, miss, f, stats, redos);
     if (form == 18)
         return idx_launch<FMRX_IDX18_NC, FMRX_IDX_NW>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride,
-                                                      inject, miss, 262144.0f, 524287.0f, stats, redos);
-    return idx_launch<16, 3>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss, 524288.0f,
-                             1048575.0f, stats, redos);
+                                                      inject, miss, f, stats, redos);
+    return idx_launch<16, 3>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss, f, stats,
+                             redos);
 }
 
 // The count runner's forms (form: the trigOffset range as launch_pll numbers it), one stream a
 // workgroup of 1 + NW waves (a CU), residency checked like idx_launch.
 template <int NI, int NC, int NW>
 static int cnt_launch(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step,
-                      float norm_bw, float* st, float* out, size_t ostride, int inject, int miss, float lo, float hi,
+                      float norm_bw, float* st, float* out, size_t ostride, int inject, int miss, const PllForm& f,
                       unsigned long long* stats, unsigned* redos) {
     constexpr int threads = 64 * (1 + NW);
     static const int resident = [] {
@@ -2131,32 +2128,16 @@ static int cnt_launch(hipStream_t s, const float* io, int n, int n_streams, size
     }();
     if (resident < 1) return -1;
     hipLaunchKernelGGL((pll_cnt_kernel<NI, NC, NW>), dim3(n_streams), dim3(threads), 0, s, io, n, n_streams, stride,
-                       step, norm_bw, st, out, ostride, inject, miss, lo, hi, stats, redos);
+                       step, norm_bw, st, out, ostride, inject, miss, f.lo, f.hi, stats, redos);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-#ifndef FMRX_CNT19_NI
-#define FMRX_CNT19_NI 64  // steps an interval of the [2^19, 2^20) count form
-#endif
-#ifndef FMRX_CNT20_NI
-#define FMRX_CNT20_NI 128  // steps an interval of the [2^20, 2^21) count form (two rows of counts)
-#endif
 #ifndef FMRX_CNT_NW
 #define FMRX_CNT_NW 4  // evaluator waves of the [2^19, 2^21) count forms
 #endif
-#ifndef FMRX_CNT17_NI
-#define FMRX_CNT17_NI 16  // steps an interval of the [2^17, 2^19) count forms (off by default)
-#endif
 #ifndef FMRX_CNT17_NW
-#define FMRX_CNT17_NW 4  // their evaluator waves
+#define FMRX_CNT17_NW 4  // evaluator waves of the [2^17, 2^19) count forms
 #endif
-int pll_form_interval(int form, bool cnt) {
-    if (cnt) return form <= 18 ? FMRX_CNT17_NI : form == 19 ? FMRX_CNT19_NI : form == 20 ? FMRX_CNT20_NI : 64;
-    if (form < 20) return 16;  // the index runner
-    if (form == 25) return kPllBatch * 8;
-    return form == 20 || form == 24 ? kPllBatch : form == 21 ? kPllBatch * FMRX_PIPE21_BPI
-         : form == 22 ? kPllBatch * FMRX_PIPE22_BPI : kPllBatch * FMRX_STICK_BPI;
-}
 
 int launch_pll_cnt(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step, float norm_bw,
                    float* st, float* out, size_t ostride, int inject, int miss, int form, unsigned long long* stats,
@@ -2165,22 +2146,25 @@ int launch_pll_cnt(hipStream_t s, const float* io, int n, int n_streams, size_t 
     reg_pred_prof();
 #endif
     if (n <= 0) return 0;
+    constexpr auto ni = [](int f) { return pll_form(f, true).interval; };
+    static_assert(ni(17) == FMRX_CNT17_NI && ni(18) == FMRX_CNT17_NI && ni(19) == FMRX_CNT19_NI &&
+                      ni(20) == FMRX_CNT20_NI && ni(21) == FMRX_CNT21_NI,
+                  "the instantiations below run pll_forms.h's intervals");
+    const PllForm& f = pll_form(form, true);
     switch (form) {
         case 17:
-            return cnt_launch<FMRX_CNT17_NI, 31, FMRX_CNT17_NW>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss,
-                                         131072.0f, 262143.0f, stats, redos);
         case 18:
             return cnt_launch<FMRX_CNT17_NI, 31, FMRX_CNT17_NW>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss,
-                                         262144.0f, 524287.0f, stats, redos);
+                                         f, stats, redos);
         case 19:
             return cnt_launch<FMRX_CNT19_NI, 15, FMRX_CNT_NW>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss,
-                                         524288.0f, 1048575.0f, stats, redos);
+                                         f, stats, redos);
         case 20:
             return cnt_launch<FMRX_CNT20_NI, 15, FMRX_CNT_NW>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss,
-                                         kPllPipeMinLow, kPllPipeMin5 - 1.0f, stats, redos);
+                                         f, stats, redos);
         default:  // three waves a stream, as the three-wave runner it would replace
-            return cnt_launch<64, 7, 2>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss,
-                                        kPllPipeMin5, kPllPipeMin - 1.0f, stats, redos);
+            return cnt_launch<FMRX_CNT21_NI, 7, 2>(s, io, n, n_streams, stride, step, norm_bw, st, out, ostride, inject, miss,
+                                                   f, stats, redos);
     }
 }
 

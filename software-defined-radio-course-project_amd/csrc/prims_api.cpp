@@ -71,8 +71,8 @@ int fmrx_pll(fmrx_ctx* c, float* d_io, int n, float freq, float fs, float nco_sc
     hint.trig_lo = hint.trig_hi = hint.known ? (double)trig : 0.0;
     hint.timer = c->stage_timer.on ? &c->stage_timer : nullptr;
     hint.redos = c->pll_redos;  // fmrx_debug_pll_redos: as stream 0
-    if (launch_pll(d_io, n, 1, (size_t)n, freq, fs, nco_scale, phase_adjust, norm_bw, c->d_scratch.p,
-                   c->d_pll_side.p, c->stream, hint, c->pll_stats))
+    const PllLoop loop{freq, fs, nco_scale, phase_adjust, norm_bw};
+    if (launch_pll(d_io, n, 1, (size_t)n, loop, c->d_scratch.p, c->d_pll_side.p, c->stream, hint, c->pll_stats))
         return fail(FMRX_EHIP, "launch failed");
     HIPCHK(hipMemcpyAsync(d_st, c->d_scratch.p, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return FMRX_OK;

@@ -574,7 +574,7 @@ def test_many_streams_cross_wave_boundaries(fmrx, orc, channels, n_streams):
                                  {"pll_inject": "7"}])
 @pytest.mark.parametrize("n_streams,nb", [(1, 450), (6, 40), (1100, 2)])
 def test_pll_speculation_fallbacks(fmrx, orc, monkeypatch, env, n_streams, nb):
-    """The speculative PLL (stereo.hip pll_spec_kernel -> pll_check_kernel -> pll_kernel from
+    """The speculative PLL (pll.hip pll_spec_kernel -> pll_check_kernel -> pll_kernel from
     the first batch that differs) equals the reference whatever the runner got wrong: with the
     test hook knob pll_inject=k the runner corrupts batch 1 + (k + s) % (nb - 1) of every
     stream s, so every stream resumes at its own batch (and a wave of several streams, at 1,100
@@ -1432,7 +1432,7 @@ def test_mixed_locked_unlocked_streams(fmrx, n_streams, cuts):
         assert (dem[s] > 0) == (s in where), (s, dem.tolist())
 
 
-# (edge, steps an interval of the form in front of it, of the form behind it: pll_form_interval)
+# (edge, steps an interval of the form in front of it, of the form behind it: pll_forms.h kPllForms)
 _FORM_EDGES = [(262144.0, 16, 16), (524288.0, 16, 64), (1048576.0, 64, 128), (2097152.0, 128, 128),
                (4194304.0, 128, 256), (16777216.0, 256, 256)]
 
