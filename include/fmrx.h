@@ -23,6 +23,8 @@
  *                                 never launched by the reference, :380-382)
  *   fmrx_rds_bits / _device,      no counterpart: the RDS back half (symbol-rate resampler, bits,
  *   fmrx_rds_parse, _decode ...   block syndromes, group parser), defined below
+ *   fmrx_set_deemphasis,          no counterpart: the reference never de-emphasises (its audio goes
+ *   fmrx_deemph, _design          from the low-pass or LRExtraction straight into the quantiser)
  *   fmrx_fm_demod_arctan       <- fmDemodArctan        model/fmSupportLib.py:34-63
  *   fmrx_estimate_psd          <- estimatePSD          include/fourier.h:27-31, src/fourier.cpp:35-117
  *   fmrx_psd_device               (model/fmSupportLib.py:83-157)
@@ -340,12 +342,47 @@ int fmrx_wide_granule(const fmrx_ctx* ctx, size_t* blocks, size_t* wide_pairs);
 int fmrx_scan_detect_rate(const float* power, int fft_bins, int rf_fs, int cap_fs, const fmrx_scan_config* cfg,
                           fmrx_station* out, int max_out, int* n_found, float* floor_db);
 
+/* ---- FM de-emphasis: the broadcast's 50 / 75 us pre-emphasis undone in front of the S16 quantiser -- */
+/* Neither the reference nor, by default, this library de-emphasises.  The stage is defined here (csrc/
+ * deemph.hip) so that it is exact in parallel.  audio_fs = if_fs audio_up / audio_down
+ * (48000 in modes 0 and 1, 44100 in modes 2 and 3), tau_us 50 (most of the world) or 75 (the Americas,
+ * Korea).  Taps, T = 64, in double: p = exp(-1.0 / (audio_fs tau_us 1e-6)), r[0] = 1 - p, r[n] = r[n-1] p,
+ * h[n] = (float) r[n]: the one-pole filter's response, whose tail past 64 samples is below half a float32
+ * ulp of its sum (p^64 <= 1.9e-8 < 2^-25 for these rates and time constants; a longer one would not be).
+ * Filter, per stream and channel: y[n] = sum_k h[k] x[n - k], acc = fl(acc + fl(h[k] x)) from 0 in
+ * ascending k (fmrx_resample's definition with up = down = 1), the 63 samples in front of a stream being
+ * 0; then the quantiser of fmrx_quantize.  MONO contexts: x is the mono product.  STEREO contexts: left
+ * and right (fmrx_lr_extraction's outputs) each go through the filter with a history of their own; the
+ * PCM stays interleaved R, L.
+ * fmrx_deemph_design is host only and needs no context, like fmrx_tuner_design: 64 floats into h64.
+ * FMRX_EINVAL, nothing written: tau_us other than 50 and 75, audio_fs <= 0, h64 NULL.                 */
+int fmrx_deemph_design(int audio_fs, int tau_us, float* h64);
+/* tau_us 0 (the default): off -- no call does, launches or allocates anything more, every output bit is
+ * what it was.  50 or 75: every call that writes PCM (fmrx_process, fmrx_process_device(_ex),
+ * fmrx_audio_block, tuned calls, fmrx_process_shared(_device), fmrx_process_wide(_device); every mode,
+ * mono and stereo, both stereo engines; with fmrx_set_rds too) routes the floats in front of its quantiser
+ * into a scratch of the context -- 4 B per audio sample and channel of a call, grown on demand; a mono
+ * fmrx_process_device_ex with d_mono uses that instead -- and the de-emphasis kernel then writes the
+ * call's PCM.  d_mono of fmrx_process_device_ex stays the mono product as it was.  The carry (63 floats
+ * per stream and channel) survives across calls, any split of a stream into calls gives the same bits;
+ * fmrx_reset clears it and keeps the setting; fmrx_set_deemphasis (any value, the current one too) clears
+ * it and nothing else.  While it is on, fmrx_get_state, fmrx_set_state and fmrx_seek return FMRX_ESTATE
+ * (the blob does not hold the carry).  FMRX_EINVAL, nothing changed: any other tau_us.                */
+int fmrx_set_deemphasis(fmrx_ctx* ctx, int tau_us);
+int fmrx_deemphasis(const fmrx_ctx* ctx, int* tau_us);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */
 /* d_state: taps-1 floats (in/out).  Returns the output count in *n_out.                    */
 int fmrx_resample(fmrx_ctx* ctx, float* d_out, float* d_state, const float* d_in, int n_in,
                   const float* d_coeff, int taps, int up, int down, int* n_out);
+/* The de-emphasis kernel on one row, with the context's audio rate's taps for tau_us (50 or 75, whatever
+ * fmrx_set_deemphasis says): y = the filter above over d_in[0..n), d_state the 63 floats in front of them
+ * (in/out: afterwards the last 63 of state ++ input, n may be shorter than that).  d_out gets y, d_pcm its
+ * quantised form; each may be NULL; d_out must not be d_in.                                         */
+int fmrx_deemph(fmrx_ctx* ctx, const float* d_in, size_t n, int tau_us, float* d_state /* 63 floats, in/out */,
+                float* d_out /* may be NULL */, int16_t* d_pcm /* may be NULL */);
 /* d_prev: 2 floats {prev_i, prev_q} (in/out).                                              */
 int fmrx_fm_demod(fmrx_ctx* ctx, float* d_out, float* d_prev, const float* d_i,
                   const float* d_q, int n);

@@ -1,6 +1,6 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
 // [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]
-// [--capture-rate HZ] [--rds]`:
+// [--capture-rate HZ] [--rds] [--deemph 50|75]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -34,6 +34,9 @@
 //     whole RDS granules (fmrx_rds_granule), the tuned front end runs (offset 0 without --offset-hz), and
 //     at end of input one line goes to stderr, `rds pi=%04X pty=%d ps="........" groups=%d`.  stdout is
 //     unchanged: blocks past the last whole granule are decoded without RDS.
+//   * --deemph 50|75 (an fmrx extension) de-emphasises the PCM with that time constant in microseconds
+//     (fmrx_set_deemphasis: 50 in most of the world, 75 in the Americas and Korea), whatever else is
+//     chosen; without it the audio is as broadcast, as project's is.  Any other value: message, exit 1.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -103,6 +106,7 @@ void usage(const char* argv0) {
                  "Usage: %s\nor \nUsage %s <mode> <channels>\n"
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
+                 "                [--deemph 50|75]  de-emphasise the audio (time constant in us; default: none)\n"
                  "                [--rds]  decode the station's RDS too; at end of input print its PI, PTY and name to stderr\n"
                  "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
                  "                [--capture-decim D]  stdin runs at D (2..10) times the mode's rate; --offset-hz and\n"
@@ -161,9 +165,9 @@ int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
     bool mono_product = false, tuned = false, scan = false, rds = false;
     long offset_hz = 0;
-    int iq_format = FMRX_IQ_U8, capture_decim = 1;
+    int iq_format = FMRX_IQ_U8, capture_decim = 1, deemph_us = 0;
     long capture_rate = 0;
-    bool have_decim = false, have_rate = false;
+    bool have_decim = false, have_rate = false, have_deemph = false;
     const char* bad_format = nullptr;
     long long scan_bytes = 1ll << 24;
     std::vector<const char*> pos;
@@ -182,6 +186,10 @@ int main(int argc, char** argv) {
             else if (!std::strcmp(f, "s16")) iq_format = FMRX_IQ_S16;
             else if (!std::strcmp(f, "f32")) iq_format = FMRX_IQ_F32;
             else bad_format = f;
+        }
+        else if (!std::strcmp(argv[i], "--deemph") && i + 1 < argc) {
+            deemph_us = std::atoi(argv[++i]);
+            have_deemph = true;
         }
         else if (!std::strcmp(argv[i], "--capture-decim") && i + 1 < argc) {
             capture_decim = std::atoi(argv[++i]);
@@ -225,6 +233,10 @@ int main(int argc, char** argv) {
     }
     if (have_rate && (capture_rate < 1 || capture_rate > 2147483647l)) {
         std::fprintf(stderr, "fmrx: --capture-rate %ld: expected a rate in Hz\n", capture_rate);
+        return 1;
+    }
+    if (have_deemph && deemph_us != 50 && deemph_us != 75) {
+        std::fprintf(stderr, "fmrx: --deemph %d: expected 50 or 75 (microseconds)\n", deemph_us);
         return 1;
     }
     bool wide = capture_decim > 1;
@@ -276,6 +288,11 @@ int main(int argc, char** argv) {
         if (scan_bytes <= 0) std::fprintf(stderr, "fmrx: --scan-bytes must be positive\n");
         fmrx_destroy(ctx);
         return rc;
+    }
+    if (have_deemph && fmrx_set_deemphasis(ctx, deemph_us) != FMRX_OK) {
+        std::fprintf(stderr, "fmrx: --deemph: %s\n", fmrx_last_error());
+        fmrx_destroy(ctx);
+        return 1;
     }
     // --rds: whole RDS granules a batch (rounded up), decoded by the tuned front end
     size_t rds_unit = unit_blocks;

@@ -89,7 +89,16 @@ int reset_state(fmrx_ctx* c) {
                           c->stream));
     int rc = reset_rds_bits(c);
     if (rc) return rc;
+    if ((rc = reset_deemph(c))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// The de-emphasis carry back to 63 zeros in front of every row (nothing to do before it was ever on)
+int reset_deemph(fmrx_ctx* c) {
+    c->deemph_cur = 0;
+    if (c->d_deemph_state[0].p)
+        HIPCHK(hipMemsetAsync(c->d_deemph_state[0].p, 0, sizeof(float) * c->d_deemph_state[0].n, c->stream));
     return 0;
 }
 
@@ -360,6 +369,8 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
     c->d_wide_hist.release(); c->d_wide_taps.release(); c->d_wide_tab.release(); c->d_wide_streams.release();
     c->d_wide_y.release(); c->d_wide_halo[0].release(); c->d_wide_halo[1].release();
+    c->d_deemph_taps.release(); c->d_deemph_state[0].release(); c->d_deemph_state[1].release();
+    c->d_deemph_x.release(); c->d_deemph_tmp.release();
     for (auto& e : c->evs) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -390,6 +401,7 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
     if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
+    if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_seek: not with de-emphasis on (its carry has no seek)");
     if (n % c->pair_bytes != 0)
         return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
     int rc = set_device(c);
@@ -410,6 +422,34 @@ int fmrx_reset(fmrx_ctx* c) {
     if (!c) return fail(FMRX_EINVAL, "null context");
     int rc = set_device(c);
     return rc ? rc : reset_state(c);
+}
+
+// ---- FM de-emphasis: configuration and a carry of its own --------------------------------------
+int fmrx_set_deemphasis(fmrx_ctx* c, int tau_us) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    if (tau_us != 0 && tau_us != 50 && tau_us != 75)
+        return fail(FMRX_EINVAL, "de-emphasis of %d us: 0 (off), 50 or 75", tau_us);
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the carry
+    if (tau_us) {
+        const size_t rows = (size_t)c->cfg.n_streams * (size_t)c->cfg.channels;
+        if ((rc = ensure_deemph_taps(c)) || (rc = c->d_deemph_state[0].ensure(rows * kDeemphHist)) ||
+            (rc = c->d_deemph_state[1].ensure(rows * kDeemphHist)))
+            return rc;
+    }
+    c->deemph_tau = tau_us;
+    if ((rc = reset_deemph(c))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return FMRX_OK;
+}
+
+int fmrx_deemphasis(const fmrx_ctx* c, int* tau_us) {
+    CtxLock lock_(c);
+    if (!c || !tau_us) return fail(FMRX_EINVAL, "null argument");
+    *tau_us = c->deemph_tau;
+    return FMRX_OK;
 }
 
 // ---- state blob: header + halo bytes + audio history + stereo state ------------------
@@ -498,6 +538,7 @@ int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
     if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_get_state: not with de-emphasis on (the blob does not hold its carry)");
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
 
@@ -505,6 +546,7 @@ int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
     if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_set_state: not with de-emphasis on (the blob does not hold its carry)");
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
     if (rc == 0) {

@@ -197,6 +197,14 @@ struct Ctx {
     // hold the rational stage's history, taps by phase, tables (kRateMaxN a stream), rows and halo
     int rate_up = 0, rate_down = 0, rate_cap_fs = 0;
     size_t rate_blocks = 1;                   // narrow blocks a granule: rate_up / gcd(rate_up, iq_pairs)
+    // FM de-emphasis (fmrx_set_deemphasis, deemph.hip): configuration and a carry of its own; nothing
+    // here is allocated until it is first turned on (or fmrx_deemph first runs)
+    int deemph_tau = 0;                       // 0 off, 50 or 75 us
+    DevBuf<float> d_deemph_taps;              // 2 x kDeemphTaps: the context's audio rate at 50, then at 75 us
+    DevBuf<float> d_deemph_state[2];          // n_streams x channels x kDeemphHist inputs in front of the next call
+    int deemph_cur = 0;
+    DevBuf<float> d_deemph_x;                 // a call's floats in front of the quantiser (4 B a sample and channel)
+    DevBuf<float> d_deemph_tmp;               // fmrx_deemph: the caller's next state, before it is copied back
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -296,6 +304,7 @@ inline int set_device(const fmrx_ctx* c) {
 
 // ---- context.cpp
 int reset_state(fmrx_ctx* c);
+int reset_deemph(fmrx_ctx* c);  // the de-emphasis carry alone, enqueued on the context stream
 // fmrx_kernel_timing around one launch on st: when timing is armed, begin takes the next event pair
 // and records its first event (*ev, null at the call, stays null otherwise); end records the second
 int timing_begin(fmrx_ctx* c, hipStream_t st, TimingPair** ev);
@@ -316,6 +325,14 @@ int run_stereo_pipelined(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int1
 int run_rds(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_if, float* d_out, float* d_nco,
             float* d_channel);
 int ensure_demod(fmrx_ctx* c, size_t n_if);
+// De-emphasis behind an audio stage (fmrx_set_deemphasis on).  deemph_rows: where the stage's float
+// outlet writes a call of na frames a stream -- the caller's d_mono when a mono call gave one, else the
+// context's scratch, grown to the call.  run_deemph: those rows through deemph.hip into d_pcm on the
+// context stream, the carry moved.  The audio rate the taps are designed for: deemph_audio_fs.
+int deemph_rows(fmrx_ctx* c, size_t na, float* d_mono, float** rows);
+int run_deemph(fmrx_ctx* c, const float* rows, size_t na, int16_t* d_pcm);
+int ensure_deemph_taps(fmrx_ctx* c);
+inline int deemph_audio_fs(const fmrx_ctx* c) { return c->geo.if_fs / c->geo.audio_down; }  // if_fs holds audio_up
 
 // ---- rds_api.cpp
 // blocks of an RDS granule (with a capture rate set: the least common multiple with the wide granule's)

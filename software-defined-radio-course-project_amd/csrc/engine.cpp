@@ -109,6 +109,45 @@ constexpr int kPipeFrontWgPerCu = 2;
 
 }  // namespace
 
+// ---- de-emphasis behind the audio stages (deemph.hip) ------------------------------
+int ensure_deemph_taps(fmrx_ctx* c) {
+    if (c->d_deemph_taps.p) return 0;
+    float h[2 * kDeemphTaps];
+    if (!deemph_design(deemph_audio_fs(c), 50, h) || !deemph_design(deemph_audio_fs(c), 75, h + kDeemphTaps))
+        return fail(FMRX_EINVAL, "no de-emphasis design at %d S/s", deemph_audio_fs(c));
+    int rc = c->d_deemph_taps.ensure(2 * kDeemphTaps);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(c->d_deemph_taps.p, h, sizeof h, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int deemph_rows(fmrx_ctx* c, size_t na, float* d_mono, float** rows) {
+    if (c->cfg.channels == FMRX_MONO && d_mono) {
+        *rows = d_mono;
+        return 0;
+    }
+    const int rc = c->d_deemph_x.ensure((size_t)c->cfg.n_streams * na * (size_t)c->cfg.channels);
+    *rows = c->d_deemph_x.p;
+    return rc;
+}
+
+int run_deemph(fmrx_ctx* c, const float* rows, size_t na, int16_t* d_pcm) {
+    DeemphLaunch D{};
+    D.in = rows;
+    D.nch = c->cfg.channels == FMRX_MONO ? 1 : 2;
+    D.in_stride = na * (size_t)D.nch;
+    D.n = na;
+    D.h = c->d_deemph_taps.p + (c->deemph_tau == 75 ? kDeemphTaps : 0);
+    D.state_in = c->d_deemph_state[c->deemph_cur].p;
+    D.state_out = c->d_deemph_state[c->deemph_cur ^ 1].p;
+    D.out = nullptr;
+    D.pcm = d_pcm;
+    D.out_stride = D.in_stride;
+    if (launch_deemph(D, c->cfg.n_streams, c->stream)) return fail(FMRX_EHIP, "de-emphasis launch failed");
+    c->deemph_cur ^= 1;
+    return 0;
+}
+
 // RF front end (+ the mono audio stage when `pcm` is non-null and the mode allows it).
 // Chunk form (the stereo pipeline, run_stereo_pipelined): blocks [b0, b0 + n_blocks) of a call of
 // call_blocks blocks a stream starting at d_iq, on stream `st`; the halo of a chunk past the first
@@ -127,6 +166,13 @@ int run_fused(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm,
     L.halo_stride = b0 == 0 ? c->halo_bytes : L.iq_stride;
     L.pcm = d_pcm;
     L.mono = d_mono;
+    // de-emphasis on: the kernel's float outlet feeds deemph.hip, which then writes the call's PCM
+    float* dx = nullptr;
+    if (with_audio && c->deemph_tau) {
+        const int rc_dx = deemph_rows(c, n_blocks * c->geo.audio_frames, d_mono, &dx);
+        if (rc_dx) return rc_dx;
+        L.mono = dx;
+    }
     L.demod = d_demod ? d_demod + b0 * c->geo.if_samples : nullptr;
     L.demod_stride = demod_stride;
     L.demod_hist = demod_hist;
@@ -162,6 +208,7 @@ int run_fused(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm,
     if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "fused kernel launch failed (%d)", rc);
     if ((rc = timing_end(ev, st))) return rc;
     if (with_audio) c->audio_hist_stale = false;  // demod_tail rewrote the audio history
+    if (dx && (rc = run_deemph(c, dx, n_blocks * c->geo.audio_frames, d_pcm))) return rc;
     if (!last) return 0;
     if (!L.halo_next) {  // the whole call's tail (every chunk's bytes are in d_iq)
         rc = launch_halo_update(d_iq, call_blocks * bb, c->d_halo[c->halo_cur].p, c->d_halo[c->halo_cur ^ 1].p,
@@ -191,6 +238,12 @@ int run_mono_audio(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_
     P.up = c->geo.audio_up;
     P.down = c->geo.audio_down;
     P.n_out = (int)na;
+    float* dx = nullptr;  // de-emphasis on: the float outlet feeds deemph.hip, which then writes d_pcm
+    if (c->deemph_tau) {
+        const int rc_dx = deemph_rows(c, na, d_mono, &dx);
+        if (rc_dx) return rc_dx;
+        d_mono = dx;
+    }
     P.out = d_mono;
     P.out_stride = na;
     P.pcm = d_pcm;
@@ -200,7 +253,7 @@ int run_mono_audio(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_
         rc = launch_copy_streams(c->d_audio_hist.p, c->audio_hist, d_demod + (n_if - (at - 1)), demod_stride,
                                  at - 1, ns, c->stream);
     if (rc) return fail(FMRX_EHIP, "mono audio stage launch failed");
-    return 0;
+    return dx ? run_deemph(c, dx, na, d_pcm) : 0;
 }
 
 // Stereo engine on c->d_demod (history in front, n_if new samples per stream).
@@ -238,6 +291,10 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
         return fail(FMRX_EHIP, "PLL launch failed");
     }
     c->pll_trig.advance(n_if);
+    // de-emphasis on: the audio kernels' (right, left) outlet feeds deemph.hip, which then writes d_pcm
+    const size_t na = n_blocks * c->geo.audio_frames;
+    float* dx = nullptr;
+    if (c->deemph_tau && (rc = deemph_rows(c, na, nullptr, &dx))) return rc;
     AudioLaunch A{};
     A.demod = c->d_demod.p;
     A.demod_stride = c->demod_stride;
@@ -248,6 +305,7 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
     A.mono_state = c->d_mono_state.p;
     A.pcm = d_pcm;
     A.mono_out = d_mono;
+    A.lr_out = reinterpret_cast<float2*>(dx);
     A.n_blocks = (int)n_blocks;
     A.if_per_block = (int)c->geo.if_samples;
     A.frames_per_block = (int)c->geo.audio_frames;
@@ -261,7 +319,7 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
                                       pilot.phase_adjust, c->d_pll.p, kDemodHist, c->stream))
             return fail(FMRX_EHIP, "stereo audio launch failed");
         c->stage_timer.end(t_au, kStAudio, 0.0, c->stream);
-        return 0;
+        return dx ? run_deemph(c, dx, na, d_pcm) : 0;
     }
     if (launch_stereo_audio(A, ns, c->stream)) return fail(FMRX_EHIP, "stereo audio launch failed");
     c->stage_timer.end(t_au, kStAudio, 0.0, c->stream);
@@ -270,7 +328,7 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
     if (launch_copy_streams(c->d_demod.p, c->demod_stride, c->d_demod.p + n_if, c->demod_stride, kDemodHist, ns,
                             c->stream))
         return fail(FMRX_EHIP, "demod history copy failed");
-    return 0;
+    return dx ? run_deemph(c, dx, na, d_pcm) : 0;
 }
 
 namespace {
@@ -382,6 +440,11 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
         max_m = std::max(max_m, (cb(k + 1) - cb(k)) * ipb);
     if ((rc = c->d_pll_side.ensure(pll_side_doubles((int)max_m, ns)))) return rc;
     if ((rc = c->d_pll_side2.ensure(pll_side_doubles((int)max_m, ns)))) return rc;
+    // de-emphasis on: the (right, left) outlet of every chunk's audio stage, then deemph.hip over the
+    // whole call on the context stream once it has waited for the audio stream
+    const size_t na = n_blocks * c->geo.audio_frames;
+    float* dx = nullptr;
+    if (c->deemph_tau && (rc = deemph_rows(c, na, nullptr, &dx))) return rc;
     AudioLaunch A{};
     A.demod = c->d_demod.p;
     A.demod_stride = c->demod_stride;
@@ -392,6 +455,7 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
     A.mono_state = c->d_mono_state.p;
     A.pcm = d_pcm;
     A.mono_out = d_mono;
+    A.lr_out = reinterpret_cast<float2*>(dx);
     A.n_blocks = (int)n_blocks;
     A.if_per_block = (int)ipb;
     A.frames_per_block = (int)c->geo.audio_frames;
@@ -503,7 +567,7 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
         return fail(FMRX_EHIP, "demod history copy failed");
     HIPCHK(hipEventRecord(ev_end, c->s_audio));
     HIPCHK(hipStreamWaitEvent(c->stream, ev_end, 0));
-    return 0;
+    return dx ? run_deemph(c, dx, na, d_pcm) : 0;
 }
 }  // namespace
 

@@ -211,6 +211,7 @@ struct AudioLaunch {
     int n_blocks, if_per_block, frames_per_block;
     int up, down, at;       // audio resampler
     const float* audio_c;
+    float2* lr_out;         // optional (right, left) floats a frame, as they enter the quantiser
 };
 // The audio stage of blocks [b0, b1) of the call (the blocks before b0 already computed: their
 // demod / channel / NCO feed b0's histories), then, when `last`, the state carry of the call's
@@ -279,6 +280,27 @@ struct RdsBitsLaunch {
     int n_if, n_out, n_win, n_sym;  // n_out = 2432 n_win = n_if 19 / down, n_sym = 76 n_win
 };
 int launch_rds_bits(const RdsBitsLaunch& L, int n_streams, hipStream_t s);
+
+// ---- FM de-emphasis (deemph.hip) -------------------------------------------
+constexpr int kDeemphTaps = 64;      // the one-pole response cut where it is below half an ulp of its sum
+constexpr int kDeemphHist = kDeemphTaps - 1;  // inputs carried in front of a call, per stream and channel
+constexpr int kDeemphChunk = 1024;   // outputs a workgroup
+// the 64 taps of fmrx_deemph_design (host only, all in double until stored); false, nothing
+// written: audio_fs <= 0 or a tau_us other than 50 and 75
+bool deemph_design(int audio_fs, int tau_us, float* h);
+struct DeemphLaunch {
+    const float* in;        // row r = (stream s, channel ch): sample i at in[s in_stride + ch + i nch]
+    size_t in_stride;
+    int nch;                // 1, or 2 for interleaved (right, left) frames
+    size_t n;               // samples a row
+    const float* h;         // kDeemphTaps taps
+    const float* state_in;  // rows x kDeemphHist: the inputs in front of the call
+    float* state_out;       // rows x kDeemphHist: the inputs in front of the next (never state_in)
+    float* out;             // optional floats, laid out as pcm
+    int16_t* pcm;           // optional S16: sample i of row r at pcm[s out_stride + ch + i nch]
+    size_t out_stride;
+};
+int launch_deemph(const DeemphLaunch& L, int n_streams, hipStream_t s);
 
 // ---- spectrum tooling and the arctan demodulator ------------------
 constexpr int kPsdMaxBins = 8192;  // N complex doubles in LDS per segment

@@ -110,6 +110,38 @@ int fmrx_quantize(fmrx_ctx* c, const float* d_x, size_t n, int16_t* d_out) {
     return launch_quantize(d_x, n, d_out, c->stream) ? fail(FMRX_EHIP, "launch failed") : 0;
 }
 
+// ---- FM de-emphasis (no counterpart in the reference) ------------------------
+int fmrx_deemph_design(int audio_fs, int tau_us, float* h64) {
+    if (!h64) return fail(FMRX_EINVAL, "null tap pointer");
+    if (!deemph_design(audio_fs, tau_us, h64))
+        return fail(FMRX_EINVAL, "de-emphasis of %d us at %d S/s: 50 or 75 us at a positive rate", tau_us, audio_fs);
+    return FMRX_OK;
+}
+
+int fmrx_deemph(fmrx_ctx* c, const float* d_in, size_t n, int tau_us, float* d_state, float* d_out, int16_t* d_pcm) {
+    CtxLock lock_(c);
+    if (!c || !d_in || !d_state) return fail(FMRX_EINVAL, "null argument");
+    if (tau_us != 50 && tau_us != 75) return fail(FMRX_EINVAL, "de-emphasis of %d us: 50 or 75", tau_us);
+    if (d_out == d_in) return fail(FMRX_EINVAL, "fmrx_deemph does not run in place");
+    if (n == 0) return FMRX_OK;
+    int rc = set_device(c);
+    if (rc || (rc = ensure_deemph_taps(c)) || (rc = c->d_deemph_tmp.ensure(kDeemphHist))) return rc;
+    DeemphLaunch D{};
+    D.in = d_in;
+    D.in_stride = n;
+    D.nch = 1;
+    D.n = n;
+    D.h = c->d_deemph_taps.p + (tau_us == 75 ? kDeemphTaps : 0);
+    D.state_in = d_state;
+    D.state_out = c->d_deemph_tmp.p;  // a first chunk may still read d_state when the last one is done
+    D.out = d_out;
+    D.pcm = d_pcm;
+    D.out_stride = n;
+    if (launch_deemph(D, 1, c->stream)) return fail(FMRX_EHIP, "de-emphasis launch failed");
+    HIPCHK(hipMemcpyAsync(d_state, c->d_deemph_tmp.p, sizeof(float) * kDeemphHist, hipMemcpyDeviceToDevice, c->stream));
+    return FMRX_OK;
+}
+
 int fmrx_test_pll_fallback(fmrx_ctx* c, int kind, const float* d_a, const float* d_b, size_t n, float* d_out) {
     CtxLock lock_(c);
     if (!c || kind < 0 || kind > 2 || (n && (!d_a || !d_out || (kind == 1 && !d_b))))

@@ -292,6 +292,7 @@ __global__ void stereo_audio_kernel(AudioLaunch L, int b0) {
     L.pcm[2 * o] = quantize_s16(right);        // project.cpp:184-187 (R first)
     L.pcm[2 * o + 1] = quantize_s16(left);
     if (L.mono_out) L.mono_out[o] = mono;
+    if (L.lr_out) L.lr_out[o] = make_float2(right, left);
 }
 
 // Modes 0/1 (up = 1): one workgroup per (block, stream).  The block's (demod, mixer) pairs sit in
@@ -364,6 +365,7 @@ __device__ void audio_tile(const AudioLaunch& L, int s, int b, bool carry = fals
         L.pcm[2 * o] = quantize_s16(right);          // project.cpp:184-187 (R first)
         L.pcm[2 * o + 1] = quantize_s16(left);
         if (L.mono_out) L.mono_out[o] = MO[m];
+        if (L.lr_out) L.lr_out[o] = make_float2(right, left);
     }
     if (!carry) return;
     __syncthreads();  // every read of the old mono_state / mix_tail happened above

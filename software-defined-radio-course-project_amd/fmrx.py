@@ -155,6 +155,10 @@ PROTOTYPES = {
     "fmrx_wide_granule": (C.c_int, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "fmrx_scan_detect_rate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(ScanConfig), C.POINTER(Station), C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "fmrx_deemph_design": (C.c_int, [C.c_int, C.c_int, _vp]),
+    "fmrx_set_deemphasis": (C.c_int, [_vp, C.c_int]),
+    "fmrx_deemphasis": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "fmrx_deemph": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp, _vp]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -294,6 +298,18 @@ def rate_design(rf_fs: int, cap_fs: int, offset_hz: int) -> dict:
     return {"up": up, "down": down, "coarse_hz": fc, "fine_hz": fr, "N": n, "k": k, "table": tab, "h": h}
 
 
+DEEMPH_TAPS = 64      # csrc/fmrx_internal.h kDeemphTaps: taps of the de-emphasis FIR (63 floats of carry)
+DEEMPH_CHUNK = 1024   # kDeemphChunk: outputs a workgroup of the de-emphasis kernel
+
+
+def deemph_design(audio_fs: int, tau_us: int) -> np.ndarray:
+    """fmrx_deemph_design: the 64 float32 taps of the de-emphasis filter for tau_us (50 or 75) at
+    audio_fs S/s.  Host only."""
+    h = np.zeros(DEEMPH_TAPS, np.float32)
+    _check(lib().fmrx_deemph_design(int(audio_fs), int(tau_us), _np_ptr(h)))
+    return h
+
+
 def iq_pair_bytes(fmt: int) -> int:
     """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
     n = lib().fmrx_iq_pair_bytes(fmt)
@@ -381,14 +397,15 @@ def rds_parse(bits, codes, info: RdsInfo | None = None) -> RdsInfo:
 
 
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
-                    capture_rate: int | None = None, rds: bool = False, **cfg):
+                    capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
     capture_decim times the mode's rate (scan_wide, tune_wide, process_wide).  capture_rate=HZ: the
     capture's rate in Hz instead (set_capture_rate; whole granules are decoded); giving both is a
     ValueError.  rds=True: the capture is trimmed to whole RDS granules and the result is
-    (stations, pcm, infos), infos one dict a station (pi, pty, tp, ps, rt and the parser's counters)."""
+    (stations, pcm, infos), infos one dict a station (pi, pty, tp, ps, rt and the parser's counters).
+    deemphasis_us=50 or 75: the PCM is de-emphasised (set_deemphasis; 0, the default: as broadcast)."""
     if capture_rate is not None and capture_decim != 1:
         raise ValueError("capture_rate and capture_decim exclude each other")
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
@@ -412,6 +429,8 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
         configure(rx)
         getattr(rx, tune)([s.offset_hz for s in stations])
+        if deemphasis_us:
+            rx.set_deemphasis(deemphasis_us)
         if rds:
             rx.set_rds(True)
             blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
@@ -612,6 +631,27 @@ class Receiver:
         info = RdsInfo()
         _check(lib().fmrx_rds_info_get(self.h, int(stream), C.byref(info)))
         return info
+
+    # ---- FM de-emphasis
+    @property
+    def audio_fs(self) -> int:
+        """The PCM's rate: if_fs audio_up / audio_down (geo.if_fs already holds audio_up)."""
+        return self.geo.if_fs // self.geo.audio_down
+
+    def set_deemphasis(self, tau_us: int) -> None:
+        """fmrx_set_deemphasis: 0 off (the default), 50 or 75 us; every call that writes PCM then
+        de-emphasises it.  Clears the stage's carry and nothing else."""
+        _check(lib().fmrx_set_deemphasis(self.h, int(tau_us)))
+
+    def deemphasis(self) -> int:
+        t = C.c_int()
+        _check(lib().fmrx_deemphasis(self.h, C.byref(t)))
+        return t.value
+
+    def deemph(self, d_in: int, n: int, tau_us: int, d_state: int, d_out: int | None = None,
+               d_pcm: int | None = None) -> None:
+        """fmrx_deemph: the de-emphasis kernel on one row of n device floats; d_state 63 floats in/out."""
+        _check(lib().fmrx_deemph(self.h, d_in, n, int(tau_us), d_state, d_out, d_pcm))
 
     def estimate_psd(self, samples: np.ndarray, freq_bins: int, fs: float):
         """estimatePSD (fourier.cpp:35-117) on the GPU: (freq, psd_db)."""
