@@ -278,7 +278,7 @@ int main(int argc, char** argv) {
             fmrx_destroy(ctx);
             return 1;
         }
-        wide = d != 1;  // the mode's own rate is no wide capture
+        wide = d != 1;  // fmrx_capture_decim reads 1 at the mode's own rate alone (D, or 0 at a rational ratio): no wide capture
     }
     const size_t pair_bytes = (size_t)fmrx_iq_pair_bytes(iq_format);
     const size_t block_bytes = unit_pairs * pair_bytes;  // bytes a read unit; geo.block_bytes for u8 at the mode's rate

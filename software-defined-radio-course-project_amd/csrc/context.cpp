@@ -59,9 +59,9 @@ int reset_state(fmrx_ctx* c) {
     HIPCHK(hipMemsetAsync(c->d_halo[0].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     HIPCHK(hipMemsetAsync(c->d_halo[1].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
     c->halo_cur = 0;
-    if (wide_on(c)) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
+    if (c->ratio.on()) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
         const size_t nh = c->halo_pairs * 8 * ns;
-        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), wide_hist_pairs(c) * c->pair_bytes, c->stream));
+        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), c->ratio.hist_pairs() * c->pair_bytes, c->stream));
         HIPCHK(hipMemsetAsync(c->d_wide_halo[0].p, 0, nh, c->stream));
         HIPCHK(hipMemsetAsync(c->d_wide_halo[1].p, 0, nh, c->stream));
         c->wide_halo_cur = 0;
@@ -400,7 +400,7 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     CtxLock lock_(c);
     if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
-    if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
+    if (c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
     if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_seek: not with de-emphasis on (its carry has no seek)");
     if (n % c->pair_bytes != 0)
         return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
@@ -537,7 +537,7 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
 int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
-    if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
     if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_get_state: not with de-emphasis on (the blob does not hold its carry)");
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
@@ -545,7 +545,7 @@ int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
 int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
-    if (wide_on(c)) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
     if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_set_state: not with de-emphasis on (the blob does not hold its carry)");
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);

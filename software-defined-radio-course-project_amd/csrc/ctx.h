@@ -15,8 +15,8 @@
 
 #include "../../include/fmrx.h"
 #include "fmrx_internal.h"
-#include "rate.h"
 #include "tuner.h"
+#include "wide.h"
 
 namespace fmrx {
 
@@ -91,6 +91,23 @@ struct PinnedBuf {
 };
 
 using TimingPair = std::pair<hipEvent_t, hipEvent_t>;
+
+// The rate of a context's captures against the mode's: cap_fs = rf_fs down / up in lowest terms.  1/1:
+// no wide stage; up = 1: the integer stage (wide.hip); anything else: the rational one (rate.hip).
+// Everything the host derives from the ratio has one form; the integer case is that form at up = 1.
+struct CaptureRatio {
+    int up = 1, down = 1;
+    size_t blocks = 1;  // narrow blocks a granule (the fewest that are whole wide pairs): up / gcd(up, iq_pairs)
+    bool on() const { return down != up; }
+    bool rational() const { return up != 1; }
+    int cap_fs(int rf_fs) const { return rf_fs / up * down; }  // up divides rf_fs
+    // raw wide pairs of history the stage keeps in front of the next call
+    size_t hist_pairs() const { return (size_t)rate_hist_pairs(up, down); }
+    // wide pairs that n_blocks narrow blocks of iq_pairs take (n_blocks a whole number of granules)
+    size_t pairs_of(size_t n_blocks, size_t iq_pairs) const { return n_blocks * iq_pairs / (size_t)up * (size_t)down; }
+    // wide pairs a narrow pair, rounded up: check_call_size's factor of a wide call
+    size_t size_factor() const { return (size_t)((down + up - 1) / up); }
+};
 
 // The members of fmrx_ctx (below: the ABI's opaque type lives outside the namespace).
 struct Ctx {
@@ -179,24 +196,20 @@ struct Ctx {
     DevBuf<float> d_scan_part;                // the launch's partial rows (scan_workgroups x N)
     DevBuf<float> d_scan_power;               // the host entry points' result, N floats
     DevBuf<uint8_t> d_scan_in;                // the host entry points' capture
-    // wide captures (fmrx_set_capture_decim): the down-converter in front of the tuner (wide.hip);
-    // its history, rows and narrow halo are its own, nothing the ordinary calls read
-    int wide_decim = 1;                       // cap_fs / rf_fs; 1: no wide stage
+    // wide captures (fmrx_set_capture_decim, fmrx_set_capture_rate): the capture stage in front of the
+    // tuner (wide.hip or rate.hip, by the ratio); its history, rows and narrow halo are its own, nothing
+    // the ordinary calls read
+    CaptureRatio ratio;                       // cap_fs / rf_fs; 1/1: no wide stage
     bool wide_tuned = false;                  // fmrx_tune_wide accepted (fmrx_tune turns it off)
     std::vector<int32_t> wide_offsets;        // n_streams, against cap_fs
-    DevBuf<uint8_t> d_wide_hist;              // the 16 decim raw pairs of the capture in front of the next call
-    DevBuf<float> d_wide_taps;                // the 16 decim + 1 taps of the low-pass
-    DevBuf<float> d_wide_tab;                 // n_streams x kWideMaxN (c, s) pairs: the coarse tables
+    DevBuf<uint8_t> d_wide_hist;              // the ratio.hist_pairs() raw pairs of the capture in front of the next call
+    DevBuf<float> d_wide_taps;                // the low-pass: 16 down + 1 floats at up = 1, else the RateTap rows by phase
+    DevBuf<float> d_wide_tab;                 // n_streams x kRateMaxN (c, s) pairs: the coarse tables
     DevBuf<uint32_t> d_wide_streams;          // WideStream per stream
     DevBuf<float> d_wide_y;                   // n_streams x wide_y_stride floats: one piece's cf32 rows at rf_fs
     size_t wide_y_stride = 0;
     DevBuf<uint8_t> d_wide_halo[2];           // the narrow stage's f32 halo (halo_pairs x 8 B a stream)
     int wide_halo_cur = 0;
-    // a capture at a rational rate (fmrx_set_capture_rate, rate.hip): cap_fs = rf_fs rate_down / rate_up
-    // in lowest terms.  rate_up = 0: none; otherwise wide_decim is 0 and the wide stage's buffers above
-    // hold the rational stage's history, taps by phase, tables (kRateMaxN a stream), rows and halo
-    int rate_up = 0, rate_down = 0, rate_cap_fs = 0;
-    size_t rate_blocks = 1;                   // narrow blocks a granule: rate_up / gcd(rate_up, iq_pairs)
     // FM de-emphasis (fmrx_set_deemphasis, deemph.hip): configuration and a carry of its own; nothing
     // here is allocated until it is first turned on (or fmrx_deemph first runs)
     int deemph_tau = 0;                       // 0 off, 50 or 75 us
@@ -282,21 +295,8 @@ inline int check_call_size(const fmrx_ctx* c, size_t n_blocks, size_t decim = 1)
         return fail(FMRX_EINVAL, "%zu blocks: the call's byte count overflows", n_blocks);
     return 0;
 }
-// The wide stage (integer or rational) is on
-inline bool wide_on(const fmrx_ctx* c) { return c->wide_decim != 1; }
-// Raw wide pairs of history the wide stage keeps in front of the next call
-inline size_t wide_hist_pairs(const fmrx_ctx* c) {
-    return c->rate_up ? (size_t)rate_hist_pairs(c->rate_up, c->rate_down) : 16 * (size_t)c->wide_decim;
-}
 // Wide pairs that n_blocks narrow blocks take (n_blocks a whole number of granules)
-inline size_t wide_pairs_of(const fmrx_ctx* c, size_t n_blocks) {
-    if (c->rate_up) return n_blocks * c->geo.iq_pairs / (size_t)c->rate_up * (size_t)c->rate_down;
-    return n_blocks * c->geo.iq_pairs * (size_t)c->wide_decim;
-}
-// check_call_size's factor of a wide call: wide pairs a narrow pair, rounded up
-inline size_t wide_size_factor(const fmrx_ctx* c) {
-    return c->rate_up ? (size_t)((c->rate_down + c->rate_up - 1) / c->rate_up) : (size_t)c->wide_decim;
-}
+inline size_t wide_pairs_of(const fmrx_ctx* c, size_t n_blocks) { return c->ratio.pairs_of(n_blocks, c->geo.iq_pairs); }
 inline int set_device(const fmrx_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     return 0;
@@ -352,7 +352,7 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
 // decim within the down-converter's range (or_one: 1, no wide stage, passes too); rf_fs a positive multiple of 4
 int check_capture_decim(int decim, bool or_one);
 int check_wide_rf_fs(int rf_fs);
-// n_blocks of a wide call: whole granules of a rational context (FMRX_EINVAL otherwise)
+// n_blocks of a wide call: whole granules (FMRX_EINVAL otherwise)
 int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks);
 
 }  // namespace fmrx

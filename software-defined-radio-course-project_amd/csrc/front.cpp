@@ -1,9 +1,8 @@
 // front.cpp — the front ends ahead of the audio stages other than the fused kernel: the tuned front
-// end (tuner.hip) and the wide down-converters in front of it (wide.hip for an integer ratio, rate.hip
-// for a rational one), with the calls that configure them: tuning, the raw I/Q format, the capture
-// decimation and the capture rate.
+// end (tuner.hip) and the capture stage in front of it (wide.h: one host path around wide.hip for an
+// integer ratio and rate.hip for a rational one), with the calls that configure them: tuning, the raw
+// I/Q format, the capture decimation and the capture rate.
 #include "ctx.h"
-#include "wide.h"
 
 #include <numeric>
 
@@ -147,7 +146,7 @@ int upload_zero_offsets(fmrx_ctx* c) {
 }
 
 // y rows of one internal piece of a wide call: at most this many bytes over all streams (a piece
-// is a whole number of blocks, at least one)
+// is a whole number of granules, at least one)
 constexpr size_t kWidePieceBytes = (size_t)128 << 20;
 
 }  // namespace
@@ -165,18 +164,21 @@ int check_wide_rf_fs(int rf_fs) {
 }
 
 int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks) {
-    if (c->rate_up && n_blocks % c->rate_blocks != 0)
-        return fail(FMRX_EINVAL, "%zu blocks: a call at %d S/s takes whole granules of %zu blocks", n_blocks, c->rate_cap_fs,
-                    c->rate_blocks);
+    if (n_blocks % c->ratio.blocks != 0)  // an integer ratio's granule is one block
+        return fail(FMRX_EINVAL, "%zu blocks: a call at %d S/s takes whole granules of %zu blocks", n_blocks,
+                    c->ratio.cap_fs(c->geo.rf_fs), c->ratio.blocks);
     return 0;
 }
 
-// run_wide at a rational rate (fmrx_set_capture_rate): the same steps with rate.hip's kernel, pieces of
-// whole granules, and the history of rate_hist_pairs raw pairs.
-static int run_rate(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
-    const int ns = c->cfg.n_streams, up = c->rate_up, down = c->rate_down;
-    const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples, gran = c->rate_blocks;
-    const size_t hb = wide_hist_pairs(c) * c->pair_bytes;
+// A wide call (fmrx_process_wide_device; arguments checked, device set): per piece of whole granules
+// the down-converter (wide.hip or rate.hip, by the ratio) into the y rows, then the tuned front end
+// reading them as an f32 stream with the wide stage's own halo; the demod rows of the whole call then
+// take the audio stage a tuned call takes.  A piece past the first finds its history in the capture itself.
+int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
+    const CaptureRatio& r = c->ratio;
+    const int ns = c->cfg.n_streams;
+    const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples, gran = r.blocks;
+    const size_t hb = r.hist_pairs() * c->pair_bytes;
     int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
     if (rc || (rc = ensure_demod(c, n_if))) return rc;
     const size_t fit = kWidePieceBytes / ((size_t)ns * ip * 8);
@@ -190,26 +192,28 @@ static int run_rate(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* 
     const size_t nhb = c->halo_pairs * 8;
     for (size_t b0 = 0; b0 < n_blocks; b0 += piece) {
         const size_t nb = std::min(piece, n_blocks - b0);
-        RateLaunch R{};
-        R.iq = d_iq + wide_pairs_of(c, b0) * c->pair_bytes;
-        R.hist = b0 == 0 ? c->d_wide_hist.p : R.iq - hb;
-        R.stream_bytes = wide_pairs_of(c, nb) * c->pair_bytes;
-        R.y = c->d_wide_y.p;
-        R.y_stride = c->wide_y_stride;
-        R.n_out = (long long)(nb * ip);
-        R.segs = rate_segments(R.n_out, up, down, ns, c->n_simd / 4);
-        R.format = c->iq_format;
-        R.up = up;
-        R.down = down;
-        R.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
-        R.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
-        R.hp = reinterpret_cast<const RateTap*>(c->d_wide_taps.p);
-        R.first_pair = c->tune_pos / (uint64_t)up * (uint64_t)down;  // tune_pos is a multiple of up
+        DdcLaunch L{};
+        L.iq = d_iq + wide_pairs_of(c, b0) * c->pair_bytes;
+        L.hist = b0 == 0 ? c->d_wide_hist.p : L.iq - hb;
+        L.stream_bytes = wide_pairs_of(c, nb) * c->pair_bytes;
+        L.y = c->d_wide_y.p;
+        L.y_stride = c->wide_y_stride;
+        L.n_out = (long long)(nb * ip);
+        L.segs = wide_segments(L.n_out, r.up, r.down, ns, c->n_simd / 4);
+        L.format = c->iq_format;
+        L.up = r.up;
+        L.down = r.down;
+        L.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
+        L.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
+        L.taps = c->d_wide_taps.p;
+        L.first_pair = c->tune_pos / (uint64_t)r.up * (uint64_t)r.down;  // tune_pos is a multiple of up
         TimingPair* ev = nullptr;  // fmrx_kernel_timing: the down-converter's launches
         if ((rc = timing_begin(c, c->stream, &ev))) return rc;
-        rc = launch_rate_ddc(R, ns, c->stream);
-        if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "rational down-converter launch failed (%d)", rc);
+        rc = launch_wide_ddc(L, ns, c->stream);
+        if (rc != 0)
+            return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "%sdown-converter launch failed (%d)", r.rational() ? "rational " : "", rc);
         if ((rc = timing_end(ev, c->stream))) return rc;
+        // the y rows as an f32 stream, the wide stage's own halo in front of them
         if ((rc = launch_front(c, reinterpret_cast<const uint8_t*>(c->d_wide_y.p), c->wide_y_stride * sizeof(float), kIqF32,
                                c->d_wide_halo, &c->wide_halo_cur, nhb, nb, c->d_demod.p + b0 * c->geo.if_samples,
                                c->demod_stride, kDemodHist, false)))
@@ -221,88 +225,55 @@ static int run_rate(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* 
     return run_audio_stage(c, n_blocks, d_pcm, nullptr);
 }
 
-// A wide call (fmrx_process_wide_device; arguments checked, device set): per piece of whole blocks
-// the down-converter (wide.hip) into the y rows, then the tuned front end reading them as an f32
-// stream with the wide stage's own halo; the demod rows of the whole call then take the audio stage
-// a tuned call takes.  A piece past the first finds its history in the capture itself.
-int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
-    if (c->rate_up) return run_rate(c, d_iq, n_blocks, d_pcm);
-    const int ns = c->cfg.n_streams, D = c->wide_decim;
-    const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples;
-    const size_t wide_block = (size_t)D * iq_block_bytes(c), hb = 16 * (size_t)D * c->pair_bytes;
-    int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
-    if (rc || (rc = ensure_demod(c, n_if))) return rc;
-    const size_t piece = std::min(n_blocks, std::max<size_t>(1, kWidePieceBytes / ((size_t)ns * ip * 8)));
-    if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->wide_y_stride = 0;
-        if ((rc = c->d_wide_y.ensure((size_t)ns * piece * ip * 2))) return rc;
-        c->wide_y_stride = piece * ip * 2;
-    }
-    const size_t nhb = c->halo_pairs * 8;
-    for (size_t b0 = 0; b0 < n_blocks; b0 += piece) {
-        const size_t nb = std::min(piece, n_blocks - b0);
-        WideLaunch W{};
-        W.iq = d_iq + b0 * wide_block;
-        W.hist = b0 == 0 ? c->d_wide_hist.p : W.iq - hb;
-        W.stream_bytes = nb * wide_block;
-        W.y = c->d_wide_y.p;
-        W.y_stride = c->wide_y_stride;
-        W.n_out = (long long)(nb * ip);
-        W.segs = wide_segments(W.n_out, D, ns, c->n_simd / 4);
-        W.format = c->iq_format;
-        W.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
-        W.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
-        W.h = c->d_wide_taps.p;
-        W.first_pair = c->tune_pos * (uint64_t)D;
-        TimingPair* ev = nullptr;  // fmrx_kernel_timing: the down-converter's launches
-        if ((rc = timing_begin(c, c->stream, &ev))) return rc;
-        rc = launch_wide_ddc(W, ns, D, c->stream);
-        if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "down-converter launch failed (%d)", rc);
-        if ((rc = timing_end(ev, c->stream))) return rc;
-        // the y rows as an f32 stream, the wide stage's own halo in front of them
-        if ((rc = launch_front(c, reinterpret_cast<const uint8_t*>(c->d_wide_y.p), c->wide_y_stride * sizeof(float), kIqF32,
-                               c->d_wide_halo, &c->wide_halo_cur, nhb, nb, c->d_demod.p + b0 * c->geo.if_samples,
-                               c->demod_stride, kDemodHist, false)))
-            return rc;
-    }
-    // the next call's history: the capture's last 16 decim pairs (a block holds more than that)
-    HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + n_blocks * wide_block - hb, hb, hipMemcpyDeviceToDevice, c->stream));
-    return run_audio_stage(c, n_blocks, d_pcm, nullptr);
-}
-
 }  // namespace fmrx
 
 namespace {
 
-// fmrx_tune_wide of a context at a rational rate: fmrx_rate_design in fmrx_wide_design's place
-int tune_rate(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
-    const int up = c->rate_up, down = c->rate_down;
-    if (first_pair % (uint64_t)down != 0)
-        return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of %d (the rate is %d/%d of the mode's)",
-                    (unsigned long long)first_pair, down, down, up);
-    const size_t ns = c->cfg.n_streams;
-    std::vector<int32_t> fine(ns);
-    std::vector<WideStream> ws(ns);
-    std::vector<float> tab(2 * (size_t)kRateMaxN * ns, 0.0f);
-    int rc;
-    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
-        int fr = 0, n = 0, k = 0;
-        if ((rc = fmrx_rate_design(c->geo.rf_fs, c->rate_cap_fs, offsets_hz[s], nullptr, nullptr, nullptr, &fr, &n, &k,
-                                   tab.data() + 2 * kRateMaxN * s, nullptr, nullptr)))
-            return rc;
-        fine[s] = fr;
-        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
-    }
-    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
-    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
-    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
-    c->tune_pos = first_pair / (uint64_t)down * (uint64_t)up;
-    c->tuned = true;
-    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
-    c->wide_tuned = true;
+// What fmrx_wide_design and fmrx_rate_design do once the ratio is known and within the limits: the split,
+// the fine part to the tuner, and the outputs, written only on success.  kOffsetOutside (no error text
+// set: the two word it differently) for 2 |offset| >= cap_fs.
+constexpr int kOffsetOutside = 1;
+int design_offset(int rf_fs, int up, int down, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k, float* cos_sin,
+                  int* taps, float* h) {
+    int fc = 0, fr = 0, n = 0, kk = 0;
+    if (!rate_split(rf_fs, up, down, offset_hz, &fc, &fr, &n, &kk, nullptr)) return kOffsetOutside;
+    int tn = 0, tk = 0, rc;
+    if ((rc = fmrx_tuner_design(rf_fs, fr, &tn, &tk, nullptr))) return rc;  // the fine part goes to the tuner
+    if (coarse_hz) *coarse_hz = fc;
+    if (fine_hz) *fine_hz = fr;
+    if (N) *N = n;
+    if (k) *k = kk;
+    if (cos_sin) rate_split(rf_fs, up, down, offset_hz, nullptr, nullptr, nullptr, nullptr, cos_sin);
+    if (taps) *taps = rate_taps(down);
+    if (h) design_lpf(h, (float)rf_fs * (float)down, (float)(3.0 * rf_fs / 8.0), rate_taps(down), up);
     return FMRX_OK;
+}
+
+// The capture stage of the ratio up / down (`blocks` a granule) in place of the context's: the stream
+// drained, the stage's buffers grown and its low-pass uploaded (none at 1/1), the ratio recorded, the
+// state reset.  The ratio is the caller's to check.
+int set_capture_stage(fmrx_ctx* c, int up, int down, size_t blocks) {
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the wide state
+    if (down != up) {
+        const size_t ns = c->cfg.n_streams;
+        std::vector<float> h((size_t)rate_taps(down));
+        design_lpf(h.data(), (float)c->geo.rf_fs * (float)down, (float)(3.0 * c->geo.rf_fs / 8.0), rate_taps(down), up);
+        // the integer kernel reads the taps as they are, the rational one regrouped by phase
+        std::vector<RateTap> hp(up == 1 ? 0 : (size_t)up * rate_phase_stride(up, down));
+        if (up != 1) rate_taps_by_phase(h.data(), up, down, hp.data());
+        const void* taps = up == 1 ? (const void*)h.data() : (const void*)hp.data();
+        const size_t tap_floats = up == 1 ? h.size() : 2 * hp.size();
+        if ((rc = c->d_wide_hist.ensure((size_t)rate_hist_pairs(up, down) * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(tap_floats)) ||
+            (rc = c->d_wide_tab.ensure(2 * (size_t)kRateMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
+            (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
+            return rc;
+        HIPCHK(hipMemcpy(c->d_wide_taps.p, taps, sizeof(float) * tap_floats, hipMemcpyHostToDevice));
+    }
+    c->ratio = CaptureRatio{up, down, blocks};
+    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
+    return reset_state(c);
 }
 
 }  // namespace
@@ -362,7 +333,7 @@ int fmrx_set_input_format(fmrx_ctx* c, int format) {
         const size_t ns = c->cfg.n_streams, hb = c->halo_pairs * (size_t)pb;
         if (format != kIqU8 && !c->tuned && (rc = upload_zero_offsets(c))) return rc;
         if ((rc = c->d_halo[0].ensure(hb * ns)) || (rc = c->d_halo[1].ensure(hb * ns))) return rc;
-        if (wide_on(c) && (rc = c->d_wide_hist.ensure(wide_hist_pairs(c) * (size_t)pb))) return rc;
+        if (c->ratio.on() && (rc = c->d_wide_hist.ensure(c->ratio.hist_pairs() * (size_t)pb))) return rc;
         c->iq_format = format;
         c->pair_bytes = (size_t)pb;
         c->halo_bytes = hb;
@@ -386,95 +357,17 @@ int fmrx_tuner_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* 
     return FMRX_OK;
 }
 
-// ---- wide captures: the decimating down-converter ahead of the tuner ------------------------------
+// ---- wide captures: the capture stage ahead of the tuner (an integer or a rational ratio) -----------
 int fmrx_wide_design(int rf_fs, int decim, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k, float* cos_sin,
                      int* taps, float* h) {
     int rc = check_capture_decim(decim, false);
     if (rc || (rc = check_wide_rf_fs(rf_fs))) return rc;
-    int fc = 0, fr = 0, n = 0, kk = 0;
-    if (!wide_split(rf_fs, decim, offset_hz, &fc, &fr, &n, &kk, nullptr))
+    rc = design_offset(rf_fs, 1, decim, offset_hz, coarse_hz, fine_hz, N, k, cos_sin, taps, h);
+    if (rc == kOffsetOutside)
         return fail(FMRX_EINVAL, "offset %d Hz outside (-%d %d/2, %d %d/2)", offset_hz, decim, rf_fs, decim, rf_fs);
-    int tn = 0, tk = 0;
-    if ((rc = fmrx_tuner_design(rf_fs, fr, &tn, &tk, nullptr))) return rc;  // the fine part goes to the tuner
-    if (coarse_hz) *coarse_hz = fc;
-    if (fine_hz) *fine_hz = fr;
-    if (N) *N = n;
-    if (k) *k = kk;
-    if (cos_sin) wide_split(rf_fs, decim, offset_hz, nullptr, nullptr, nullptr, nullptr, cos_sin);
-    if (taps) *taps = wide_taps(decim);
-    if (h) design_lpf(h, (float)rf_fs * (float)decim, (float)(3.0 * rf_fs / 8.0), wide_taps(decim), 1);
-    return FMRX_OK;
+    return rc;
 }
 
-int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
-    CtxLock lock_(c);
-    if (!c) return fail(FMRX_EINVAL, "null context");
-    int rc = check_capture_decim(decim, true);
-    if (rc) return rc;
-    if (decim == 1 && c->wide_decim == 1) return FMRX_OK;  // the default: nothing anywhere changes (a rational rate: 0)
-    if (decim > 1 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
-        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
-                    c->geo.rf_decim);
-    if ((rc = set_device(c))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the wide state
-    if (decim > 1) {
-        const size_t ns = c->cfg.n_streams;
-        std::vector<float> h((size_t)wide_taps(decim));
-        design_lpf(h.data(), (float)c->geo.rf_fs * (float)decim, (float)(3.0 * c->geo.rf_fs / 8.0), wide_taps(decim), 1);
-        if ((rc = c->d_wide_hist.ensure(16 * (size_t)decim * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(h.size())) ||
-            (rc = c->d_wide_tab.ensure(2 * (size_t)kWideMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
-            (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
-            return rc;
-        HIPCHK(hipMemcpy(c->d_wide_taps.p, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
-    }
-    c->wide_decim = decim;
-    c->rate_up = c->rate_down = c->rate_cap_fs = 0;  // out of a rational rate
-    c->rate_blocks = 1;
-    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
-    return reset_state(c);
-}
-
-int fmrx_capture_decim(const fmrx_ctx* c, int* decim) {
-    CtxLock lock_(c);
-    if (!c || !decim) return fail(FMRX_EINVAL, "null argument");
-    *decim = c->wide_decim;
-    return FMRX_OK;
-}
-
-int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
-    CtxLock lock_(c);
-    if (!c || !offsets_hz) return fail(FMRX_EINVAL, "null argument");
-    if (c->rate_up) return tune_rate(c, offsets_hz, first_pair);
-    const int D = c->wide_decim;
-    if (D == 1) return fail(FMRX_ESTATE, "fmrx_tune_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
-    if (first_pair % (uint64_t)D != 0)
-        return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of the decimation %d",
-                    (unsigned long long)first_pair, D);
-    const size_t ns = c->cfg.n_streams;
-    std::vector<int32_t> fine(ns);
-    std::vector<WideStream> ws(ns);
-    std::vector<float> tab(2 * (size_t)kWideMaxN * ns, 0.0f);
-    int rc;
-    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
-        int fr = 0, n = 0, k = 0;
-        if ((rc = fmrx_wide_design(c->geo.rf_fs, D, offsets_hz[s], nullptr, &fr, &n, &k, tab.data() + 2 * kWideMaxN * s,
-                                   nullptr, nullptr)))
-            return rc;
-        fine[s] = fr;
-        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
-    }
-    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
-    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
-    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
-    c->tune_pos = first_pair / (uint64_t)D;
-    c->tuned = true;
-    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
-    c->wide_tuned = true;
-    return FMRX_OK;
-}
-
-// ---- captures at a rational rate: the polyphase down-converter ahead of the tuner -------------------
 int fmrx_rate_design(int rf_fs, int cap_fs, int offset_hz, int* up, int* down, int* coarse_hz, int* fine_hz, int* N, int* k,
                      float* cos_sin, int* taps, float* h) {
     int l = 0, m = 0;
@@ -482,28 +375,26 @@ int fmrx_rate_design(int rf_fs, int cap_fs, int offset_hz, int* up, int* down, i
     if (kind < 0 || (kind == 1 && m == 1))
         return fail(FMRX_EINVAL, "capture rate %d S/s against %d S/s: need cap_fs / rf_fs = M / L with L <= %d, L < M <= %d, M <= 10 L",
                     cap_fs, rf_fs, kRateMaxUp, kRateMaxDown);
-    if (kind == 1) {  // an integer ratio: the existing stage's design
-        const int rc = fmrx_wide_design(rf_fs, m, offset_hz, coarse_hz, fine_hz, N, k, cos_sin, taps, h);
-        if (rc) return rc;
-        if (up) *up = 1;
-        if (down) *down = m;
-        return FMRX_OK;
-    }
-    int fc = 0, fr = 0, n = 0, kk = 0;
-    if (!rate_split(rf_fs, l, m, offset_hz, &fc, &fr, &n, &kk, nullptr))
-        return fail(FMRX_EINVAL, "offset %d Hz outside (-%d/2, %d/2)", offset_hz, cap_fs, cap_fs);
-    int tn = 0, tk = 0, rc;
-    if ((rc = fmrx_tuner_design(rf_fs, fr, &tn, &tk, nullptr))) return rc;  // the fine part goes to the tuner
+    // an integer ratio: fmrx_wide_design's range of the decimation and its wording of a refusal
+    int rc = kind == 1 ? fmrx_wide_design(rf_fs, m, offset_hz, coarse_hz, fine_hz, N, k, cos_sin, taps, h)
+                       : design_offset(rf_fs, l, m, offset_hz, coarse_hz, fine_hz, N, k, cos_sin, taps, h);
+    if (rc == kOffsetOutside) rc = fail(FMRX_EINVAL, "offset %d Hz outside (-%d/2, %d/2)", offset_hz, cap_fs, cap_fs);
+    if (rc) return rc;
     if (up) *up = l;
     if (down) *down = m;
-    if (coarse_hz) *coarse_hz = fc;
-    if (fine_hz) *fine_hz = fr;
-    if (N) *N = n;
-    if (k) *k = kk;
-    if (cos_sin) rate_split(rf_fs, l, m, offset_hz, nullptr, nullptr, nullptr, nullptr, cos_sin);
-    if (taps) *taps = rate_taps(m);
-    if (h) design_lpf(h, (float)rf_fs * (float)m, (float)(3.0 * rf_fs / 8.0), rate_taps(m), l);
     return FMRX_OK;
+}
+
+int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
+    CtxLock lock_(c);
+    if (!c) return fail(FMRX_EINVAL, "null context");
+    const int rc = check_capture_decim(decim, true);
+    if (rc) return rc;
+    if (decim == 1 && !c->ratio.on()) return FMRX_OK;  // the default: nothing anywhere changes
+    if (decim > 1 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
+        return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
+                    c->geo.rf_decim);
+    return set_capture_stage(c, 1, decim, 1);
 }
 
 int fmrx_set_capture_rate(fmrx_ctx* c, int cap_fs) {
@@ -514,7 +405,7 @@ int fmrx_set_capture_rate(fmrx_ctx* c, int cap_fs) {
     if (kind < 0)
         return fail(FMRX_EINVAL, "capture rate %d S/s against %d S/s: need cap_fs / rf_fs = M / L with L <= %d, L < M <= %d, M <= 10 L",
                     cap_fs, c->geo.rf_fs, kRateMaxUp, kRateMaxDown);
-    if (kind == 1) return fmrx_set_capture_decim(c, down);  // an integer ratio: the existing stage
+    if (kind == 1) return fmrx_set_capture_decim(c, down);  // an integer ratio: its range of the decimation
     if (!tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
         return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
                     c->geo.rf_decim);
@@ -523,43 +414,66 @@ int fmrx_set_capture_rate(fmrx_ctx* c, int cap_fs) {
     const size_t blocks = (size_t)up / std::gcd((size_t)up, ip), wide = blocks * ip / (size_t)up * (size_t)down;
     if (wide % 2 != 0 || wide < (size_t)rate_hist_pairs(up, down))
         return fail(FMRX_EINVAL, "capture rate %d S/s: a granule of %zu wide pairs is no whole number of staging units", cap_fs, wide);
-    int rc = set_device(c);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the wide state
-    const size_t ns = c->cfg.n_streams;
-    std::vector<float> h((size_t)rate_taps(down));
-    std::vector<RateTap> hp((size_t)up * rate_phase_stride(up, down));
-    design_lpf(h.data(), (float)c->geo.rf_fs * (float)down, (float)(3.0 * c->geo.rf_fs / 8.0), rate_taps(down), up);
-    rate_taps_by_phase(h.data(), up, down, hp.data());
-    if ((rc = c->d_wide_hist.ensure((size_t)rate_hist_pairs(up, down) * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(2 * hp.size())) ||
-        (rc = c->d_wide_tab.ensure(2 * (size_t)kRateMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
-        (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
-        return rc;
-    HIPCHK(hipMemcpy(c->d_wide_taps.p, hp.data(), sizeof(RateTap) * hp.size(), hipMemcpyHostToDevice));
-    c->wide_decim = 0;  // what fmrx_capture_decim reports at a rational rate
-    c->rate_up = up;
-    c->rate_down = down;
-    c->rate_cap_fs = cap_fs;
-    c->rate_blocks = blocks;
-    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
-    return reset_state(c);
+    return set_capture_stage(c, up, down, blocks);
+}
+
+int fmrx_capture_decim(const fmrx_ctx* c, int* decim) {
+    CtxLock lock_(c);
+    if (!c || !decim) return fail(FMRX_EINVAL, "null argument");
+    *decim = c->ratio.rational() ? 0 : c->ratio.down;  // D, 1 with no wide stage, 0 at a rational rate
+    return FMRX_OK;
 }
 
 int fmrx_capture_rate(const fmrx_ctx* c, int* cap_fs, int* up, int* down) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    if (cap_fs) *cap_fs = c->rate_up ? c->rate_cap_fs : c->wide_decim * c->geo.rf_fs;
-    if (up) *up = c->rate_up ? c->rate_up : 1;
-    if (down) *down = c->rate_up ? c->rate_down : c->wide_decim;
+    if (cap_fs) *cap_fs = c->ratio.cap_fs(c->geo.rf_fs);
+    if (up) *up = c->ratio.up;
+    if (down) *down = c->ratio.down;
     return FMRX_OK;
 }
 
 int fmrx_wide_granule(const fmrx_ctx* c, size_t* blocks, size_t* wide_pairs) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    const size_t b = c->rate_up ? c->rate_blocks : 1;
-    if (blocks) *blocks = b;
-    if (wide_pairs) *wide_pairs = wide_pairs_of(c, b);
+    if (blocks) *blocks = c->ratio.blocks;
+    if (wide_pairs) *wide_pairs = wide_pairs_of(c, c->ratio.blocks);
+    return FMRX_OK;
+}
+
+int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    CtxLock lock_(c);
+    if (!c || !offsets_hz) return fail(FMRX_EINVAL, "null argument");
+    const CaptureRatio& r = c->ratio;
+    if (!r.on()) return fail(FMRX_ESTATE, "fmrx_tune_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
+    if (first_pair % (uint64_t)r.down != 0) {
+        if (r.rational())
+            return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of %d (the rate is %d/%d of the mode's)",
+                        (unsigned long long)first_pair, r.down, r.down, r.up);
+        return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of the decimation %d",
+                    (unsigned long long)first_pair, r.down);
+    }
+    const size_t ns = c->cfg.n_streams;
+    std::vector<int32_t> fine(ns);
+    std::vector<WideStream> ws(ns);
+    std::vector<float> tab(2 * (size_t)kRateMaxN * ns, 0.0f);
+    int rc;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int fr = 0, n = 0, k = 0;
+        if ((rc = fmrx_rate_design(c->geo.rf_fs, r.cap_fs(c->geo.rf_fs), offsets_hz[s], nullptr, nullptr, nullptr, &fr, &n, &k,
+                                   tab.data() + 2 * kRateMaxN * s, nullptr, nullptr)))
+            return rc;
+        fine[s] = fr;
+        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
+    }
+    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
+    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
+    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
+    c->tune_pos = first_pair / (uint64_t)r.down * (uint64_t)r.up;
+    c->tuned = true;
+    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
+    c->wide_tuned = true;
     return FMRX_OK;
 }
 
@@ -567,8 +481,7 @@ int fmrx_wide_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* e
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
     if (offsets_hz) std::copy(c->wide_offsets.begin(), c->wide_offsets.end(), offsets_hz);
-    if (next_pair)
-        *next_pair = c->rate_up ? c->tune_pos / (uint64_t)c->rate_up * (uint64_t)c->rate_down : c->tune_pos * (uint64_t)c->wide_decim;
+    if (next_pair) *next_pair = c->tune_pos / (uint64_t)c->ratio.up * (uint64_t)c->ratio.down;
     if (enabled) *enabled = c->wide_tuned ? 1 : 0;
     return FMRX_OK;
 }

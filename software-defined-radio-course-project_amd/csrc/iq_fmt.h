@@ -1,6 +1,7 @@
-// iq_fmt.h — device helpers shared by the kernels that read raw I/Q (tuner.hip, wide.hip): the
+// iq_fmt.h — device helpers shared by the kernels that read raw I/Q (tuner.hip, wide.hip, rate.hip): the
 // formats' two-pair staging unit, the unit load from a virtual stream (halo ++ data ++ zeros), the
-// rotation of a unit against a (cos, sin) table and the single-wave LDS hand-off.
+// rotation of a unit against a (cos, sin) table, the rotator's phase steps and the single-wave LDS
+// hand-off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,6 +79,18 @@ __device__ inline typename IqFmt<F>::Raw load_unit(const uint8_t* in, const uint
     }
     return *reinterpret_cast<const Raw*>(halo + (halo_bytes + off));
 }
+// The same of a stream that may be read further back than its halo (zeros ++ halo ++ data ++ zeros)
+template <int F>
+__device__ inline typename IqFmt<F>::Raw load_unit_bounded(const uint8_t* in, const uint8_t* halo, long long off,
+                                                           long long total, long long halo_bytes) {
+    using Raw = typename IqFmt<F>::Raw;
+    if (off >= 0) {
+        if (off + (long long)sizeof(Raw) <= total) return *reinterpret_cast<const Raw*>(in + off);
+        return IqFmt<F>::zero();
+    }
+    if (off >= -halo_bytes) return *reinterpret_cast<const Raw*>(halo + (halo_bytes + off));
+    return IqFmt<F>::zero();
+}
 
 // The two pairs x0, x1 rotated by table entries a (first pair) and b: (I', Q', I', Q'), every
 // product and sum rounded separately (no FMA: -ffp-contract=off).
@@ -93,12 +106,44 @@ __device__ inline float4 rotate2(typename IqFmt<F>::Raw w, float2 a, float2 b) {
     IqFmt<F>::unpack(w, x0, x1);
     return rotate_pairs(x0, x1, a, b);
 }
+// The same with the integer formats normalised first (x = integer 2^-7 / 2^-15: exact): what the
+// capture stage's kernels stage, whose rows hold the samples themselves
+template <int F>
+__device__ inline float4 rotate_scaled(typename IqFmt<F>::Raw w, float2 a, float2 b) {
+    float2v x0, x1;
+    IqFmt<F>::unpack(w, x0, x1);
+    if constexpr (F != kIqF32) {
+        x0 = x0 * IqFmt<F>::SCALE;
+        x1 = x1 * IqFmt<F>::SCALE;
+    }
+    return rotate_pairs(x0, x1, a, b);
+}
 
 // a + b mod n for a, b < n
 __device__ inline uint32_t addmod(uint32_t a, uint32_t b, uint32_t n) {
     const uint32_t v = a + b;
     return v >= n ? v - n : v;
 }
+
+// The phases of a station's rotator (period N, step k: pair n of the stream takes table entry (k n) mod N)
+// as a workgroup of `threads` lanes meets them: it stages chunks of P pairs by unit loads, lane u of a
+// load holding pairs 2u, 2u + 1.  The steps are sums mod N from one 64-bit reduction of the call's
+// first pair; k n < 2^24.
+struct RotatorPhase {
+    uint32_t N, k, n0;
+    uint32_t tid;    // lane u's pairs 2u, 2u + 1 of a load
+    uint32_t ld;     // from one load to the next
+    uint32_t chunk;  // from one chunk to the next
+    __device__ RotatorPhase(uint32_t N_, uint32_t k_, unsigned long long first_pair, uint32_t lane, uint32_t threads, uint32_t P)
+        : N(N_), k(k_), n0((uint32_t)(first_pair % (unsigned long long)N_)),  // 64-bit reduction first
+          tid((2u * k_ * lane) % N_), ld((2u * k_ * threads) % N_), chunk((k_ * (P % N_)) % N_) {}
+    // phase of the pair `rel` pairs from the call's first one (rel < 0: in front of it)
+    __device__ uint32_t of(long long rel) const {
+        long long r = rel % (long long)N;
+        if (r < 0) r += (long long)N;
+        return (k * addmod(n0, (uint32_t)r, N)) % N;
+    }
+};
 
 // A single-wave workgroup's LDS hand-off (mono_fused.hip chunk_sync<64>): LDS instructions of one
 // wave execute in issue order; the fences keep the compiler from moving accesses across it.

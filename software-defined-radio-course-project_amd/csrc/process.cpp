@@ -10,7 +10,7 @@ using namespace fmrx;
 namespace {
 
 int check_wide_tuned(const fmrx_ctx* c, const char* who) {
-    if (c->wide_decim == 1 || !c->wide_tuned)
+    if (!c->ratio.on() || !c->wide_tuned)
         return fail(FMRX_ESTATE, "%s: wide tuning is off (fmrx_set_capture_decim, fmrx_tune_wide first)", who);
     return 0;
 }
@@ -138,7 +138,7 @@ int fmrx_process_wide_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, 
     if (n_blocks == 0) return FMRX_OK;
     if (reinterpret_cast<uintptr_t>(d_iq) % (2 * c->pair_bytes) != 0)
         return fail(FMRX_EINVAL, "wide calls need a %zu-byte aligned capture", 2 * c->pair_bytes);
-    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, wide_size_factor(c))) || (rc = set_device(c)))
+    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, c->ratio.size_factor())) || (rc = set_device(c)))
         return rc;
     return run_wide(c, d_iq, n_blocks, d_pcm);
 }
@@ -160,7 +160,7 @@ int fmrx_process_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* 
     if (rc) return rc;
     if (n_blocks == 0) return FMRX_OK;
     if ((rc = set_device(c))) return rc;
-    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, wide_size_factor(c)))) return rc;
+    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, c->ratio.size_factor()))) return rc;
     const size_t in_bytes = wide_pairs_of(c, n_blocks) * c->pair_bytes;
     const size_t out_n = (size_t)c->cfg.n_streams * n_blocks * c->geo.pcm_samples;
     return staged_call(c, iq, in_bytes, true, c->d_out, pcm, out_n, false, [&](const void* d_iq, int16_t* d_pcm, bool) {

@@ -25,13 +25,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <numeric>
 
 #include "dsp_device.h"
 #include "iq_fmt.h"
-#include "rate.h"
 #include "tuner.h"
+#include "wide.h"
 
 namespace fmrx {
 
@@ -42,32 +40,6 @@ constexpr int kNW = 4;                // waves a workgroup: they share the chunk
 constexpr int kNS = kNT * kNW;        // threads a workgroup
 constexpr int kR = 4;                 // phases side by side
 constexpr int kK = 4;                 // unit loads a lane in flight
-
-// One unit (two I/Q pairs) of the virtual stream (zeros ++ history ++ data ++ zeros) at byte offset
-// `off` (a multiple of the unit) from the call's first pair
-template <int F>
-__device__ inline typename IqFmt<F>::Raw rate_load_unit(const uint8_t* in, const uint8_t* hist, long long off,
-                                                        long long total, long long hist_bytes) {
-    using Raw = typename IqFmt<F>::Raw;
-    if (off >= 0) {
-        if (off + (long long)sizeof(Raw) <= total) return *reinterpret_cast<const Raw*>(in + off);
-        return IqFmt<F>::zero();
-    }
-    if (off >= -hist_bytes) return *reinterpret_cast<const Raw*>(hist + (hist_bytes + off));
-    return IqFmt<F>::zero();
-}
-
-// The two pairs of unit w, normalised and rotated by table entries a and b: (I', Q', I', Q')
-template <int F>
-__device__ inline float4 rate_rotate(typename IqFmt<F>::Raw w, float2 a, float2 b) {
-    float2v x0, x1;
-    IqFmt<F>::unpack(w, x0, x1);
-    if constexpr (F != kIqF32) {  // x = integer 2^-7 / 2^-15: exact
-        x0 = x0 * IqFmt<F>::SCALE;
-        x1 = x1 * IqFmt<F>::SCALE;
-    }
-    return rotate_pairs(x0, x1, a, b);
-}
 
 // R phases phi0 .. phi0 + R - 1 of the chunk in xb, each one sequential sum over its taps in ascending
 // k, the results to the hand-off rows.  The taps and where they read are wave-uniform loads.
@@ -101,7 +73,7 @@ __device__ inline void rate_phases(const float2* xb, float2* ob, const RateTap* 
 }
 
 template <int F>
-__global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateTap* __restrict__ hp) {
+__global__ void __launch_bounds__(kNS) rate_ddc_kernel(DdcLaunch A, const RateTap* __restrict__ hp) {
     using Fmt = IqFmt<F>;
     using Raw = typename Fmt::Raw;
     constexpr int PB = Fmt::PB;
@@ -134,16 +106,8 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
     const WideStream ws = A.streams[stream];
     const uint32_t N = ws.N, k = ws.k;
     for (uint32_t i = (uint32_t)tid; i < N; i += NS) rot[i] = A.tables[(size_t)stream * kRateMaxN + i];
-    const uint32_t n0 = (uint32_t)(A.first_pair % (unsigned long long)N);  // 64-bit reduction first
-    auto phase_of = [&](long long rel) -> uint32_t {  // pair `rel` pairs from the call's first one
-        long long r = rel % (long long)N;
-        if (r < 0) r += (long long)N;
-        return (k * addmod(n0, (uint32_t)r, N)) % N;
-    };
-    const uint32_t ph_tid = (2u * k * (uint32_t)tid) % N;   // lane u's pairs 2u, 2u + 1 of a load
-    const uint32_t ph_ld = (2u * k * (uint32_t)NS) % N;     // from one load to the next
-    const uint32_t ph_chunk = (k * ((uint32_t)P % N)) % N;  // from one chunk to the next
-    uint32_t pc = phase_of((long long)c0 * P);              // phase of chunk c's first pair
+    const RotatorPhase rp(N, k, A.first_pair, (uint32_t)tid, (uint32_t)NS, (uint32_t)P);
+    uint32_t pc = rp.of((long long)c0 * P);  // phase of chunk c's first pair
     __syncthreads();  // table staged
 
     // ---- prologue: the HC M pairs in front of chunk c0 to buffer pairs [0, HC M); whole units, so an
@@ -152,9 +116,9 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
         const int hp_pairs = HC * M, hpe = (hp_pairs + 1) & ~1, shift = hpe - hp_pairs;
         for (int j = tid; j < hpe / 2; j += NS) {
             const long long rel = (long long)c0 * P - hpe + 2 * j;
-            const Raw w = rate_load_unit<F>(in, hist, rel * PB, total, hb);
-            const uint32_t p0 = phase_of(rel);
-            const float4 r = rate_rotate<F>(w, rot[p0], rot[addmod(p0, k, N)]);
+            const Raw w = load_unit_bounded<F>(in, hist, rel * PB, total, hb);
+            const uint32_t p0 = rp.of(rel);
+            const float4 r = rotate_scaled<F>(w, rot[p0], rot[addmod(p0, k, N)]);
             const int b0 = 2 * j - shift, b1 = b0 + 1;
             if (b0 >= 0) xb[(b0 % M) * W + b0 / M] = make_float2(r.x, r.y);
             xb[(b1 % M) * W + b1 / M] = make_float2(r.z, r.w);
@@ -174,7 +138,7 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
         for (int t = 0; t < kK; t++) {
             const int u = tid + (l0 + t) * NS;
             pf[t] = Fmt::zero();
-            if (u < n_units) pf[t] = rate_load_unit<F>(in, hist, ((long long)c * P + 2 * u) * PB, total, hb);
+            if (u < n_units) pf[t] = load_unit_bounded<F>(in, hist, ((long long)c * P + 2 * u) * PB, total, hb);
         }
     };
     fetch(c0, 0);
@@ -193,7 +157,7 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
     for (int c = c0; c < c1; c++) {
         // ---- stage chunk c: rotate, to the polyphase rows behind the history columns
         {
-            uint32_t ph = addmod(pc, ph_tid, N);
+            uint32_t ph = addmod(pc, rp.tid, N);
             int row = row_t, col = HC + col_t;
             for (int l0 = 0; l0 < nld; l0 += kK) {
                 Raw cur[kK];
@@ -204,12 +168,12 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
                 for (int t = 0; t < kK; t++) {
                     const int u = tid + (l0 + t) * NS;
                     if (u < n_units) {
-                        const float4 r = rate_rotate<F>(cur[t], rot[ph], rot[addmod(ph, k, N)]);
+                        const float4 r = rotate_scaled<F>(cur[t], rot[ph], rot[addmod(ph, k, N)]);
                         xb[row * W + col] = make_float2(r.x, r.y);
                         const bool last = row + 1 == M;  // the second pair: the next row, or row 0 a column on
                         xb[last ? col + 1 : (row + 1) * W + col] = make_float2(r.z, r.w);
                     }
-                    ph = addmod(ph, ph_ld, N);
+                    ph = addmod(ph, rp.ld, N);
                     row += drow;
                     col += dcol;
                     if (row >= M) {
@@ -218,7 +182,7 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
                     }
                 }
             }
-            pc = addmod(pc, ph_chunk, N);
+            pc = addmod(pc, rp.chunk, N);
         }
         __syncthreads();  // (A) chunk c staged
         if (c + 1 < c1) fetch(c + 1, 0);
@@ -259,89 +223,20 @@ __global__ void __launch_bounds__(kNS) rate_ddc_kernel(RateLaunch A, const RateT
 }
 
 template <int F>
-int launch_one(const RateLaunch& A, int n_streams, hipStream_t s) {
+int launch_one(const DdcLaunch& A, int n_streams, hipStream_t s) {
     const size_t lds = rate_lds_bytes(A.up, A.down);
     // > 64 KiB of dynamic LDS for the largest ratios (set per call: per current device)
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rate_ddc_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)rate_lds_bytes(kRateMaxUp, kRateMaxDown)) != hipSuccess)
         return -2;
-    hipLaunchKernelGGL((rate_ddc_kernel<F>), dim3(n_streams * A.segs), dim3(kNS), lds, s, A, A.hp);
+    hipLaunchKernelGGL((rate_ddc_kernel<F>), dim3(n_streams * A.segs), dim3(kNS), lds, s, A,
+                       static_cast<const RateTap*>(A.taps));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 }  // namespace
 
-int rate_ratio(int rf_fs, int cap_fs, int* up, int* down) {
-    if (rf_fs <= 0 || rf_fs % 4 != 0 || cap_fs < rf_fs) return -1;
-    const int g = std::gcd(rf_fs, cap_fs);
-    const int l = rf_fs / g, m = cap_fs / g;
-    if (l == 1) {
-        if (up) *up = 1;
-        if (down) *down = m;
-        return 1;
-    }
-    if (l < kRateMinUp || l > kRateMaxUp || m <= l || m > kRateMaxDown || m > 10 * l) return -1;
-    if (up) *up = l;
-    if (down) *down = m;
-    return 0;
-}
-
-bool rate_split(int rf_fs, int up, int down, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k, float* cos_sin) {
-    const long long fs = rf_fs, f = offset_hz, a = f < 0 ? -f : f;
-    if (2 * a * up >= fs * down) return false;  // 2 |f| >= cap_fs
-    const long long qa = (8 * a + fs) / (2 * fs), q = f < 0 ? -qa : qa;
-    const long long fc = q * (fs / 4);
-    const long long g = std::gcd(qa * up, (long long)(4 * down));  // gcd(0, 4 M) = 4 M: N = 1, k = 0
-    const long long n = 4 * down / g;
-    const long long kk = ((q * up / g) % n + n) % n;
-    if (coarse_hz) *coarse_hz = (int)fc;
-    if (fine_hz) *fine_hz = (int)(f - fc);
-    if (N) *N = (int)n;
-    if (k) *k = (int)kk;
-    if (cos_sin) {
-        for (long long p = 0; p < n; p++) {  // the angle as (2 pi p) / N, one rounding each
-            const double ang = (2.0 * 3.14159265358979323846 * (double)p) / (double)n;
-            cos_sin[2 * p] = (float)std::cos(ang);
-            cos_sin[2 * p + 1] = (float)std::sin(ang);
-        }
-    }
-    return true;
-}
-
-void rate_taps_by_phase(const float* h, int up, int down, RateTap* tp) {
-    const int ts = rate_phase_stride(up, down), taps = rate_taps(down);
-    const int hc = rate_hist_cols(up), w = rate_row_cols(up);
-    for (int phi = 0; phi < up; phi++) {
-        const int e = phi * down / up, k0 = phi * down - e * up;
-        for (int i = 0; i < ts; i++) {
-            const int kk = k0 + up * i;
-            const int u = hc * down + e - i;  // >= 0 for every tap there is
-            tp[phi * ts + i] = kk < taps ? RateTap{h[kk], (int32_t)sizeof(float2) * ((u % down) * w + u / down)} : RateTap{0.0f, 0};
-        }
-    }
-}
-
-size_t rate_lds_bytes(int up, int down) {
-    return sizeof(float2) * ((size_t)kRateMaxN + (size_t)down * rate_row_cols(up) + (size_t)kNT * (up | 1));
-}
-
-int rate_segments(long long n_out, int up, int down, int n_streams, int cus) {
-    const long long cm = (long long)kNT * up;
-    const long long chunks = (n_out + cm - 1) / cm;
-    // resident workgroups a CU: 160 KiB of LDS, at most six waves a SIMD (80 registers)
-    const long long lds = (long long)rate_lds_bytes(up, down);
-    const long long target_wg = (long long)std::max(1, cus) * std::min<long long>(6, std::max<long long>(1, 160 * 1024 / lds));
-    // wide_segments' rule: one wave of workgroups, segments of at least four chunks, and a call too
-    // short to fill the grid even so takes one chunk a segment
-    if ((long long)n_streams * chunks <= target_wg) return (int)std::max<long long>(1, chunks);
-    long long segs = std::max<long long>(1, target_wg / std::max(1, n_streams));
-    segs = std::min(segs, std::max<long long>(1, chunks / 4));
-    return (int)segs;
-}
-
-int launch_rate_ddc(const RateLaunch& A, int n_streams, hipStream_t s) {
-    if (A.segs < 1 || n_streams < 1 || A.n_out < 1) return -1;
-    if (A.up < kRateMinUp || A.up > kRateMaxUp || A.down <= A.up || A.down > kRateMaxDown || A.down > 10 * A.up) return -1;
+int launch_rate_kernel(const DdcLaunch& A, int n_streams, hipStream_t s) {
     switch (A.format) {
         case kIqU8: return launch_one<kIqU8>(A, n_streams, s);
         case kIqS8: return launch_one<kIqS8>(A, n_streams, s);

@@ -87,9 +87,8 @@ namespace fmrx {
 
 size_t rds_granule_blocks(const fmrx_ctx* c) {
     const size_t per_window = (size_t)(kRdsbWin / kRdsbUp) * (size_t)(c->geo.bp_fs / 2000);  // mixer samples a window
-    size_t g = std::lcm((size_t)c->geo.if_samples, per_window) / (size_t)c->geo.if_samples;
-    if (c->rate_up) g = std::lcm(g, c->rate_blocks);
-    return g;
+    const size_t g = std::lcm((size_t)c->geo.if_samples, per_window) / (size_t)c->geo.if_samples;
+    return std::lcm(g, c->ratio.blocks);
 }
 
 int check_rds_blocks(const fmrx_ctx* c, size_t n_blocks) {

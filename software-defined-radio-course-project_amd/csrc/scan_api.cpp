@@ -134,12 +134,12 @@ fmrx_scan_config scan_config_of(const fmrx_scan_config* cfg_in) {
     return cfg_in ? *cfg_in : cfg;
 }
 
-// The detector of fmrx_scan_detect (decim = 1) and fmrx_scan_detect_wide (decim > 1: rf_fs is then the
-// capture's rate, and a candidate is checked by fmrx_wide_design instead of fmrx_tuner_design).  Host
-// arrays in and out: nothing here touches the GPU.  mode_fs > 0 (fmrx_scan_detect_rate): rf_fs is a
-// capture rate any ratio above the mode's rate mode_fs, and fmrx_rate_design checks a candidate.
-int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, const fmrx_scan_config& cfg, fmrx_station* out,
-                    int max_out, int* n_found, float* floor_db, int mode_fs = 0) {
+// The detector of fmrx_scan_detect, fmrx_scan_detect_wide and fmrx_scan_detect_rate on the spectrum of a
+// capture at rf_fs for a mode at mode_fs.  A candidate is one the receiver can tune to: at the mode's own
+// rate fmrx_tuner_design accepts it, at any other fmrx_rate_design does (an integer ratio: with
+// fmrx_wide_design's answer).  Host arrays in and out: nothing here touches the GPU.
+int scan_detect_run(const float* power, int fft_bins, int rf_fs, int mode_fs, const fmrx_scan_config& cfg, fmrx_station* out,
+                    int max_out, int* n_found, float* floor_db) {
     if (!power || !n_found || max_out < 0 || (max_out > 0 && !out)) return fail(FMRX_EINVAL, "bad argument");
     const int N = fft_bins;
     if (!scan_bins_ok(N))
@@ -167,9 +167,8 @@ int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, cons
         const long long f = org + m * ras;
         int tn = 0, tk = 0;
         // every reported offset can be tuned to
-        const int rc = mode_fs > 0 ? fmrx_rate_design(mode_fs, rf_fs, (int)f, nullptr, nullptr, nullptr, nullptr, &tn, &tk, nullptr, nullptr, nullptr)
-                       : decim == 1 ? fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr)
-                                  : fmrx_wide_design(rf_fs / decim, decim, (int)f, nullptr, nullptr, &tn, &tk, nullptr, nullptr, nullptr);
+        const int rc = mode_fs == rf_fs ? fmrx_tuner_design(rf_fs, (int)f, &tn, &tk, nullptr)
+                                        : fmrx_rate_design(mode_fs, rf_fs, (int)f, nullptr, nullptr, nullptr, nullptr, &tn, &tk, nullptr, nullptr, nullptr);
         if (rc) return rc;
         cands.push_back(Cand{f, 0.0, 0, 0.0});
     }
@@ -221,57 +220,59 @@ int scan_detect_run(const float* power, int fft_bins, int rf_fs, int decim, cons
 }
 
 // fmrx_scan and fmrx_scan_wide: spectrum + detect at the rate of the capture
-int scan_both(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int decim, const fmrx_scan_config* cfg_in, fmrx_station* out,
+int scan_both(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int fs, const fmrx_scan_config* cfg_in, fmrx_station* out,
               int max_out, int* n_found) {
     const fmrx_scan_config cfg = scan_config_of(cfg_in);
-    const int mode_fs = c->rate_up ? c->geo.rf_fs : 0;  // a rational rate: decim is 0
-    const int fs = c->rate_up ? c->rate_cap_fs : c->geo.rf_fs * decim;
+    const int mode_fs = c->geo.rf_fs;
     int rc = scan_check_size(cfg.fft_bins, n_pairs);
     if (rc) return rc;
     {  // refuse a bad detector configuration before any GPU work
         std::vector<float> flat((size_t)cfg.fft_bins, 1.0f);
         std::vector<fmrx_station> tmp((size_t)std::max(max_out, 0));
         int n = 0;
-        if ((rc = scan_detect_run(flat.data(), cfg.fft_bins, fs, decim, cfg, tmp.data(), max_out, &n, nullptr, mode_fs))) return rc;
+        if ((rc = scan_detect_run(flat.data(), cfg.fft_bins, fs, mode_fs, cfg, tmp.data(), max_out, &n, nullptr))) return rc;
     }
     std::vector<float> power((size_t)cfg.fft_bins);
     if ((rc = fmrx_scan_spectrum(c, iq, n_pairs, cfg.fft_bins, power.data(), nullptr))) return rc;
-    return scan_detect_run(power.data(), cfg.fft_bins, fs, decim, cfg, out, max_out, n_found, nullptr, mode_fs);
+    return scan_detect_run(power.data(), cfg.fft_bins, fs, mode_fs, cfg, out, max_out, n_found, nullptr);
 }
 }  // namespace
 
 int fmrx_scan_detect(const float* power, int fft_bins, int rf_fs, const fmrx_scan_config* cfg_in, fmrx_station* out,
                      int max_out, int* n_found, float* floor_db) {
-    return scan_detect_run(power, fft_bins, rf_fs, 1, scan_config_of(cfg_in), out, max_out, n_found, floor_db);
+    return scan_detect_run(power, fft_bins, rf_fs, rf_fs, scan_config_of(cfg_in), out, max_out, n_found, floor_db);
 }
 
 int fmrx_scan_detect_wide(const float* power, int fft_bins, int rf_fs, int decim, const fmrx_scan_config* cfg_in,
                           fmrx_station* out, int max_out, int* n_found, float* floor_db) {
     int rc = check_capture_decim(decim, false);
     if (rc || (rc = check_wide_rf_fs(rf_fs))) return rc;
-    return scan_detect_run(power, fft_bins, rf_fs * decim, decim, scan_config_of(cfg_in), out, max_out, n_found, floor_db);
+    return scan_detect_run(power, fft_bins, rf_fs * decim, rf_fs, scan_config_of(cfg_in), out, max_out, n_found, floor_db);
 }
 
 int fmrx_scan_detect_rate(const float* power, int fft_bins, int rf_fs, int cap_fs, const fmrx_scan_config* cfg_in,
                           fmrx_station* out, int max_out, int* n_found, float* floor_db) {
     int rc = fmrx_rate_design(rf_fs, cap_fs, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;  // the rate itself
-    return scan_detect_run(power, fft_bins, cap_fs, 0, scan_config_of(cfg_in), out, max_out, n_found, floor_db, rf_fs);
+    return scan_detect_run(power, fft_bins, cap_fs, rf_fs, scan_config_of(cfg_in), out, max_out, n_found, floor_db);
 }
 
 int fmrx_scan_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
                    int max_out, int* n_found) {
     CtxLock lock_(c);
     if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
-    if (c->wide_decim == 1) return fail(FMRX_ESTATE, "fmrx_scan_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
-    return scan_both(c, iq, n_pairs, c->wide_decim, cfg_in, out, max_out, n_found);
+    if (!c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_scan_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
+    return scan_both(c, iq, n_pairs, c->ratio.cap_fs(c->geo.rf_fs), cfg_in, out, max_out, n_found);
 }
 
 int fmrx_scan(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
               int max_out, int* n_found) {
     CtxLock lock_(c);
     if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
-    return scan_both(c, iq, n_pairs, 1, cfg_in, out, max_out, n_found);
+    // kept as it was: on a context at a rational rate this call has always scanned at the capture's rate,
+    // as fmrx_scan_wide does, and at rf_fs on every other (fmrx.h promises rf_fs throughout)
+    const int fs = c->ratio.rational() ? c->ratio.cap_fs(c->geo.rf_fs) : c->geo.rf_fs;
+    return scan_both(c, iq, n_pairs, fs, cfg_in, out, max_out, n_found);
 }
 
 }  // extern "C"

@@ -114,24 +114,15 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
     const TunerStream ts = L.streams[stream];
     const uint32_t N = ts.N, k = ts.k;
     for (uint32_t i = tid; i < N; i += NT) rot[i] = L.tables[(size_t)ts.tab + i];
-    const uint32_t n0 = (uint32_t)(L.first_pair % (unsigned long long)N);  // 64-bit reduction first
-    // phase of the pair `rel` pairs from the call's first one (rel < 0: in the halo); k n < 2^24
-    auto phase_of = [&](long long rel) -> uint32_t {
-        long long r = rel % (long long)N;
-        if (r < 0) r += (long long)N;
-        return (k * addmod(n0, (uint32_t)r, N)) % N;
-    };
-    const uint32_t ph_tid = (2u * k * (uint32_t)tid) % N;   // lane u's pairs 2u, 2u + 1 of a load
-    const uint32_t ph_ld = (2u * k * (uint32_t)NT) % N;     // from one load to the next
-    const uint32_t ph_chunk = (k * ((uint32_t)P % N)) % N;  // from one chunk to the next
-    uint32_t pc = phase_of((long long)(c0 - 1) * P);        // phase of chunk c's first pair
+    const RotatorPhase rp(N, k, L.first_pair, (uint32_t)tid, (uint32_t)NT, (uint32_t)P);
+    uint32_t pc = rp.of((long long)(c0 - 1) * P);  // phase of chunk c's first pair
     wave_sync();  // table staged
 
     // ---- prologue: RF history in front of the pre-roll chunk (pairs [(c0-1)P - H, (c0-1)P))
     for (int i = tid; i < H / 2; i += NT) {
         const long long rel = (long long)(c0 - 1) * P - H + 2 * i;
         const Raw w = load_unit<F>(in, halo, rel * PB, total, hb);
-        const uint32_t p0 = phase_of(rel);
+        const uint32_t p0 = rp.of(rel);
         xb4[C::slot(2 * i) / 2] = rotate2<F>(w, rot[p0], rot[addmod(p0, k, N)]);
     }
     // Input prefetch, one chunk ahead: always the same coalesced unit loads, from a base clamped
@@ -159,16 +150,16 @@ __global__ void __launch_bounds__(kNT) tuner_kernel(TunerLaunch L, MonoTaps taps
             for (int l = 0; l < NLD; l++)
                 pf[l] = load_unit<F>(in, halo, (long long)c * (PB * P) + (long long)sizeof(Raw) * (tid + l * NT), total, hb);
         }
-        uint32_t ph = addmod(pc, ph_tid, N);
+        uint32_t ph = addmod(pc, rp.tid, N);
 #pragma unroll
         for (int l = 0; l < NLD; l++) {
             const int u = tid + l * NT;
             const float4 f = rotate2<F>(pf[l], rot[ph], rot[addmod(ph, k, N)]);
-            ph = addmod(ph, ph_ld, N);
+            ph = addmod(ph, rp.ld, N);
             xb4[C::slot(H + 2 * u) / 2] = f;
             if (l >= C::LH0) hist[l - C::LH0] = f;  // the chunk's last H pairs: next chunk's history
         }
-        pc = addmod(pc, ph_chunk, N);
+        pc = addmod(pc, rp.chunk, N);
         wave_sync();  // (A) chunk c staged
         if (c + 1 < c1) fetch(c + 1);
 

@@ -4,7 +4,7 @@
 // the offset.  Every station reads the ONE capture.
 //
 // Arithmetic (the contract the tests check bit for bit).  An offset f splits into
-// f_c = q rf_fs / 4 and f_r = f - f_c (wide_split below).  With N = 4 D / gcd(|q|, 4 D),
+// f_c = q rf_fs / 4 and f_r = f - f_c (rate_split at up = 1, wide_design.cpp).  With N = 4 D / gcd(|q|, 4 D),
 // k = (q / gcd) mod N, the table c[p] = (float)cos(2 pi p / N), s[p] = (float)sin(2 pi p / N) and
 // p = (k n) mod N, wide pair n (absolute index) with the format's normalised samples x_i, x_q becomes
 //   I' = fl(fl(x_i c[p]) + fl(x_q s[p])),  Q' = fl(fl(x_q c[p]) - fl(x_i s[p]))
@@ -23,10 +23,6 @@
 // its history from the raw pairs in front of it (the capture, or the context's history of the
 // previous call), and a phase is a function of the absolute index alone, so there is no carried state.
 #include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <numeric>
 
 #include "dsp_device.h"
 #include "iq_fmt.h"
@@ -51,18 +47,13 @@ struct WideCfg {
     static constexpr int NLD = (P / 2) / kNT; // unit (2-pair) loads per lane and chunk
     static constexpr int NGRP = (T + kG - 1) / kG;  // tap groups
     static_assert((P / 2) % kNT == 0, "whole loads per chunk");
+    static_assert(CM == kWideChunk, "wide_segments counts chunks of kWideChunk outputs");
 };
 
 // The two pairs of unit w, normalised and rotated by table entries a and b, to buffer pairs b0, b0 + 1
 template <int D, int F>
 __device__ inline void stage_unit(float2* xb, int b0, typename IqFmt<F>::Raw w, float2 a, float2 b) {
-    float2v x0, x1;
-    IqFmt<F>::unpack(w, x0, x1);
-    if constexpr (F != kIqF32) {  // x = integer 2^-7 / 2^-15: exact
-        x0 = x0 * IqFmt<F>::SCALE;
-        x1 = x1 * IqFmt<F>::SCALE;
-    }
-    const float4 r = rotate_pairs(x0, x1, a, b);
+    const float4 r = rotate_scaled<F>(w, a, b);
     constexpr int W = WideCfg<D>::W;
     const int b1 = b0 + 1;
     xb[(b0 % D) * W + b0 / D] = make_float2(r.x, r.y);
@@ -70,7 +61,7 @@ __device__ inline void stage_unit(float2* xb, int b0, typename IqFmt<F>::Raw w, 
 }
 
 template <int D, int F>
-__global__ void __launch_bounds__(kNT) wide_ddc_kernel(WideLaunch L, const float* __restrict__ h) {
+__global__ void __launch_bounds__(kNT) wide_ddc_kernel(DdcLaunch L, const float* __restrict__ h) {
     using C = WideCfg<D>;
     using Fmt = IqFmt<F>;
     using Raw = typename Fmt::Raw;
@@ -98,24 +89,16 @@ __global__ void __launch_bounds__(kNT) wide_ddc_kernel(WideLaunch L, const float
     // ---- the station's rotator: table to LDS, phases of this workgroup's first pairs
     const WideStream ws = L.streams[stream];
     const uint32_t N = ws.N, k = ws.k;  // N <= kWideMaxN < NT
-    if ((uint32_t)tid < N) rot[tid] = L.tables[(size_t)stream * kWideMaxN + tid];
-    const uint32_t n0 = (uint32_t)(L.first_pair % (unsigned long long)N);  // 64-bit reduction first
-    auto phase_of = [&](long long rel) -> uint32_t {  // pair `rel` pairs from the call's first one
-        long long r = rel % (long long)N;
-        if (r < 0) r += (long long)N;
-        return (k * addmod(n0, (uint32_t)r, N)) % N;
-    };
-    const uint32_t ph_tid = (2u * k * (uint32_t)tid) % N;   // lane u's pairs 2u, 2u + 1 of a load
-    const uint32_t ph_ld = (2u * k * (uint32_t)NT) % N;     // from one load to the next
-    const uint32_t ph_chunk = (k * ((uint32_t)P % N)) % N;  // from one chunk to the next
-    uint32_t pc = phase_of((long long)c0 * P);              // phase of chunk c's first pair
+    if ((uint32_t)tid < N) rot[tid] = L.tables[(size_t)stream * kRateMaxN + tid];
+    const RotatorPhase rp(N, k, L.first_pair, (uint32_t)tid, (uint32_t)NT, (uint32_t)P);
+    uint32_t pc = rp.of((long long)c0 * P);  // phase of chunk c's first pair
     wave_sync();  // table staged
 
     // ---- prologue: the history in front of chunk c0 (pairs [c0 P - H, c0 P)) to buffer pairs [0, H)
     for (int i = tid; i < H / 2; i += NT) {
         const long long rel = (long long)c0 * P - H + 2 * i;
         const Raw w = load_unit<F>(in, hist, rel * PB, total, hb);
-        const uint32_t p0 = phase_of(rel);
+        const uint32_t p0 = rp.of(rel);
         stage_unit<D, F>(xb, 2 * i, w, rot[p0], rot[addmod(p0, k, N)]);
     }
     // Input prefetch, one chunk ahead: always the same coalesced unit loads, from a base clamped
@@ -139,14 +122,14 @@ __global__ void __launch_bounds__(kNT) wide_ddc_kernel(WideLaunch L, const float
             for (int l = 0; l < NLD; l++)
                 pf[l] = load_unit<F>(in, hist, (long long)c * (PB * P) + (long long)sizeof(Raw) * (tid + l * NT), total, hb);
         }
-        uint32_t ph = addmod(pc, ph_tid, N);
+        uint32_t ph = addmod(pc, rp.tid, N);
 #pragma unroll
         for (int l = 0; l < NLD; l++) {
             const int u = tid + l * NT;
             stage_unit<D, F>(xb, H + 2 * u, pf[l], rot[ph], rot[addmod(ph, k, N)]);
-            ph = addmod(ph, ph_ld, N);
+            ph = addmod(ph, rp.ld, N);
         }
-        pc = addmod(pc, ph_chunk, N);
+        pc = addmod(pc, rp.chunk, N);
         wave_sync();  // (A) chunk c staged
         if (c + 1 < c1) fetch(c + 1);
 
@@ -212,13 +195,14 @@ __global__ void __launch_bounds__(kNT) wide_ddc_kernel(WideLaunch L, const float
 }
 
 template <int D, int F>
-int launch_one(const WideLaunch& L, int n_streams, hipStream_t s) {
-    hipLaunchKernelGGL((wide_ddc_kernel<D, F>), dim3(n_streams * L.segs), dim3(kNT), 0, s, L, L.h);
+int launch_one(const DdcLaunch& L, int n_streams, hipStream_t s) {
+    hipLaunchKernelGGL((wide_ddc_kernel<D, F>), dim3(n_streams * L.segs), dim3(kNT), 0, s, L,
+                       static_cast<const float*>(L.taps));
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 template <int D>
-int launch_decim(const WideLaunch& L, int n_streams, hipStream_t s) {
+int launch_decim(const DdcLaunch& L, int n_streams, hipStream_t s) {
     switch (L.format) {
         case kIqU8: return launch_one<D, kIqU8>(L, n_streams, s);
         case kIqS8: return launch_one<D, kIqS8>(L, n_streams, s);
@@ -230,46 +214,8 @@ int launch_decim(const WideLaunch& L, int n_streams, hipStream_t s) {
 
 }  // namespace
 
-bool wide_split(int rf_fs, int decim, int offset_hz, int* coarse_hz, int* fine_hz, int* N, int* k, float* cos_sin) {
-    if (decim < kWideMinDecim || decim > kWideMaxDecim || rf_fs <= 0 || rf_fs % 4 != 0) return false;
-    const long long fs = rf_fs, f = offset_hz, a = f < 0 ? -f : f;
-    if (2 * a >= fs * decim) return false;
-    const long long qa = (8 * a + fs) / (2 * fs), q = f < 0 ? -qa : qa;
-    const long long fc = q * (fs / 4);
-    const long long g = std::gcd(qa, (long long)(4 * decim));  // gcd(0, 4 D) = 4 D: N = 1, k = 0
-    const long long n = 4 * decim / g;
-    const long long kk = ((q / g) % n + n) % n;
-    if (coarse_hz) *coarse_hz = (int)fc;
-    if (fine_hz) *fine_hz = (int)(f - fc);
-    if (N) *N = (int)n;
-    if (k) *k = (int)kk;
-    if (cos_sin) {
-        for (long long p = 0; p < n; p++) {  // the angle as (2 pi p) / N, one rounding each
-            const double ang = (2.0 * 3.14159265358979323846 * (double)p) / (double)n;
-            cos_sin[2 * p] = (float)std::cos(ang);
-            cos_sin[2 * p + 1] = (float)std::sin(ang);
-        }
-    }
-    return true;
-}
-
-int wide_segments(long long n_out, int decim, int n_streams, int cus) {
-    const long long cm = (long long)kNT * kR;
-    const long long chunks = (n_out + cm - 1) / cm;
-    // resident workgroups a CU: 160 KiB of LDS, at most two waves a SIMD
-    const int lds = 8 * (decim * (16 + (int)cm + 1) + kWideMaxN);
-    const long long target_wg = (long long)std::max(1, cus) * std::min(8, std::max(1, 160 * 1024 / lds));
-    // tuner_segments' rule: one wave of workgroups, segments of at least four chunks, and a call
-    // too short to fill the grid even so takes one chunk a segment
-    if ((long long)n_streams * chunks <= target_wg) return (int)std::max<long long>(1, chunks);
-    long long segs = std::max<long long>(1, target_wg / std::max(1, n_streams));
-    segs = std::min(segs, std::max<long long>(1, chunks / 4));
-    return (int)segs;
-}
-
-int launch_wide_ddc(const WideLaunch& L, int n_streams, int decim, hipStream_t s) {
-    if (L.segs < 1 || n_streams < 1) return -1;
-    switch (decim) {
+int launch_decim_kernel(const DdcLaunch& L, int n_streams, hipStream_t s) {
+    switch (L.down) {
         case 2: return launch_decim<2>(L, n_streams, s);
         case 3: return launch_decim<3>(L, n_streams, s);
         case 4: return launch_decim<4>(L, n_streams, s);

@@ -305,6 +305,42 @@ def test_integer_rate_is_the_decimating_stage(fmrx):
     assert np.array_equal(got, want) and np.array_equal(got, wide_compose(raw, U8, 0, 51, d, f)["pcm_mono"]) and got.any()
 
 
+def test_one_context_walks_integer_rational_integer(fmrx):
+    """One context through D = 2, then 6/25, then D = 10: the stage's buffers are shared, the tap buffer
+    holds floats in the integer states and taps by phase in the rational one, and the rational table of
+    q = 1 (N_c = 50) is longer than any integer one (at most 40).  Every step is one call of one granule,
+    bit for bit the composition of its own state."""
+    rf_fs, be = oracle.MODES[0][3], oracle.MODES[0][0]
+    cap_fs = 10000000
+    with fmrx.Receiver(0, fmrx.MONO) as rx:
+        f = rf_fs // 4 + 7000  # q = 1: N_c = 8
+        assert fmrx.wide_design(rf_fs, 2, f)["N"] == 8
+        raw = iqgen.make("synth:86", 2 * be, rf_fs)
+        rx.set_capture_decim(2)
+        assert rx.wide_info()[2] is False
+        rx.tune_wide(f)
+        got = rx.process_wide(raw)
+        assert np.array_equal(got, wide_compose(raw, U8, 0, 51, 2, f)["pcm_mono"]) and got.any()
+
+        f = rf_fs // 4  # q = 1: N_c = 50
+        assert fmrx.rate_design(rf_fs, cap_fs, f)["N"] == 50
+        raw = capture(87, 0, cap_fs, 1)
+        rx.set_capture_rate(cap_fs)
+        assert rx.wide_info()[2] is False and rx.capture_rate == (cap_fs, 6, 25) and rx.wide_granule[0] == 3
+        rx.tune_wide(f)
+        got = rx.process_wide(raw)
+        assert np.array_equal(got, rate_compose(raw, U8, 0, 51, cap_fs, f)["pcm_mono"]) and got.any()
+
+        f = rf_fs // 4 - 30000  # q = 1: N_c = 40
+        assert fmrx.wide_design(rf_fs, 10, f)["N"] == 40
+        raw = iqgen.make("synth:88", 10 * be, rf_fs)
+        rx.set_capture_decim(10)
+        assert rx.wide_info()[2] is False and rx.capture_decim == 10
+        rx.tune_wide(f)
+        got = rx.process_wide(raw)
+        assert np.array_equal(got, wide_compose(raw, U8, 0, 51, 10, f)["pcm_mono"]) and got.any()
+
+
 # ---- scan and decode ------------------------------------------------------------------------------------------
 
 def test_scan_and_decode_stations(fmrx):

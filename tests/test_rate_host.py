@@ -42,6 +42,51 @@ def test_reduction(fmrx, rf_fs, cap_fs, up, down):
         assert d["h"].shape == (16 * down + 1,) and d["table"].tolist() == [[1.0, 0.0]]
 
 
+def test_integer_design_is_the_rational_design_at_up_1(fmrx):
+    """fmrx_rate_design(rf_fs, D rf_fs, f) against fmrx_wide_design(rf_fs, D, f) for every D, the modes'
+    three rates and every f on a 25 kHz raster inside (-cap_fs / 2, cap_fs / 2), with the edges +-cap_fs / 2
+    and +-(cap_fs / 2 - 1): the same code; accepted, the same 1 / D, split, period, step, table and taps;
+    refused, no output written by either.  The taps depend on (rf_fs, D) alone: compared once each."""
+    lib = fmrx.lib()
+    accepted = refused = 0
+    for rf_fs in sorted({m[3] for m in oracle.MODES.values()}):
+        for d in range(2, 11):
+            cap_fs, half = d * rf_fs, d * rf_fs // 2
+            raster = range(-((half - 1) // 25000) * 25000, half, 25000)
+            first = True
+            for f in [-half, -(half - 1), *raster, half - 1, half]:
+                rv, wv = [C.c_int(-7) for _ in range(7)], [C.c_int(-7) for _ in range(5)]
+                rt, wt = np.full(80, 9.0, np.float32), np.full(80, 9.0, np.float32)
+                rh = wh = None
+                if first and abs(f) < half - 1:  # the first offset on the raster: also the taps
+                    rh, wh = np.full(16 * d + 1, 9.0, np.float32), np.full(16 * d + 1, 9.0, np.float32)
+                r = [C.byref(v) for v in rv]
+                w = [C.byref(v) for v in wv]
+                rc_r = lib.fmrx_rate_design(rf_fs, cap_fs, f, r[0], r[1], r[2], r[3], r[4], r[5], rt.ctypes.data, r[6],
+                                            None if rh is None else rh.ctypes.data)
+                rc_w = lib.fmrx_wide_design(rf_fs, d, f, w[0], w[1], w[2], w[3], wt.ctypes.data, w[4],
+                                            None if wh is None else wh.ctypes.data)
+                assert rc_r == rc_w, (rf_fs, d, f)
+                got_r, got_w = [v.value for v in rv], [v.value for v in wv]
+                if rc_r != fmrx.FMRX_OK:
+                    assert rc_r == fmrx.FMRX_EINVAL and got_r == [-7] * 7 and got_w == [-7] * 5, (rf_fs, d, f)
+                    assert np.all(rt == 9.0) and np.all(wt == 9.0), (rf_fs, d, f)
+                    assert rh is None or (np.all(rh == 9.0) and np.all(wh == 9.0)), (rf_fs, d, f)
+                    refused += 1
+                    continue
+                assert got_r[:2] == [1, d] and got_r[2:] == got_w, (rf_fs, d, f)
+                n = got_r[4]
+                assert 1 <= n <= 40 and got_r[6] == 16 * d + 1, (rf_fs, d, f)
+                assert np.array_equal(rt.view(np.uint32), wt.view(np.uint32)) and np.all(rt[2 * n:] == 9.0), (rf_fs, d, f)
+                if rh is not None:
+                    assert np.array_equal(rh.view(np.uint32), wh.view(np.uint32)) and np.all(rh != 9.0)
+                    first = False
+                accepted += 1
+            assert not first, (rf_fs, d)
+    print(f"{accepted} offsets accepted, {refused} refused by both")
+    assert accepted > 1000 and refused >= 4 * 9 * 3  # the four edges of every (rf_fs, D) are refused
+
+
 @pytest.mark.parametrize("rf_fs,cap_fs,f", [
     (2400000, 2400000, 0),        # D = 1: no wide stage to design
     (2400000, 2000000, 0),        # cap_fs < rf_fs
