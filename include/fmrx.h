@@ -371,6 +371,61 @@ int fmrx_deemph_design(int audio_fs, int tau_us, float* h64);
 int fmrx_set_deemphasis(fmrx_ctx* ctx, int tau_us);
 int fmrx_deemphasis(const fmrx_ctx* ctx, int* tau_us);
 
+/* ---- subcarrier meter: is there a 19 kHz pilot, is there a 57 kHz RDS subcarrier ------------------- */
+/* No counterpart in the reference, which runs the pilot PLL on every stream (src/project.cpp:166).  The
+ * meter says, per stream, whether the expensive stages have anything to lock to (csrc/meter.hip, DESIGN.md
+ * §5.12).  It is stateless and defined exactly, so the GPU is checked without a tolerance.  Per stream on
+ * the demod row d[n] at bp_fs: P = bp_fs / 1000 samples are a 1 ms window (240, 288, 240, 256 in modes
+ * 0..3), 64 windows a frame (64 ms, the RDS window); a frame depends on its own 64 P samples alone.  Seven
+ * tones at k kHz, k = 17, 19, 21, 56, 58, 61, 63 in that order: the pilot with the guard band either side
+ * of it, the two sides of the RDS carrier (biphase RDS has a null at 57 kHz itself) and two bins above its
+ * skirt.  fmrx_meter_design is host only, like fmrx_deemph_design; in double, then rounded to float:
+ *   w[n] = 0.5 - 0.5 cos(2 pi n / P)                       (Hann: the pilot is an exact zero of 17 and 21)
+ *   c_k[n] = (float)(w[n] cos(2 pi ((k n) mod P) / P)),  s_k[n] = (float)(w[n] sin(2 pi ((k n) mod P) / P))
+ * tables: 7 x 2 x P floats, tone-major, c then s (may be NULL); *P may be NULL.  FMRX_EINVAL, nothing
+ * written: bp_fs no positive multiple of 16000, or P > 288.
+ * Per window and tone, x = d[window start + n]: sixteen partial sums a_j = fl(a_j + fl(x[16 i + j] c_k[16 i
+ * + j])) from 0, i ascending over 0 .. P/16 - 1 (products and sums rounded separately, no FMA:
+ * fmrx_resample's convention), folded by stride halving, a_j = fl(a_j + a_{j+s}) for j < s, s = 8, 4, 2, 1;
+ * re = a_0, im the same with s_k, p = fl(fl(re re) + fl(im im)).  Per frame and tone the 64 window powers are
+ * folded by the same tree (s = 32 .. 1).  power: n_streams x F x 7 floats, F the frames of the call.  NaN
+ * and Inf in the input follow IEEE arithmetic and never fault.
+ * A call takes whole frames: n_blocks a multiple of fmrx_rds_granule's blocks (24, 24, 3, 1; with a capture
+ * rate set the least common multiple with fmrx_wide_granule's), else FMRX_EINVAL and nothing runs.         */
+#define FMRX_METER_TONES 7
+int fmrx_meter_design(int bp_fs, int* P, float* tables /* 14 P floats, may be NULL */);
+/* the primitive: demod rows as fmrx_rf_block returns them, whole frames; power: n_streams x F x 7 */
+int fmrx_meter(fmrx_ctx* ctx, const float* demod, size_t n_blocks, float* power);
+int fmrx_meter_device(fmrx_ctx* ctx, const float* d_demod, size_t n_blocks,
+                      float* d_power);             /* async on the context stream */
+/* The decision, host only, no context, everything in double.  sum[t]: the sequential ascending sum, over
+ * the frames in stream order, of the float powers widened to double (any split of a stream into calls
+ * gives the same bits).  With S19 = max(sum[19], 1e-30), R = (sum[56] + sum[58]) / 2:
+ *   pilot_snr_db = 10 log10(S19 / max((sum[17] + sum[21]) / 2, 1e-30)),  pilot_db = 10 log10(S19 / (64 frames))
+ *   rds_snr_db = 10 log10(max(R, 1e-30) / max((sum[61] + sum[63]) / 2, 1e-30)),  rds_db = 10 log10(max(R, 1e-30) / (64 frames))
+ *   stereo = pilot_snr_db >= cfg.pilot_min_snr_db,  rds = rds_snr_db >= cfg.rds_min_snr_db
+ * (defaults 10 dB and 1.94 dB, DESIGN.md §5.12 has the measured classes either side; cfg = NULL: the
+ * defaults).  FMRX_EINVAL: a null report or out, frames == 0.                                              */
+typedef struct { double sum[FMRX_METER_TONES]; uint64_t frames; } fmrx_meter_report;
+typedef struct { float pilot_min_snr_db, rds_min_snr_db; } fmrx_meter_config;
+typedef struct { float pilot_db, pilot_snr_db, rds_db, rds_snr_db;
+                 int stereo, rds; } fmrx_subcarriers;
+int fmrx_meter_config_default(fmrx_meter_config* cfg);
+int fmrx_meter_accumulate(fmrx_meter_report* io, const float* power,
+                          size_t frames);          /* host only: frames x 7 floats of one stream */
+int fmrx_meter_detect(const fmrx_meter_report* report, const fmrx_meter_config* cfg,
+                      fmrx_subcarriers* out);
+/* on != 0: the calls whose front end writes demod rows (tuned fmrx_process / _device / _device_ex,
+ * fmrx_process_shared / _device, fmrx_process_wide / _device) also run the meter over those rows, on the
+ * context stream in front of the audio stage, copy the F x 7 floats a stream back and add them to the
+ * stream's report once the call's work is enqueued (a host synchronisation, as with fmrx_set_rds).  Such a
+ * call must be whole frames (FMRX_EINVAL and nothing runs otherwise).  The PCM is the same bits either
+ * way.  fmrx_reset clears the reports and keeps the switch; the reports are not in the fmrx_get_state blob
+ * (the meter holds no signal state).  Off (the default): no call launches, allocates or copies anything
+ * more.  The untuned fused u8 path writes no demod rows and is never metered.                             */
+int fmrx_set_meter(fmrx_ctx* ctx, int on);
+int fmrx_meter_get(const fmrx_ctx* ctx, int stream, fmrx_meter_report* out);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

@@ -1,6 +1,6 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
 // [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]
-// [--capture-rate HZ] [--rds] [--deemph 50|75]`:
+// [--capture-rate HZ] [--rds] [--deemph 50|75] [--meter]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -37,6 +37,10 @@
 //   * --deemph 50|75 (an fmrx extension) de-emphasises the PCM with that time constant in microseconds
 //     (fmrx_set_deemphasis: 50 in most of the world, 75 in the Americas and Korea), whatever else is
 //     chosen; without it the audio is as broadcast, as project's is.  Any other value: message, exit 1.
+//   * --meter (an fmrx extension) also measures the station's 19 kHz pilot and 57 kHz RDS subcarrier
+//     (fmrx_set_meter): batches of whole frames and the tuned front end as with --rds, and at end of input
+//     one line goes to stderr, `meter pilot_snr=%.1f stereo=%d rds_snr=%.1f rds=%d frames=%llu`.  stdout is
+//     unchanged: blocks past the last whole frame are decoded without the meter.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -107,6 +111,7 @@ void usage(const char* argv0) {
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
                  "                [--deemph 50|75]  de-emphasise the audio (time constant in us; default: none)\n"
+                 "                [--meter]  measure the pilot and the RDS subcarrier; at end of input print their levels to stderr\n"
                  "                [--rds]  decode the station's RDS too; at end of input print its PI, PTY and name to stderr\n"
                  "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
                  "                [--capture-decim D]  stdin runs at D (2..10) times the mode's rate; --offset-hz and\n"
@@ -163,7 +168,7 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
 
 int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false, tuned = false, scan = false, rds = false;
+    bool mono_product = false, tuned = false, scan = false, rds = false, meter = false;
     long offset_hz = 0;
     int iq_format = FMRX_IQ_U8, capture_decim = 1, deemph_us = 0;
     long capture_rate = 0;
@@ -178,6 +183,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
         else if (!std::strcmp(argv[i], "--scan")) scan = true;
         else if (!std::strcmp(argv[i], "--rds")) rds = true;
+        else if (!std::strcmp(argv[i], "--meter")) meter = true;
         else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
         else if (!std::strcmp(argv[i], "--iq-format") && i + 1 < argc) {
             const char* f = argv[++i];
@@ -294,17 +300,18 @@ int main(int argc, char** argv) {
         fmrx_destroy(ctx);
         return 1;
     }
-    // --rds: whole RDS granules a batch (rounded up), decoded by the tuned front end
+    // --rds, --meter: whole RDS granules (the meter's frames) a batch (rounded up), decoded by the tuned front end
     size_t rds_unit = unit_blocks;
-    if (rds) {
-        if (fmrx_rds_granule(ctx, &rds_unit) != FMRX_OK || fmrx_set_rds(ctx, 1) != FMRX_OK) {
-            std::fprintf(stderr, "fmrx: --rds: %s\n", fmrx_last_error());
+    if (rds || meter) {
+        if (fmrx_rds_granule(ctx, &rds_unit) != FMRX_OK || (rds && fmrx_set_rds(ctx, 1) != FMRX_OK) ||
+            (meter && fmrx_set_meter(ctx, 1) != FMRX_OK)) {
+            std::fprintf(stderr, "fmrx: %s: %s\n", rds ? "--rds" : "--meter", fmrx_last_error());
             fmrx_destroy(ctx);
             return 1;
         }
         batch = (int)(((size_t)batch + rds_unit - 1) / rds_unit * rds_unit);
     }
-    if (tuned || wide || rds) {  // out of range (or no 32-bit value) -> message, exit 1
+    if (tuned || wide || rds || meter) {  // out of range (or no 32-bit value) -> message, exit 1
         const int32_t f = (int32_t)offset_hz;
         if ((long)f != offset_hz || (wide ? fmrx_tune_wide : fmrx_tune)(ctx, &f, 0) != FMRX_OK) {
             std::fprintf(stderr, "fmrx: --offset-hz %ld: %s\n", offset_hz,
@@ -369,13 +376,13 @@ int main(int argc, char** argv) {
         const int i = filled_q.pop();
         Slot& s = slots[i];
         if (s.blocks > 0) {
-            // with --rds: the whole granules, then (end of input only) the blocks left over without RDS
+            // with --rds or --meter: the whole granules, then (end of input only) the blocks left over without either
             const size_t head = s.blocks / rds_unit * rds_unit;
             CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks / unit_blocks * block_bytes, hipMemcpyHostToDevice, up));
             CLI_HIP(hipEventRecord(s.uploaded, up));
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
             if ((head > 0 && process(ctx, s.d_in, head, s.d_out) != FMRX_OK) ||
-                (head < s.blocks && (fmrx_set_rds(ctx, 0) != FMRX_OK ||
+                (head < s.blocks && (fmrx_set_rds(ctx, 0) != FMRX_OK || fmrx_set_meter(ctx, 0) != FMRX_OK ||
                                      process(ctx, s.d_in + head / unit_blocks * block_bytes, s.blocks - head,
                                              s.d_out + head * geo.pcm_samples) != FMRX_OK))) {
                 std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
@@ -410,6 +417,13 @@ int main(int argc, char** argv) {
         if (fmrx_rds_info_get(ctx, 0, &info) == FMRX_OK)
             std::fprintf(stderr, "rds pi=%04X pty=%d ps=\"%s\" groups=%d\n", (unsigned)info.pi, (int)info.pty, info.ps,
                          (int)info.groups);
+    }
+    if (meter) {
+        fmrx_meter_report rep;
+        fmrx_subcarriers sc{};
+        if (fmrx_meter_get(ctx, 0, &rep) == FMRX_OK && (rep.frames == 0 || fmrx_meter_detect(&rep, nullptr, &sc) == FMRX_OK))
+            std::fprintf(stderr, "meter pilot_snr=%.1f stereo=%d rds_snr=%.1f rds=%d frames=%llu\n", (double)sc.pilot_snr_db,
+                         sc.stereo, (double)sc.rds_snr_db, sc.rds, (unsigned long long)rep.frames);
     }
     fmrx_destroy(ctx);
     std::fprintf(stderr, "End of input stream reached!\n");

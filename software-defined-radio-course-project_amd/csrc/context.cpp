@@ -90,6 +90,7 @@ int reset_state(fmrx_ctx* c) {
     int rc = reset_rds_bits(c);
     if (rc) return rc;
     if ((rc = reset_deemph(c))) return rc;
+    reset_meter(c);
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -323,6 +324,7 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
     if (hipMemcpy(c->d_rdsb_taps.p, rdsb_taps.data(), sizeof(float) * rdsb_taps.size(), hipMemcpyHostToDevice) != hipSuccess)
         return cleanup(fail(FMRX_EHIP, "RDS tap upload failed"));
     c->rds_info.resize((size_t)ns);
+    c->meter_rep.resize((size_t)ns);
     // RDS taps, project.cpp:211 and :217 (bp_taps = 51 at bp_fs)
     std::vector<float> rds_taps(2 * kRdsTaps);
     design_bpf(rds_taps.data(), (float)g.bp_fs, 54000.0f, 60000.0f, kRdsTaps);
@@ -371,6 +373,7 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_wide_y.release(); c->d_wide_halo[0].release(); c->d_wide_halo[1].release();
     c->d_deemph_taps.release(); c->d_deemph_state[0].release(); c->d_deemph_state[1].release();
     c->d_deemph_x.release(); c->d_deemph_tmp.release();
+    c->d_meter_tab.release(); c->d_meter_pow.release();
     for (auto& e : c->evs) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);

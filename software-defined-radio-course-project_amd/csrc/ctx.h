@@ -1,6 +1,6 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, rds_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, meter_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -218,6 +218,15 @@ struct Ctx {
     int deemph_cur = 0;
     DevBuf<float> d_deemph_x;                 // a call's floats in front of the quantiser (4 B a sample and channel)
     DevBuf<float> d_deemph_tmp;               // fmrx_deemph: the caller's next state, before it is copied back
+    // subcarrier meter (fmrx_set_meter, meter.hip): no signal state; nothing here is allocated until the
+    // switch is first turned on (or fmrx_meter first runs)
+    bool meter_on = false;                    // fmrx_set_meter
+    int meter_p = 0;                          // samples a window (bp_fs / 1000) once d_meter_tab is filled
+    DevBuf<float> d_meter_tab;                // the 14 tables of fmrx_meter_design
+    DevBuf<float> d_meter_pow;                // a call's powers: n_streams x frames x 7
+    std::vector<float> meter_host;            // their host copy
+    size_t meter_pending = 0;                 // frames a stream of a call enqueued and not yet added
+    std::vector<fmrx_meter_report> meter_rep; // n_streams
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -343,6 +352,14 @@ int reset_rds_bits(fmrx_ctx* c);  // the back half's start state, enqueued on th
 // rds_decode_finish waits for the stream and parses them into rds_info
 int rds_decode_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
 int rds_decode_finish(fmrx_ctx* c);
+
+// ---- meter_api.cpp
+int check_meter_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole frames: the RDS granule's blocks
+void reset_meter(fmrx_ctx* c);                               // the reports back to zero
+// the meter over the rows at d_demod (whole frames) and the copy of its powers to the host, enqueued;
+// meter_finish waits for the stream and adds them to the streams' reports
+int meter_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
+int meter_finish(fmrx_ctx* c);
 
 // ---- front.cpp
 int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,

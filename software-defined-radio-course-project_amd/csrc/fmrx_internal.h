@@ -302,6 +302,23 @@ struct DeemphLaunch {
 };
 int launch_deemph(const DeemphLaunch& L, int n_streams, hipStream_t s);
 
+// ---- subcarrier meter (meter.hip) -------------------------------------------
+constexpr int kMeterTones = 7;       // 17, 19, 21, 56, 58, 61, 63 kHz
+constexpr int kMeterWindows = 64;    // 1 ms windows a frame
+constexpr int kMeterMaxP = 288;      // samples a window: bp_fs / 1000, a multiple of 16
+// P and the 7 x 2 x P table floats of fmrx_meter_design (host only, in double until stored; P and
+// tables may be null); false, nothing written: bp_fs no positive multiple of 16000 or P past kMeterMaxP
+bool meter_design(int bp_fs, int* P, float* tables);
+struct MeterLaunch {
+    const float* demod;     // n_streams rows (stride demod_stride) of frames x 64 P samples
+    size_t demod_stride;
+    const float* tables;    // 14 P floats: tone-major, c then s
+    int P;                  // 240, 256 or 288
+    int frames;             // frames a stream
+    float* power;           // n_streams x frames x kMeterTones
+};
+int launch_meter(const MeterLaunch& L, int n_streams, hipStream_t s);
+
 // ---- spectrum tooling and the arctan demodulator ------------------
 constexpr int kPsdMaxBins = 8192;  // N complex doubles in LDS per segment
 int launch_demod_arctan(float* out, double* prev, const float* i, const float* q, int n, hipStream_t s);

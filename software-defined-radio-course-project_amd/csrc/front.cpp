@@ -65,16 +65,19 @@ int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n
 // The audio stage of a call whose front end filled the context's demod rows (mono: the polyphase
 // stage; stereo: the non-pipelined engine).  With fmrx_set_rds on, the RDS decode of the same rows
 // goes on the stream in front of it (the audio stage moves the rows' tail afterwards) and is parsed
-// once the call's work is done; the audio stage reads and writes nothing the decode touches.
+// once the call's work is done; the audio stage reads and writes nothing the decode touches.  With
+// fmrx_set_meter on, the meter reads the same rows first and its powers are added to the reports last.
 static int run_audio_stage(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
     const size_t n_if = n_blocks * c->geo.if_samples;
     int rc;
+    if (c->meter_on && (rc = meter_enqueue(c, c->d_demod.p + kDemodHist, c->demod_stride, n_blocks))) return rc;
     if (c->rds_on && (rc = rds_decode_enqueue(c, c->d_demod.p + kDemodHist, c->demod_stride, n_blocks))) return rc;
     if (c->cfg.channels != FMRX_MONO)
         rc = run_stereo_audio(c, n_blocks, d_pcm, d_mono);
     else
         rc = run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
     if (rc) return rc;
+    if (c->meter_on && (rc = meter_finish(c))) return rc;
     return c->rds_on ? rds_decode_finish(c) : 0;
 }
 
@@ -84,7 +87,7 @@ int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_block
     const int ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;
     int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
-    if (rc || (rc = ensure_demod(c, n_if))) return rc;
+    if (rc || (c->meter_on && (rc = check_meter_blocks(c, n_blocks))) || (rc = ensure_demod(c, n_if))) return rc;
     if (c->cfg.channels != FMRX_MONO) {
         if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, false)))
             return rc;
@@ -180,7 +183,7 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) 
     const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples, gran = r.blocks;
     const size_t hb = r.hist_pairs() * c->pair_bytes;
     int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
-    if (rc || (rc = ensure_demod(c, n_if))) return rc;
+    if (rc || (c->meter_on && (rc = check_meter_blocks(c, n_blocks))) || (rc = ensure_demod(c, n_if))) return rc;
     const size_t fit = kWidePieceBytes / ((size_t)ns * ip * 8);
     const size_t piece = std::min(n_blocks, std::max(gran, fit / gran * gran));
     if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -89,7 +90,31 @@ class RdsInfo(C.Structure):
                 "blocks": self.blocks, "groups": self.groups}
 
 
-_vp, _sz, _fp, _i16p, _u8p = C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
+METER_TONES = 7  # include/fmrx.h FMRX_METER_TONES
+METER_TONES_KHZ = (17, 19, 21, 56, 58, 61, 63)
+METER_WINDOWS = 64  # 1 ms windows a frame
+
+
+class MeterReport(C.Structure):
+    """fmrx_meter_report: a stream's summed tone powers and the frames they cover."""
+    _fields_ = [("sum", C.c_double * METER_TONES), ("frames", C.c_uint64)]
+
+
+class MeterConfig(C.Structure):
+    """fmrx_meter_config: the decision's two thresholds in dB."""
+    _fields_ = [("pilot_min_snr_db", C.c_float), ("rds_min_snr_db", C.c_float)]
+
+
+class Subcarriers(C.Structure):
+    """fmrx_subcarriers: what fmrx_meter_detect says of a report."""
+    _fields_ = [("pilot_db", C.c_float), ("pilot_snr_db", C.c_float), ("rds_db", C.c_float), ("rds_snr_db", C.c_float),
+                ("stereo", C.c_int), ("rds", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+_vp, _sz, _fp, _i16p, _u8p =C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every function declared in include/fmrx.h
 PROTOTYPES = {
@@ -159,6 +184,14 @@ PROTOTYPES = {
     "fmrx_set_deemphasis": (C.c_int, [_vp, C.c_int]),
     "fmrx_deemphasis": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "fmrx_deemph": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp, _vp]),
+    "fmrx_meter_design": (C.c_int, [C.c_int, C.POINTER(C.c_int), _vp]),
+    "fmrx_meter": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_meter_device": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_meter_config_default": (C.c_int, [C.POINTER(MeterConfig)]),
+    "fmrx_meter_accumulate": (C.c_int, [C.POINTER(MeterReport), _vp, _sz]),
+    "fmrx_meter_detect": (C.c_int, [C.POINTER(MeterReport), C.POINTER(MeterConfig), C.POINTER(Subcarriers)]),
+    "fmrx_set_meter": (C.c_int, [_vp, C.c_int]),
+    "fmrx_meter_get": (C.c_int, [_vp, C.c_int, C.POINTER(MeterReport)]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -310,6 +343,38 @@ def deemph_design(audio_fs: int, tau_us: int) -> np.ndarray:
     return h
 
 
+def meter_design(bp_fs: int) -> tuple[int, np.ndarray]:
+    """fmrx_meter_design: (P, tables) of the subcarrier meter at bp_fs; tables float32 of shape (7, 2, P):
+    tone, (c, s), sample of the 1 ms window.  Host only."""
+    p = C.c_int()
+    _check(lib().fmrx_meter_design(int(bp_fs), C.byref(p), None))
+    tab = np.zeros((METER_TONES, 2, p.value), np.float32)
+    _check(lib().fmrx_meter_design(int(bp_fs), None, _np_ptr(tab)))
+    return p.value, tab
+
+
+def meter_accumulate(power, report: MeterReport | None = None) -> MeterReport:
+    """fmrx_meter_accumulate (host only): add one stream's frames x 7 powers to report (a new one when None)."""
+    report = MeterReport() if report is None else report
+    p = np.ascontiguousarray(power, np.float32).reshape(-1, METER_TONES)
+    _check(lib().fmrx_meter_accumulate(C.byref(report), _np_ptr(p), p.shape[0]))
+    return report
+
+
+def meter_detect(report: MeterReport, pilot_min_snr_db: float | None = None, rds_min_snr_db: float | None = None) -> dict:
+    """fmrx_meter_detect (host only): levels and flags of a report as a dict (pilot_db, pilot_snr_db, rds_db,
+    rds_snr_db, stereo, rds).  A threshold left None keeps fmrx_meter_config_default's (10 and 1.94 dB)."""
+    cfg, out = MeterConfig(), Subcarriers()
+    _check(lib().fmrx_meter_config_default(C.byref(cfg)))
+    if pilot_min_snr_db is not None:
+        cfg.pilot_min_snr_db = pilot_min_snr_db
+    if rds_min_snr_db is not None:
+        cfg.rds_min_snr_db = rds_min_snr_db
+    given = pilot_min_snr_db is not None or rds_min_snr_db is not None
+    _check(lib().fmrx_meter_detect(C.byref(report), C.byref(cfg) if given else None, C.byref(out)))
+    return out.as_dict()
+
+
 def iq_pair_bytes(fmt: int) -> int:
     """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
     n = lib().fmrx_iq_pair_bytes(fmt)
@@ -396,8 +461,12 @@ def rds_parse(bits, codes, info: RdsInfo | None = None) -> RdsInfo:
     return info
 
 
+PROBE_FRAMES = 16  # frames (64 ms each) decode_stations(probe=True) meters before it decides
+
+
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
-                    capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, **cfg):
+                    capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, probe: bool = False,
+                    **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
@@ -405,7 +474,13 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     capture's rate in Hz instead (set_capture_rate; whole granules are decoded); giving both is a
     ValueError.  rds=True: the capture is trimmed to whole RDS granules and the result is
     (stations, pcm, infos), infos one dict a station (pi, pty, tp, ps, rt and the parser's counters).
-    deemphasis_us=50 or 75: the PCM is de-emphasised (set_deemphasis; 0, the default: as broadcast)."""
+    deemphasis_us=50 or 75: the PCM is de-emphasised (set_deemphasis; 0, the default: as broadcast).
+    probe=True: a mono pass with the subcarrier meter on (set_meter) over the capture's leading whole
+    frames, PROBE_FRAMES of them at most, first says which stations carry a pilot and an RDS subcarrier;
+    the stations are then decoded in one context a group (the groups side by side, a thread each): stereo only with a pilot (a station without one
+    under channels=STEREO returns its mono PCM duplicated into R and L), RDS only with the subcarrier
+    (None in infos otherwise).  The result gains a trailing list, levels: meter_detect's dict a station
+    (None where the capture holds no whole frame: everything is then decoded as without probe)."""
     if capture_rate is not None and capture_decim != 1:
         raise ValueError("capture_rate and capture_decim exclude each other")
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
@@ -421,25 +496,63 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
         elif wide:
             rx.set_capture_decim(capture_decim)
 
+    def run(sel, ch, want_rds, meter=False):
+        """The stations sel in one context of ch channels: (pcm rows, infos or None, levels or None)."""
+        data = iq
+        with Receiver(mode, ch, rf_taps=rf_taps, n_streams=len(sel)) as rx:
+            configure(rx)
+            getattr(rx, tune)([stations[k].offset_hz for k in sel])
+            if deemphasis_us and not meter:
+                rx.set_deemphasis(deemphasis_us)
+            if rds or meter:
+                blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
+                per = rx.rds_granule // blocks * pairs * 2  # elements of the capture an RDS granule (whole frames) takes
+                n = data.size // per
+                if meter:  # the leading frames alone
+                    frames = rx.rds_granule * rx.geo.if_samples // (METER_WINDOWS * (rx.geo.bp_fs // 1000))
+                    n = min(n, max(1, PROBE_FRAMES // frames))
+                    if n == 0:
+                        return None, None, None
+                data = data[: n * per]
+            if want_rds:
+                rx.set_rds(True)
+            if meter:
+                rx.set_meter(True)
+            pcm = getattr(rx, process)(data).reshape(len(sel), -1)
+            infos = [rx.rds_info(k).as_dict() for k in range(len(sel))] if want_rds else None
+            levels = [meter_detect(rx.meter_report(k)) for k in range(len(sel))] if meter else None
+        return pcm, infos, levels
+
     with Receiver(mode, channels, rf_taps=rf_taps) as rx:
         configure(rx)
         stations = getattr(rx, scan)(iq, **cfg)
+    tail = ([],) if probe else ()
     if not stations:
-        return ([], np.zeros((0, 0), np.int16), []) if rds else ([], np.zeros((0, 0), np.int16))
-    with Receiver(mode, channels, rf_taps=rf_taps, n_streams=len(stations)) as rx:
-        configure(rx)
-        getattr(rx, tune)([s.offset_hz for s in stations])
-        if deemphasis_us:
-            rx.set_deemphasis(deemphasis_us)
-        if rds:
-            rx.set_rds(True)
-            blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
-            per = rx.rds_granule // blocks * pairs * 2  # elements of the capture an RDS granule takes
-            iq = iq[: iq.size // per * per]
-        pcm = getattr(rx, process)(iq)
-        infos = [rx.rds_info(k).as_dict() for k in range(len(stations))] if rds else None
-    pcm = pcm.reshape(len(stations), -1)
-    return (stations, pcm, infos) if rds else (stations, pcm)
+        return (([], np.zeros((0, 0), np.int16), []) if rds else ([], np.zeros((0, 0), np.int16))) + tail
+    everyone = list(range(len(stations)))
+    if not probe:
+        pcm, infos, _ = run(everyone, channels, rds)
+        return (stations, pcm, infos) if rds else (stations, pcm)
+    levels = run(everyone, MONO, False, meter=True)[2]
+    groups: dict = {}
+    for k in everyone:
+        key = (channels == STEREO, rds) if levels is None else (bool(levels[k]["stereo"]) and channels == STEREO,
+                                                                bool(levels[k]["rds"]) and rds)
+        groups.setdefault(key, []).append(k)
+    rows, infos = [None] * len(stations), [None] * len(stations)
+    # the groups' contexts side by side, a thread each (a context has a stream of its own and the library's
+    # calls release the GIL), so that their serial PLL chains overlap as they do inside one context
+    with ThreadPoolExecutor(max_workers=len(groups)) as pool:
+        done = list(pool.map(lambda kv: run(kv[1], STEREO if kv[0][0] else MONO, kv[0][1]), groups.items()))
+    for ((stereo, with_rds), sel), (pcm, inf, _) in zip(groups.items(), done):
+        if channels == STEREO and not stereo:
+            pcm = np.repeat(pcm, 2, axis=1)  # mono into R and L
+        for i, k in enumerate(sel):
+            rows[k] = pcm[i]
+            infos[k] = inf[i] if with_rds else None
+    pcm = np.stack(rows)
+    levels = [None] * len(stations) if levels is None else levels
+    return (stations, pcm, infos, levels) if rds else (stations, pcm, levels)
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:
@@ -652,6 +765,31 @@ class Receiver:
                d_pcm: int | None = None) -> None:
         """fmrx_deemph: the de-emphasis kernel on one row of n device floats; d_state 63 floats in/out."""
         _check(lib().fmrx_deemph(self.h, d_in, n, int(tau_us), d_state, d_out, d_pcm))
+
+    # ---- subcarrier meter (DESIGN §5.12)
+    def meter(self, demod: np.ndarray) -> np.ndarray:
+        """fmrx_meter: demod rows (whole frames: multiples of rds_granule blocks) -> the tone powers,
+        float32 of shape (n_streams, frames, 7), or (frames, 7) for one stream."""
+        d = np.ascontiguousarray(demod, np.float32).reshape(self.n_streams, -1)
+        nb = d.shape[1] // self.geo.if_samples
+        if nb * self.geo.if_samples != d.shape[1]:
+            raise FmrxError(FMRX_EINVAL, "meter takes whole blocks")
+        frames = d.shape[1] // (METER_WINDOWS * (self.geo.bp_fs // 1000))
+        out = np.zeros((self.n_streams, frames, METER_TONES), np.float32)
+        _check(lib().fmrx_meter(self.h, _np_ptr(d), nb, _np_ptr(out)))
+        return out if self.n_streams > 1 else out[0]
+
+    def meter_device(self, d_demod: int, n_blocks: int, d_power: int) -> None:
+        _check(lib().fmrx_meter_device(self.h, d_demod, n_blocks, d_power))
+
+    def set_meter(self, on: bool) -> None:
+        """fmrx_set_meter: the tuned, shared and wide process calls also meter their demod rows (whole frames)."""
+        _check(lib().fmrx_set_meter(self.h, int(bool(on))))
+
+    def meter_report(self, stream: int = 0) -> MeterReport:
+        rep = MeterReport()
+        _check(lib().fmrx_meter_get(self.h, int(stream), C.byref(rep)))
+        return rep
 
     def estimate_psd(self, samples: np.ndarray, freq_bins: int, fs: float):
         """estimatePSD (fourier.cpp:35-117) on the GPU: (freq, psd_db)."""
