@@ -120,6 +120,9 @@ int fmrx_rf_block(fmrx_ctx* ctx, const uint8_t* iq, size_t n_blocks, float* demo
 int fmrx_audio_block(fmrx_ctx* ctx, const float* demod, size_t n_blocks, int16_t* pcm);
 
 /* ---- device-resident fused path (async on the context stream) ------------------------ */
+/* Alignment, untuned u8 contexts: d_iq (and so every stream's row in it) may start at any byte and
+ * d_pcm at any multiple of 2; rows that are not 16-byte aligned only cost one small launch more.
+ * Tuned calls and the other formats are stricter (fmrx_set_input_format below).               */
 int fmrx_process_device(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm);
 /* Optional float taps of the mono product (n_streams x n_blocks*audio_frames), may be NULL */
 int fmrx_process_device_ex(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm,
