@@ -19,7 +19,7 @@
  *   fmrx_audio_block           <- audio_thread body    src/project.cpp:132-195
  *   fmrx_process               <- both bodies fused (host buffers in, host PCM out)
  *   fmrx_process_device        <- both bodies fused, device-resident buffers, async
- *   fmrx_rds_block / _device   <- rds_thread body      src/project.cpp:200-271 (RDS front half;
+ *   fmrx_rds_block_rec / _device   <- rds_thread body      src/project.cpp:200-271 (RDS front half;
  *                                 never launched by the reference, :380-382)
  *   fmrx_rds_bits / _device,      no counterpart: the RDS back half (symbol-rate resampler, bits,
  *   fmrx_rds_parse, _decode ...   block syndromes, group parser), defined below
@@ -539,6 +539,107 @@ int fmrx_rds_info_get(const fmrx_ctx* ctx, int stream, fmrx_rds_info* out);
  * synchronisation).  Such a call must be whole RDS granules (FMRX_EINVAL and nothing runs
  * otherwise).  The PCM is the same either way.  Off (the default): no call does anything more.    */
 int fmrx_set_rds(fmrx_ctx* ctx, int on);
+
+/* ---- RDS block sync: per-block acceptance, burst correction, block-wise groups ---- */
+/* A stage behind fmrx_rds_bits' bits, off by default; signs and integers only.  Per stream, over the bits
+ * b[0 .. N) it has been given since fmrx_reset:
+ *   1. s[i], i >= 25: step 6's syndrome of the 26-bit word w[i] ending at bit i.
+ *   2. The burst table (fmrx_rds_sync_design, host only): 1024 entries by syndrome, the 26-bit error pattern
+ *      that is a burst of length <= B (first and last bit of the burst set) at some shift and has that
+ *      syndrome, else FMRX_RDS_NO_BURST; entry 0 is the empty pattern.  B = 2: 51 patterns; no two bursts
+ *      share a syndrome for B <= 5 (a collision would make the design fail with FMRX_ESTATE).
+ *   3. Slots u = 0..3 are A, B, C*, D (C*: C or C').  With e = s[i] ^ offset word, w[i] is exact for the
+ *      slot where e == 0 and correctable where the table holds a pattern for e; slot 2 tries exact C,
+ *      exact C', correctable C, correctable C' in that order.  The information word is (w ^ pattern) >> 10.
+ *   4. votes[u][i] = the j in -J .. J, j != 0, for which position i + 26 j is exact for slot (u + j) mod 4;
+ *      positions in front of the stream's first word, and (at a flush) past its last bit, are no match.
+ *   5. Position i carries a block of slot u if it is exact or correctable for u and votes[u][i] >= V; of
+ *      several such slots the one with the most votes, the lowest u on a tie.
+ * A position is judged once its 26 J bits of lookahead have arrived: a call judges those positions and the
+ * context carries the last 25 + 52 J bits a stream, so any split of a stream into calls gives the same
+ * records.  fmrx_rds_blocks_flush judges the positions still pending, the bits that have not arrived
+ * counting as no match; bits given afterwards continue the same stream.  fmrx_reset clears the carry (and
+ * the streams' fmrx_rds_ext) and keeps the switch; none of it is in the fmrx_get_state blob.              */
+#define FMRX_RDS_NO_BURST 0xFFFFFFFFu
+typedef struct { int J, V, B; } fmrx_rds_sync_config;   /* defaults 8, 3, 2; 1 <= J <= 8, 1 <= V <= 2 J, 0 <= B <= 5 */
+int fmrx_rds_sync_config_default(fmrx_rds_sync_config* cfg);
+int fmrx_rds_sync_design(int B, uint32_t* table /* 1024, may be NULL */, int* patterns /* may be NULL */);
+/* An accepted block: the stream index of its last bit, the slot (0..3), whether C* matched as C', whether a
+ * burst was corrected, the votes it had and its 16 information bits.  pad is zero.                        */
+typedef struct { uint64_t bit; uint16_t info; uint8_t slot, c_prime, corrected, votes; uint8_t pad[2]; } fmrx_rds_block_rec;
+/* The primitive.  bits: n_streams rows of n_bits bytes (bit 0 of each is used), any n_bits.  blocks:
+ * n_streams rows of max_blocks records, a stream's accepted blocks in bit order; counts: n_streams, the
+ * blocks accepted (where it exceeds max_blocks the row holds the first max_blocks); n_bits <= 2^30.  cfg =
+ * NULL: the defaults; a cfg other than the one the stream began with is FMRX_EINVAL until fmrx_reset.  The device
+ * form is asynchronous on the context stream and all its pointers are device memory.                     */
+int fmrx_rds_blocks(fmrx_ctx* ctx, const fmrx_rds_sync_config* cfg, const uint8_t* bits, size_t n_bits,
+                    fmrx_rds_block_rec* blocks, size_t max_blocks, uint32_t* counts);
+int fmrx_rds_blocks_device(fmrx_ctx* ctx, const fmrx_rds_sync_config* cfg, const uint8_t* d_bits, size_t n_bits,
+                           fmrx_rds_block_rec* d_blocks, size_t max_blocks, uint32_t* d_counts);
+/* Host buffers; blocks and counts may both be NULL (at most 26 J positions a stream are pending).  With
+ * fmrx_set_rds_sync on, the records also go into the streams' fmrx_rds_ext and close their open groups.    */
+int fmrx_rds_blocks_flush(fmrx_ctx* ctx, fmrx_rds_block_rec* blocks, size_t max_blocks, uint32_t* counts);
+
+#define FMRX_RDS_EXT_TAIL 16  /* records the block-wise parser keeps */
+#define FMRX_RDS_MAX_AF 25
+/* What the block-wise parser has read so far.  Plain data, as fmrx_rds_info is; fmrx_rds_ext_init gives the
+ * start (characters not yet received are spaces; ps, rt and ptyn are NUL-terminated).                     */
+typedef struct {
+    uint64_t bits;              /* bits the records came from (the n_bits given)                           */
+    uint64_t exact_blocks;      /* records without a correction                                            */
+    uint64_t corrected_blocks;  /* records with one                                                        */
+    uint64_t groups;            /* B blocks closed with A, C* and D all there                              */
+    uint64_t partial_groups;    /* B blocks closed with one of them missing                                */
+    uint16_t pi;                /* the last exact A block (valid where pi_set)                             */
+    uint8_t pi_set;
+    uint8_t pty, tp;            /* the last B block                                                        */
+    uint8_t ta, ms, di;         /* the last group 0: TA, MS, and the four DI bits (d3 the most significant) */
+    uint8_t rt_ab, ptyn_ab;     /* the A/B flags of the last group 2 and group 10A                         */
+    uint8_t ps_sure, ptyn_sure; /* bit k: character k was written by blocks without a correction           */
+    uint64_t rt_sure;
+    uint8_t af_n;               /* AF codes kept (1..204: 87.5 MHz + 0.1 MHz x code), first appearance first */
+    uint8_t af_count;           /* the last count a 0A group announced (code 224 + count)                  */
+    uint8_t af[FMRX_RDS_MAX_AF];
+    uint8_t ct_set;             /* a group 4A with B, C and D uncorrected has been read; its fields follow */
+    uint8_t ct_hour, ct_minute, ct_month, ct_day;
+    int8_t ct_offset;           /* local time offset in half hours                                         */
+    uint16_t ct_year;           /* year, month, day of ct_mjd by IEC 62106 annex G in integers (good from
+                                   1900-03-01 to 2100-02-28; zeros below MJD 15079)                        */
+    uint32_t ct_mjd;
+    char ps[9];
+    char rt[65];
+    char ptyn[9];
+    uint8_t tail_n;             /* the carried tail: the last records, oldest first, and which B are closed */
+    uint8_t tail_done[FMRX_RDS_EXT_TAIL];
+    fmrx_rds_block_rec tail[FMRX_RDS_EXT_TAIL];
+} fmrx_rds_ext;
+int fmrx_rds_ext_init(fmrx_rds_ext* io);
+/* Host only, no context.  n records of one stream in bit order, in pieces of any size (the result depends on
+ * the records, not on how they were cut); n_bits is added to io->bits.  Every record is counted; an exact A
+ * block sets pi.  A B block at bit i is closed, with whichever of the blocks at i - 26 (A), i + 26 (C*) and
+ * i + 52 (D) are among the last FMRX_RDS_EXT_TAIL records, once a record at or past i + 52 has come, or at
+ * flush != 0 (which closes every open one).  A corrected A block counts only if it equals pi.  B sets tp and
+ * pty.  Group 0A/0B: TA, MS and the DI bit of segment B & 3; D gives two characters of ps; 0A with C, the AF
+ * codes 1..204 (at most FMRX_RDS_MAX_AF, in order of first appearance) and the count 224..249.  Group 2A: C
+ * gives two characters of rt at 4 (B & 15), D the next two; 2B: D two at 2 (B & 15); a change of the A/B flag
+ * first clears rt, as in fmrx_rds_parse.  Group 4A with C and D: the clock time (hour < 24 and minute < 60,
+ * else ignored).  Group 10A: ptyn at 4 (B & 1) as rt of 2A, with an A/B flag of its own.  A C' block never
+ * supplies version-A contents.  Bytes outside 0x20..0x7E are stored as spaces; every other group type sets
+ * tp and pty alone.
+ * A correction can be wrong (a longer error that looks like a short burst), so corrected blocks count for
+ * less: characters from a B and a C or D block both without a correction are always written and mark their
+ * places (ps_sure, rt_sure, ptyn_sure); characters with a correction in either block are written only to
+ * places not so marked.  A corrected B block may not change an A/B flag: where its flag differs, the group's
+ * text is left out.  AF codes and the clock time, which nothing soon repeats, are taken only where B and the
+ * blocks read are all without a correction.                                                              */
+int fmrx_rds_parse_blocks(fmrx_rds_ext* io, const fmrx_rds_block_rec* blocks, size_t n, uint64_t n_bits, int flush);
+/* on != 0: with fmrx_set_rds on too, every call that decodes RDS also runs the block sync (default
+ * constants) over the bits it produces, on the same stream, copies the streams' counts and records back
+ * and parses them into the streams' fmrx_rds_ext, which fmrx_rds_ext_get copies out.  The PCM and
+ * fmrx_rds_info are the same either way.  With fmrx_set_rds off the stage does nothing.  Off (the default):
+ * no call launches, allocates or copies anything more.                                                   */
+int fmrx_set_rds_sync(fmrx_ctx* ctx, int on);
+int fmrx_rds_ext_get(const fmrx_ctx* ctx, int stream, fmrx_rds_ext* out);
 
 /* ---- arctan demodulator and PSD estimate (floating-point diagnostics) ------ */
 /* fmDemodArctan: out[k] = atan2(Q,I) phase difference to the previous sample, wrapped into

@@ -34,6 +34,11 @@
 //     whole RDS granules (fmrx_rds_granule), the tuned front end runs (offset 0 without --offset-hz), and
 //     at end of input one line goes to stderr, `rds pi=%04X pty=%d ps="........" groups=%d`.  stdout is
 //     unchanged: blocks past the last whole granule are decoded without RDS.
+//   * --rds-sync (an fmrx extension, with --rds) also runs the block sync behind the bits (fmrx_set_rds_sync),
+//     flushes it at end of input and prints, after the `rds ...` line, to stderr
+//     `rdsx pi=%04X pty=%d ps="........" ct=YYYY-MM-DDTHH:MM+HH:MM af=%d blocks=%llu+%llu groups=%llu+%llu`
+//     (ct=- without a clock time; blocks exact + corrected, groups complete + partial).  Without --rds:
+//     message, exit 1.
 //   * --deemph 50|75 (an fmrx extension) de-emphasises the PCM with that time constant in microseconds
 //     (fmrx_set_deemphasis: 50 in most of the world, 75 in the Americas and Korea), whatever else is
 //     chosen; without it the audio is as broadcast, as project's is.  Any other value: message, exit 1.
@@ -112,6 +117,7 @@ void usage(const char* argv0) {
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
                  "                [--deemph 50|75]  de-emphasise the audio (time constant in us; default: none)\n"
                  "                [--meter]  measure the pilot and the RDS subcarrier; at end of input print their levels to stderr\n"
+                 "                [--rds-sync]  with --rds: per-block sync with burst correction; print the extended line too\n"
                  "                [--rds]  decode the station's RDS too; at end of input print its PI, PTY and name to stderr\n"
                  "                [--iq-format u8|s8|s16|f32]  raw format of stdin (default u8)\n"
                  "                [--capture-decim D]  stdin runs at D (2..10) times the mode's rate; --offset-hz and\n"
@@ -168,7 +174,7 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
 
 int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false, tuned = false, scan = false, rds = false, meter = false;
+    bool mono_product = false, tuned = false, scan = false, rds = false, rds_sync = false, meter = false;
     long offset_hz = 0;
     int iq_format = FMRX_IQ_U8, capture_decim = 1, deemph_us = 0;
     long capture_rate = 0;
@@ -183,6 +189,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
         else if (!std::strcmp(argv[i], "--scan")) scan = true;
         else if (!std::strcmp(argv[i], "--rds")) rds = true;
+        else if (!std::strcmp(argv[i], "--rds-sync")) rds_sync = true;
         else if (!std::strcmp(argv[i], "--meter")) meter = true;
         else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
         else if (!std::strcmp(argv[i], "--iq-format") && i + 1 < argc) {
@@ -223,6 +230,10 @@ int main(int argc, char** argv) {
         if (channels < 1 || channels > 2) { std::fprintf(stderr, "Invaild channel: %d!\n", channels); return 1; }  // project.cpp:289, verbatim
     } else {  // :292-298
         usage(argv[0]);
+        return 1;
+    }
+    if (rds_sync && !rds) {
+        std::fprintf(stderr, "fmrx: --rds-sync needs --rds\n");
         return 1;
     }
     if (bad_format) {
@@ -304,6 +315,7 @@ int main(int argc, char** argv) {
     size_t rds_unit = unit_blocks;
     if (rds || meter) {
         if (fmrx_rds_granule(ctx, &rds_unit) != FMRX_OK || (rds && fmrx_set_rds(ctx, 1) != FMRX_OK) ||
+            (rds_sync && fmrx_set_rds_sync(ctx, 1) != FMRX_OK) ||
             (meter && fmrx_set_meter(ctx, 1) != FMRX_OK)) {
             std::fprintf(stderr, "fmrx: %s: %s\n", rds ? "--rds" : "--meter", fmrx_last_error());
             fmrx_destroy(ctx);
@@ -417,6 +429,21 @@ int main(int argc, char** argv) {
         if (fmrx_rds_info_get(ctx, 0, &info) == FMRX_OK)
             std::fprintf(stderr, "rds pi=%04X pty=%d ps=\"%s\" groups=%d\n", (unsigned)info.pi, (int)info.pty, info.ps,
                          (int)info.groups);
+    }
+    if (rds_sync) {
+        fmrx_rds_ext x;
+        if (fmrx_rds_blocks_flush(ctx, nullptr, 0, nullptr) == FMRX_OK && fmrx_rds_ext_get(ctx, 0, &x) == FMRX_OK) {
+            char ct[32] = "-";
+            if (x.ct_set) {
+                const int half = x.ct_offset < 0 ? -x.ct_offset : x.ct_offset;
+                std::snprintf(ct, sizeof ct, "%04d-%02d-%02dT%02d:%02d%c%02d:%02d", (int)x.ct_year, (int)x.ct_month, (int)x.ct_day,
+                              (int)x.ct_hour, (int)x.ct_minute, x.ct_offset < 0 ? '-' : '+', half / 2, half % 2 * 30);
+            }
+            std::fprintf(stderr, "rdsx pi=%04X pty=%d ps=\"%s\" ct=%s af=%d blocks=%llu+%llu groups=%llu+%llu\n", (unsigned)x.pi,
+                         (int)x.pty, x.ps, ct, (int)x.af_n, (unsigned long long)x.exact_blocks,
+                         (unsigned long long)x.corrected_blocks, (unsigned long long)x.groups,
+                         (unsigned long long)x.partial_groups);
+        }
     }
     if (meter) {
         fmrx_meter_report rep;

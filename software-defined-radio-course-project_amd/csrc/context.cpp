@@ -324,6 +324,7 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
     if (hipMemcpy(c->d_rdsb_taps.p, rdsb_taps.data(), sizeof(float) * rdsb_taps.size(), hipMemcpyHostToDevice) != hipSuccess)
         return cleanup(fail(FMRX_EHIP, "RDS tap upload failed"));
     c->rds_info.resize((size_t)ns);
+    c->rds_ext.resize((size_t)ns);
     c->meter_rep.resize((size_t)ns);
     // RDS taps, project.cpp:211 and :217 (bp_taps = 51 at bp_fs)
     std::vector<float> rds_taps(2 * kRdsTaps);
@@ -367,6 +368,8 @@ void fmrx_destroy(fmrx_ctx* c) {
     c->d_rds_pll.release();
     c->d_rdsb_taps.release(); c->d_rdsb_hist.release(); c->d_rdsb_state.release(); c->d_rdsb_work.release();
     c->d_rdsb_mix.release(); c->d_rdsb_out.release();
+    c->d_rdss_table.release(); c->d_rdss_carry.release(); c->d_rdss_work.release(); c->d_rdss_in.release();
+    c->d_rdss_blocks.release(); c->d_rdss_counts.release();
     c->d_tune_tab.release(); c->d_tune_streams.release();
     c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
     c->d_wide_hist.release(); c->d_wide_taps.release(); c->d_wide_tab.release(); c->d_wide_streams.release();

@@ -1,6 +1,6 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, rds_api.cpp, meter_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -157,6 +157,25 @@ struct Ctx {
     size_t rdsb_pending = 0;              // symbols a stream of a decode enqueued and not yet parsed
     std::vector<fmrx_rds_info> rds_info;  // n_streams
     bool rds_on = false;                  // fmrx_set_rds
+    // RDS block sync (fmrx_set_rds_sync, rds_sync.hip; not part of the checkpoint blob): nothing here is
+    // allocated until the switch is first turned on (or fmrx_rds_blocks first runs)
+    bool rds_sync_on = false;             // fmrx_set_rds_sync
+    fmrx_rds_sync_config rdss_cfg{8, 3, 2};  // the constants the streams began with
+    int rdss_table_b = -1;                // the B d_rdss_table holds (-1: none yet)
+    uint64_t rdss_seen = 0;               // bits a stream has been given since the reset
+    uint64_t rdss_judged = 0;             // positions below it are judged
+    DevBuf<uint32_t> d_rdss_table;        // kRdsSyncTable burst patterns
+    DevBuf<uint8_t> d_rdss_carry;         // n_streams x kRdsSyncCarry: the last bits, right-aligned
+    DevBuf<uint32_t> d_rdss_work;         // a call's candidates, records and exact masks
+    DevBuf<uint8_t> d_rdss_in;            // fmrx_rds_blocks: the caller's bit rows
+    DevBuf<fmrx_rds_block_rec> d_rdss_blocks; // the host forms' lists: n_streams x the positions judged
+    DevBuf<uint32_t> d_rdss_counts;       // n_streams
+    std::vector<uint32_t> rdss_counts;    // their host copies: the counts, and rdss_most records a stream
+    std::vector<fmrx_rds_block_rec> rdss_host;
+    size_t rdss_most = 0;
+    bool rdss_pending = false;            // a decode enqueued the stage and has not yet parsed its records
+    size_t rdss_cap = 0, rdss_bits = 0;   //   its list rows and its bits a stream
+    std::vector<fmrx_rds_ext> rds_ext;    // n_streams
     // staging for the host-buffer entry points
     DevBuf<uint8_t> d_in;
     DevBuf<int16_t> d_out;
@@ -352,6 +371,13 @@ int reset_rds_bits(fmrx_ctx* c);  // the back half's start state, enqueued on th
 // rds_decode_finish waits for the stream and parses them into rds_info
 int rds_decode_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
 int rds_decode_finish(fmrx_ctx* c);
+
+// ---- rds_sync_api.cpp
+void reset_rds_sync(fmrx_ctx* c);  // the carry's counters and the extended infos back to the start
+// the block sync over n_bits more bits a stream at d_bits (rows n_bits apart) and the copy of its counts, enqueued;
+// rds_sync_finish waits for the stream, fetches the records and parses them into rds_ext
+int rds_sync_enqueue(fmrx_ctx* c, const uint8_t* d_bits, size_t n_bits);
+int rds_sync_finish(fmrx_ctx* c);
 
 // ---- meter_api.cpp
 int check_meter_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole frames: the RDS granule's blocks

@@ -281,6 +281,31 @@ struct RdsBitsLaunch {
 };
 int launch_rds_bits(const RdsBitsLaunch& L, int n_streams, hipStream_t s);
 
+// ---- RDS block sync (rds_sync.hip) ------------------------------------------
+constexpr int kRdsSyncMaxJ = 8;
+constexpr int kRdsSyncCarry = 25 + 52 * kRdsSyncMaxJ;  // bits a stream carries at most, right-aligned in its row
+constexpr int kRdsSyncTable = 1024;                    // burst patterns by syndrome
+// A call's domain is the carried bits followed by the new ones: position d < n_carry is bit
+// carry[kRdsSyncCarry - n_carry + d], the others bits[d - n_carry]; d stands for stream bit base + d.
+struct RdsSyncLaunch {
+    const uint8_t* bits;    // n_streams x n_new (stride bits_stride)
+    size_t bits_stride;
+    uint8_t* carry;         // n_streams x kRdsSyncCarry
+    const uint32_t* table;  // kRdsSyncTable
+    uint8_t* exact;         // scratch, n_streams x n_dom: bit u set where the position is exact for slot u
+    uint32_t* cand;         // scratch, n_streams x 4 x n_dom: info16 | valid << 16 | corrected << 17 | C' << 18
+    uint32_t* rec;          // scratch, n_streams x n_judge: cand | slot << 19 | votes << 21 | accepted << 31
+    void* blocks;           // n_streams x max_blocks fmrx_rds_block_rec
+    uint32_t* counts;       // n_streams
+    unsigned long long base;  // the stream index of domain position 0
+    int n_carry, n_new, n_dom;  // n_dom = n_carry + n_new
+    int j0, n_judge;        // the positions judged: [j0, j0 + n_judge) of the domain
+    int n_keep;             // bits carried afterwards: min(n_dom, 25 + 52 J)
+    int J, V;
+    unsigned max_blocks;
+};
+int launch_rds_sync(const RdsSyncLaunch& L, int n_streams, hipStream_t s);
+
 // ---- FM de-emphasis (deemph.hip) -------------------------------------------
 constexpr int kDeemphTaps = 64;      // the one-pole response cut where it is below half an ulp of its sum
 constexpr int kDeemphHist = kDeemphTaps - 1;  // inputs carried in front of a call, per stream and channel

@@ -106,6 +106,7 @@ int reset_rds_bits(fmrx_ctx* c) {
     HIPCHK(hipMemset2DAsync(c->d_rdsb_state.p, kRdsbStateBytes, 1, 2, ns, c->stream));
     for (auto& io : c->rds_info) fmrx_rds_info_init(&io);
     c->rdsb_pending = 0;
+    reset_rds_sync(c);
     return 0;
 }
 
@@ -123,6 +124,8 @@ int rds_decode_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, s
     c->rdsb_host.resize(2 * ns * n_sym);
     HIPCHK(hipMemcpyAsync(c->rdsb_host.data(), c->d_rdsb_out.p, 2 * ns * n_sym, hipMemcpyDeviceToHost, c->stream));
     c->rdsb_pending = n_sym;
+    // the block sync over the same bits (fmrx_set_rds_sync), behind the copy
+    if (c->rds_sync_on && (rc = rds_sync_enqueue(c, c->d_rdsb_out.p, n_sym))) return rc;
     return 0;
 }
 
@@ -135,7 +138,7 @@ int rds_decode_finish(fmrx_ctx* c) {
         int rc = fmrx_rds_parse(&c->rds_info[s], c->rdsb_host.data() + s * n, c->rdsb_host.data() + (ns + s) * n, n);
         if (rc) return rc;
     }
-    return 0;
+    return rds_sync_finish(c);
 }
 
 }  // namespace fmrx

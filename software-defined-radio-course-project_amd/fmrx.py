@@ -90,6 +90,72 @@ class RdsInfo(C.Structure):
                 "blocks": self.blocks, "groups": self.groups}
 
 
+RDS_EXT_TAIL, RDS_MAX_AF = 16, 25  # include/fmrx.h FMRX_RDS_EXT_TAIL, FMRX_RDS_MAX_AF
+RDS_NO_BURST = 0xFFFFFFFF  # FMRX_RDS_NO_BURST: a burst table entry without a pattern
+# fmrx_rds_block_rec as a numpy record: an accepted block of the RDS block sync
+RDS_BLOCK = np.dtype([("bit", "<u8"), ("info", "<u2"), ("slot", "u1"), ("c_prime", "u1"), ("corrected", "u1"),
+                      ("votes", "u1"), ("pad", "u1", (2,))])
+
+
+class RdsSyncConfig(C.Structure):
+    """fmrx_rds_sync_config: the block sync's constants (defaults 8, 3, 2)."""
+    _fields_ = [("J", C.c_int), ("V", C.c_int), ("B", C.c_int)]
+
+
+class _RdsBlockRec(C.Structure):
+    _fields_ = [("bit", C.c_uint64), ("info", C.c_uint16), ("slot", C.c_uint8), ("c_prime", C.c_uint8),
+                ("corrected", C.c_uint8), ("votes", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class RdsExt(C.Structure):
+    """Mirror of fmrx_rds_ext: what the block-wise RDS parser has read so far."""
+    _fields_ = [("bits", C.c_uint64), ("exact_blocks", C.c_uint64), ("corrected_blocks", C.c_uint64),
+                ("groups", C.c_uint64), ("partial_groups", C.c_uint64), ("pi", C.c_uint16), ("pi_set", C.c_uint8),
+                ("pty", C.c_uint8), ("tp", C.c_uint8), ("ta", C.c_uint8), ("ms", C.c_uint8), ("di", C.c_uint8),
+                ("rt_ab", C.c_uint8), ("ptyn_ab", C.c_uint8), ("ps_sure", C.c_uint8), ("ptyn_sure", C.c_uint8),
+                ("rt_sure", C.c_uint64), ("af_n", C.c_uint8), ("af_count", C.c_uint8),
+                ("af_raw", C.c_uint8 * RDS_MAX_AF), ("ct_set", C.c_uint8), ("ct_hour", C.c_uint8),
+                ("ct_minute", C.c_uint8), ("ct_month", C.c_uint8), ("ct_day", C.c_uint8), ("ct_offset", C.c_int8),
+                ("ct_year", C.c_uint16), ("ct_mjd", C.c_uint32), ("ps_raw", C.c_char * 9), ("rt_raw", C.c_char * 65),
+                ("ptyn_raw", C.c_char * 9), ("tail_n", C.c_uint8), ("tail_done", C.c_uint8 * RDS_EXT_TAIL),
+                ("tail", _RdsBlockRec * RDS_EXT_TAIL)]
+
+    def __init__(self):
+        super().__init__()
+        _check(lib().fmrx_rds_ext_init(C.byref(self)))
+
+    @property
+    def ps(self) -> str:
+        return self.ps_raw.decode("ascii")
+
+    @property
+    def rt(self) -> str:
+        return self.rt_raw.decode("ascii")
+
+    @property
+    def ptyn(self) -> str:
+        return self.ptyn_raw.decode("ascii")
+
+    @property
+    def af(self) -> list:
+        """The alternative frequencies in MHz, in order of first appearance."""
+        return [round(87.5 + 0.1 * self.af_raw[k], 1) for k in range(self.af_n)]
+
+    @property
+    def ct(self) -> dict | None:
+        """The last clock time as fields (offset: the local time offset in half hours), None before one."""
+        if not self.ct_set:
+            return None
+        return {"mjd": self.ct_mjd, "year": self.ct_year, "month": self.ct_month, "day": self.ct_day,
+                "hour": self.ct_hour, "minute": self.ct_minute, "offset": self.ct_offset}
+
+    def as_dict(self) -> dict:
+        return {"pi": self.pi if self.pi_set else None, "pty": self.pty, "tp": self.tp, "ta": self.ta, "ms": self.ms,
+                "di": self.di, "ps": self.ps, "rt": self.rt, "ptyn": self.ptyn, "af": self.af, "af_count": self.af_count,
+                "ct": self.ct, "bits": self.bits, "exact_blocks": self.exact_blocks,
+                "corrected_blocks": self.corrected_blocks, "groups": self.groups, "partial_groups": self.partial_groups}
+
+
 METER_TONES = 7  # include/fmrx.h FMRX_METER_TONES
 METER_TONES_KHZ = (17, 19, 21, 56, 58, 61, 63)
 METER_WINDOWS = 64  # 1 ms windows a frame
@@ -144,6 +210,15 @@ PROTOTYPES = {
     "fmrx_rds_decode_device": (C.c_int, [_vp, _vp, _sz]),
     "fmrx_rds_info_get": (C.c_int, [_vp, C.c_int, C.POINTER(RdsInfo)]),
     "fmrx_set_rds": (C.c_int, [_vp, C.c_int]),
+    "fmrx_rds_sync_config_default": (C.c_int, [C.POINTER(RdsSyncConfig)]),
+    "fmrx_rds_sync_design": (C.c_int, [C.c_int, _vp, C.POINTER(C.c_int)]),
+    "fmrx_rds_blocks": (C.c_int, [_vp, C.POINTER(RdsSyncConfig), _vp, _sz, _vp, _sz, _vp]),
+    "fmrx_rds_blocks_device": (C.c_int, [_vp, C.POINTER(RdsSyncConfig), _vp, _sz, _vp, _sz, _vp]),
+    "fmrx_rds_blocks_flush": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_rds_ext_init": (C.c_int, [C.POINTER(RdsExt)]),
+    "fmrx_rds_parse_blocks": (C.c_int, [C.POINTER(RdsExt), _vp, _sz, C.c_uint64, C.c_int]),
+    "fmrx_set_rds_sync": (C.c_int, [_vp, C.c_int]),
+    "fmrx_rds_ext_get": (C.c_int, [_vp, C.c_int, C.POINTER(RdsExt)]),
     "fmrx_fm_demod_arctan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "fmrx_estimate_psd": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_float, _vp, _vp]),
     "fmrx_psd_device": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_float, _vp]),
@@ -461,12 +536,39 @@ def rds_parse(bits, codes, info: RdsInfo | None = None) -> RdsInfo:
     return info
 
 
+def rds_sync_config(**kw) -> RdsSyncConfig:
+    """fmrx_rds_sync_config_default, with the fields given (J, V, B) set."""
+    cfg = RdsSyncConfig()
+    _check(lib().fmrx_rds_sync_config_default(C.byref(cfg)))
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+def rds_sync_design(B: int = 2) -> tuple[np.ndarray, int]:
+    """fmrx_rds_sync_design (host only): the 1024 burst patterns by syndrome (RDS_NO_BURST: none) and how
+    many bursts of length <= B the table holds."""
+    tab = np.zeros(1024, np.uint32)
+    n = C.c_int(0)
+    _check(lib().fmrx_rds_sync_design(int(B), _np_ptr(tab), C.byref(n)))
+    return tab, n.value
+
+
+def rds_parse_blocks(blocks, n_bits: int = 0, ext: RdsExt | None = None, flush: bool = False) -> RdsExt:
+    """fmrx_rds_parse_blocks (host only): feed one stream's block records (RDS_BLOCK), in pieces of any size,
+    into ext (a new RdsExt when None) and return it; flush=True also closes the open groups."""
+    ext = RdsExt() if ext is None else ext
+    b = np.ascontiguousarray(blocks, RDS_BLOCK).reshape(-1)
+    _check(lib().fmrx_rds_parse_blocks(C.byref(ext), _np_ptr(b), b.size, int(n_bits), int(bool(flush))))
+    return ext
+
+
 PROBE_FRAMES = 16  # frames (64 ms each) decode_stations(probe=True) meters before it decides
 
 
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
                     capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, probe: bool = False,
-                    **cfg):
+                    rds_sync: bool = False, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
@@ -480,7 +582,11 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     the stations are then decoded in one context a group (the groups side by side, a thread each): stereo only with a pilot (a station without one
     under channels=STEREO returns its mono PCM duplicated into R and L), RDS only with the subcarrier
     (None in infos otherwise).  The result gains a trailing list, levels: meter_detect's dict a station
-    (None where the capture holds no whole frame: everything is then decoded as without probe)."""
+    (None where the capture holds no whole frame: everything is then decoded as without probe).
+    rds_sync=True (with rds=True; a ValueError without): the block sync runs behind the bits (set_rds_sync) and
+    is flushed at the end, and infos holds RdsExt.as_dict()'s extended dict a station instead."""
+    if rds_sync and not rds:
+        raise ValueError("rds_sync needs rds")
     if capture_rate is not None and capture_decim != 1:
         raise ValueError("capture_rate and capture_decim exclude each other")
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
@@ -516,10 +622,15 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
                 data = data[: n * per]
             if want_rds:
                 rx.set_rds(True)
+                rx.set_rds_sync(rds_sync)
             if meter:
                 rx.set_meter(True)
             pcm = getattr(rx, process)(data).reshape(len(sel), -1)
-            infos = [rx.rds_info(k).as_dict() for k in range(len(sel))] if want_rds else None
+            if want_rds and rds_sync:
+                rx.rds_blocks_flush()
+                infos = [rx.rds_ext(k).as_dict() for k in range(len(sel))]
+            else:
+                infos = [rx.rds_info(k).as_dict() for k in range(len(sel))] if want_rds else None
             levels = [meter_detect(rx.meter_report(k)) for k in range(len(sel))] if meter else None
         return pcm, infos, levels
 
@@ -746,6 +857,41 @@ class Receiver:
         return info
 
     # ---- FM de-emphasis
+    def _rds_block_rows(self, counts: np.ndarray, rows: np.ndarray) -> list:
+        return [rows[s, : min(int(counts[s]), rows.shape[1])].copy() for s in range(self.n_streams)]
+
+    def rds_blocks(self, bits: np.ndarray, **cfg) -> list:
+        """fmrx_rds_blocks: n_streams rows of bits (rds_bits' "bits"; any length) -> a list of RDS_BLOCK record
+        arrays, the blocks a stream's positions judged by this call carry, in bit order.  J, V, B: the
+        constants (the defaults when none is given)."""
+        d = np.ascontiguousarray(bits, np.uint8).reshape(self.n_streams, -1)
+        n = d.shape[1]
+        rows = np.zeros((self.n_streams, max(n, 1)), RDS_BLOCK)
+        counts = np.zeros(self.n_streams, np.uint32)
+        c = C.byref(rds_sync_config(**cfg)) if cfg else None
+        _check(lib().fmrx_rds_blocks(self.h, c, _np_ptr(d), n, _np_ptr(rows), rows.shape[1], _np_ptr(counts)))
+        return self._rds_block_rows(counts, rows)
+
+    def rds_blocks_device(self, d_bits: int, n_bits: int, d_blocks: int, max_blocks: int, d_counts: int, **cfg) -> None:
+        c = C.byref(rds_sync_config(**cfg)) if cfg else None
+        _check(lib().fmrx_rds_blocks_device(self.h, c, d_bits, n_bits, d_blocks, max_blocks, d_counts))
+
+    def rds_blocks_flush(self) -> list:
+        """fmrx_rds_blocks_flush: the blocks of the positions still pending, as rds_blocks returns them."""
+        rows = np.zeros((self.n_streams, 26 * 8), RDS_BLOCK)
+        counts = np.zeros(self.n_streams, np.uint32)
+        _check(lib().fmrx_rds_blocks_flush(self.h, _np_ptr(rows), rows.shape[1], _np_ptr(counts)))
+        return self._rds_block_rows(counts, rows)
+
+    def set_rds_sync(self, on: bool) -> None:
+        """fmrx_set_rds_sync: with set_rds on, the RDS decode also runs the block sync into rds_ext."""
+        _check(lib().fmrx_set_rds_sync(self.h, int(bool(on))))
+
+    def rds_ext(self, stream: int = 0) -> RdsExt:
+        ext = RdsExt()
+        _check(lib().fmrx_rds_ext_get(self.h, int(stream), C.byref(ext)))
+        return ext
+
     @property
     def audio_fs(self) -> int:
         """The PCM's rate: if_fs audio_up / audio_down (geo.if_fs already holds audio_up)."""
