@@ -470,7 +470,7 @@ def test_scan_real_data_against_float64(fmrx, fmt):
     else:
         raw = (clean.astype(np.float64) + noise).astype(np.float32)
     with receiver(fmrx, fmt) as rx:
-        for n in (256, 4096, 8192):
+        for n in (256, 512, 1024, 2048, 4096, 8192):
             want = welch64(raw, fmt, n)
             assert want.min() >= 1e-6 * want.max()  # the input keeps every bin off float32's rounding floor
             got, _ = rx.scan_spectrum(raw, n)

@@ -1,7 +1,9 @@
 """GPU tests of the band scan (csrc/scan.hip, fmrx_scan*): the spectrum against numpy float64 (the
 definition in include/fmrx.h, restated in tests/test_scan_host.py), bit identity between the entry
 points, runs and alignments, the scan end to end and through the CLI, and that a scan leaves the
-receiver state alone.
+receiver state alone.  SCAN_CASES names every compiled scan_segments_kernel<log2 N, F>
+(tests/test_variants_host.py compares the list with the library): each meets float64 on one segment,
+on a few, and on more segments than the launch has workgroups.
 
 Tolerances (a numpy float32 radix-2 prototype, every product and sum in float32, against float64 on
 these inputs): one bin differed by at most 5e-4 dB (single-segment low-power bins), the power
@@ -15,21 +17,39 @@ import numpy as np
 import pytest
 
 import oracle
+from test_formats_host import DTYPES, F32, S8, S16, U8, normalise
 from test_scan_host import (DEFAULTS, candidate_bins, capture, quantised, rf_fs_of, welch64)
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
+torch = None  # imported by the _gpu fixture, like gf (tests/test_gpu_formats.py): SCAN_CASES imports without them
+gf = None
 
 BIN_TOL_DB = 0.01
 CAND_TOL_DB = 1e-3
 
+NAMES = {U8: "u8", S8: "s8", S16: "s16", F32: "f32"}
+# scan_segments_kernel<log2 N, F>: six sizes in four formats
+SCAN_CASES = [(log2n, fmt) for log2n in range(8, 14) for fmt in (U8, S8, S16, F32)]
+# the cases that also run with more segments than workgroups: u8 at every size, the three pairs whose
+# loads happen at staging time (PF false in the kernel), and each other format with its loads in flight
+SCAN_WALK_CASES = [(log2n, U8) for log2n in range(8, 14)] + [(13, S16), (12, F32), (13, F32), (9, S8), (8, S16), (9, F32)]
+
+
+def case_id(case):
+    return f"{1 << case[0]}-{NAMES[case[1]]}"
+
 
 @pytest.fixture(scope="module", autouse=True)
 def _gpu():
+    global torch, gf
+    torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     torch.cuda.init()
+    import test_gpu_formats
+
+    gf = test_gpu_formats
 
 
 @pytest.fixture(scope="module")
@@ -95,6 +115,121 @@ def test_spectrum_more_segments_than_workgroups(rx):
     got, nseg = rx.scan_spectrum(big, 256)
     assert nseg == 8192
     check_spectrum(got, big, 256)
+
+
+# ---- every instantiation against numpy float64 -------------------------------------------------------
+
+def welch64_slabs(raw, fmt, n, slab=128):
+    """gf.welch64 (fmrx.h's power spectrum in float64 on the format's normalised samples, FFT-shifted)
+    summed over slabs of segments, so that a long capture never stands in memory as complex128."""
+    nseg = raw.size // 2 // n
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
+    total = np.zeros(n, np.float64)
+    for s0 in range(0, nseg, slab):
+        x = normalise(raw[2 * n * s0: 2 * n * min(nseg, s0 + slab)], fmt).astype(np.float64)
+        z = (x[0::2] + 1j * x[1::2]).reshape(-1, n)
+        total += (np.abs(np.fft.fft(z * w, axis=1)) ** 2).sum(axis=0)
+    return np.fft.fftshift(8.0 / (3.0 * n * n * nseg) * total)
+
+
+def check_bins(got, want, label):
+    """Every bin of got (float32, from the GPU) against want (float64), which must keep every bin off
+    float32's rounding floor."""
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert want.min() >= 1e-6 * want.max(), label
+    worst = float(np.max(np.abs(db(got.astype(np.float64)) - db(want))))
+    print(f"{label}: worst bin {worst:.2e} dB")
+    assert worst <= BIN_TOL_DB, label
+
+
+def white(fmt, n_pairs, seed):
+    """Non-repeating white noise: uniform random bytes, or normal samples of sigma 1/4 of full scale
+    (int16 by rint with clipping)."""
+    rng = np.random.default_rng(seed)
+    if fmt in (U8, S8):
+        return rng.integers(0, 256, 2 * n_pairs, dtype=np.uint8).view(DTYPES[fmt])
+    x = rng.standard_normal(2 * n_pairs, dtype=np.float32) * np.float32(0.25)
+    if fmt == S16:
+        return np.clip(np.rint(x * np.float32(32768.0)), -32768, 32767).astype(np.int16)
+    return x
+
+
+# Seeds of the one-segment inputs.  One Hann-windowed segment of white noise has a smallest bin near
+# 1 / (9 N) of its largest (the smallest of N exponential variates over the largest), 1.4e-5 at 8192
+# bins, so check_bins' 1e-6 leaves little room and the seeds are chosen on the float64 spectra alone:
+# uniform bytes of seed 1 give 1.0e-5 (8192 bins) .. 2.0e-4 (512), the normal samples of seed 14 give
+# 8.2e-6 at the least over every size here.  (Two stations plus noise of sigma 2^-8, the input of
+# tests/test_gpu_formats.py::test_scan_real_data_against_float64, cannot serve for one segment: an FM
+# carrier is nearly a line within so short a time and the smallest bin falls to 2e-9 .. 8e-8 of it.  That
+# test runs the stations at every size over 6 to 200 segments instead.)
+BYTE_SEED, NORMAL_SEED = 1, 14
+
+
+def noise_like(fmt, n_pairs):
+    return white(fmt, n_pairs, BYTE_SEED if fmt in (U8, S8) else NORMAL_SEED)
+
+
+@pytest.mark.parametrize("case", SCAN_CASES, ids=case_id)
+def test_every_instantiation_one_segment_and_a_few(fmrx, case):
+    """N pairs (one segment: nothing is averaged) and 3 N + 100 pairs (three segments and a dropped tail)."""
+    log2n, fmt = case
+    n = 1 << log2n
+    raw = noise_like(fmt, 3 * n + 100)
+    with gf.receiver(fmrx, fmt) as r:
+        for n_pairs in (n, 3 * n + 100):
+            part = raw[: 2 * n_pairs]
+            got, nseg = r.scan_spectrum(part, n)
+            assert nseg == n_pairs // n
+            want = gf.welch64(part, fmt, n)
+            assert np.allclose(welch64_slabs(part, fmt, n, 2), want, rtol=1e-12, atol=0.0)
+            check_bins(got, want, f"{NAMES[fmt]} bins={n} pairs={n_pairs}")
+            if fmt == U8:
+                check_spectrum(got, part, n)  # and the candidates
+
+
+def walk_segments(n, cus):
+    """2 G_max + 1 segments, G_max the most workgroups scan_workgroups can make: workgroups of 256 threads
+    (32 waves a CU: 8) with 8 (N + N / 16) bytes of static LDS (160 KiB a CU).  The occupancy call can only
+    return this or less, so every workgroup takes at least two segments and some take three."""
+    return 2 * cus * min(8, 160 * 1024 // (8 * (n + n // 16))) + 1
+
+
+@pytest.mark.parametrize("case", SCAN_WALK_CASES, ids=case_id)
+def test_more_segments_than_workgroups(fmrx, case):
+    """The grid-stride loop on white noise that never repeats: segments past a workgroup's first come
+    through the loads inside the loop (in flight during the transform, or at staging time where they do
+    not fit the registers) and add to a live accumulator.  A stale segment in place of half of them moves
+    the worst bin of the float64 average by 0.2 dB (256 bins) to 0.55 dB (8192), twenty times the bound."""
+    log2n, fmt = case
+    n = 1 << log2n
+    nseg = walk_segments(n, torch.cuda.get_device_properties(0).multi_processor_count)
+    raw = white(fmt, nseg * n, 2)
+    with gf.receiver(fmrx, fmt) as r:
+        got, got_seg = r.scan_spectrum(raw, n)
+    assert got_seg == nseg
+    check_bins(got, welch64_slabs(raw, fmt, n), f"{NAMES[fmt]} bins={n} nseg={nseg} white")
+
+
+@pytest.mark.parametrize("case", SCAN_WALK_CASES, ids=case_id)
+def test_one_live_segment_among_blanks(fmrx, case):
+    """Every pair the format's zero but for one segment of noise, first at index 0, then at nseg - 1, then
+    in the middle: the spectrum is that segment's float64 spectrum divided by nseg, bin by bin.  Nothing is
+    averaged away: at nseg - 1 the segment is some workgroup's second or third, so its samples came through
+    the loads inside the loop; at 0 the later blank segments add exactly nothing to a live accumulator."""
+    log2n, fmt = case
+    n = 1 << log2n
+    nseg = walk_segments(n, torch.cuda.get_device_properties(0).multi_processor_count)
+    blank = 128 if fmt == U8 else 0
+    live = noise_like(fmt, n)
+    want = gf.welch64(live, fmt, n) / nseg
+    raw = np.full(2 * nseg * n, blank, DTYPES[fmt])
+    with gf.receiver(fmrx, fmt) as r:
+        for at in (0, nseg - 1, nseg // 2):
+            raw[2 * n * at: 2 * n * (at + 1)] = live
+            got, got_seg = r.scan_spectrum(raw, n)
+            assert got_seg == nseg
+            check_bins(got, want, f"{NAMES[fmt]} bins={n} nseg={nseg} live segment at {at}")
+            raw[2 * n * at: 2 * n * (at + 1)] = blank
 
 
 def test_spectrum_rand(rx):
@@ -168,9 +303,10 @@ def test_host_device_and_repeat_runs_are_bit_identical(rx, n):
     assert np.array_equal(bits(dev), bits(device_spectrum(rx, d_iq.data_ptr(), iq.size // 2, n)))
 
 
-@pytest.mark.parametrize("n", [256, 4096])
+@pytest.mark.parametrize("n", [256, 512, 1024, 2048, 4096])
 def test_two_byte_aligned_device_pointer(rx, n):
-    """d_iq advanced by one pair: the capture starts 2 bytes off a dword."""
+    """d_iq advanced by one pair: the capture starts 2 bytes off a dword (one, one, two, four and eight
+    funnel-shifted dwords a thread and segment)."""
     iq = capture("three")[0]
     d_iq = torch.from_numpy(np.array(iq)).cuda()
     assert d_iq.data_ptr() % 4 == 0

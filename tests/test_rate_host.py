@@ -15,6 +15,7 @@ import pytest
 import iqgen
 import oracle
 from test_formats_host import F32, S16, U8, normalise
+from test_gpu_rate_sweep import RATE_SWEEP, sweep_ratio
 from test_wide_host import (Q_BLOCKS, Q_D, Q_MODE, Q_SCAN, Q_SKIP, Q_STATIONS, _orc, as_complex, narrow_compose,
                             narrow_station, peak_correlation, two_station_capture, welch64, wide_compose)
 
@@ -270,12 +271,33 @@ def test_resample_is_the_definition():
 
 # ---- the kernel's plan in numpy -----------------------------------------------------------------------------
 
-def emulate_kernel(xi, xq, n_c, k_c, tab, h, up, down, n_out, segs, first_pair=0):
+def taps_by_phase(h, up, down):
+    """rate_taps_by_phase (csrc/wide_design.cpp) restated: the taps regrouped by output phase, L rows of
+    ceil((16 M + 1) / L), and the byte offset in the LDS rows of the pair lane 0 multiplies by each."""
+    hc, ts = (16 + up - 1) // up, (16 * down + 1 + up - 1) // up
+    w = (64 + hc) | 1
+    hp, off = np.zeros((up, ts), np.float32), np.zeros((up, ts), np.int64)
+    for phi in range(up):
+        e, k0 = divmod(phi * down, up)
+        for i in range(ts):
+            if k0 + up * i < 16 * down + 1:
+                u = hc * down + e - i
+                assert u >= 0
+                hp[phi, i], off[phi, i] = h[k0 + up * i], 8 * ((u % down) * w + u // down)
+    return hp, off
+
+
+def emulate_kernel(xi, xq, n_c, k_c, tab, h, up, down, n_out, segs, first_pair=0, grouped=False):
     """rate_ddc_kernel's staging, layout, phase stepping, history copy and hand-off in numpy float32 for
     one station: workgroups of 256 threads (four waves of 64 lanes) stage chunks of 64 M wide pairs = 64 L
     outputs, the rotated pairs in M rows of W columns behind HC history columns, the taps by phase (each
     phase summed by the 64 lanes of one wave), the outputs through rows of L | 1 and out by all 256
-    threads.  xi, xq: the normalised samples of the call (zeros in front of them)."""
+    threads.  xi, xq: the normalised samples of the call (zeros in front of them).
+
+    grouped: the phases in the kernel's order -- wave by wave, in groups of pg <= 4 phases side by side,
+    the last one ragged -- each tap read at the byte offset taps_by_phase gives it, nmin taps for every
+    phase of a group and then one more for the phases with k_0 < rem, the hand-off rows written group by
+    group.  Otherwise one phase at a time, walking the rows itself."""
     nt, ns = 64, 256
     hc, ts = (16 + up - 1) // up, (16 * down + 1 + up - 1) // up
     w, ls = (nt + hc) | 1, up | 1
@@ -338,7 +360,27 @@ def emulate_kernel(xi, xq, n_c, k_c, tab, h, up, down, n_out, segs, first_pair=0
                 row = np.where(row >= down, row - down, row)
             pc = (pc + ph_chunk) % n_c
             ob = np.full((nt * ls, 2), np.nan, np.float32)
-            for phi in range(up):
+            if grouped:
+                tp_h, tp_off = taps_by_phase(h, up, down)
+                turns = ((up + 3) // 4 + 3) // 4
+                pg = (up + 4 * turns - 1) // (4 * turns)
+                done = []
+                for wave in range(4):
+                    for phi0 in range(wave * pg, up, 4 * pg):
+                        r_n = min(pg, up - phi0)
+                        acc = np.zeros((r_n, nt, 2), np.float32)
+                        for i in range(nmin):
+                            for r in range(r_n):
+                                at = tp_off[phi0 + r, i] // 8 + tid
+                                acc[r] = (acc[r] + (xb[at] * tp_h[phi0 + r, i]).astype(np.float32)).astype(np.float32)
+                        for r in range(r_n):
+                            if ((phi0 + r) * down) % up < rem:
+                                at = tp_off[phi0 + r, nmin] // 8 + tid
+                                acc[r] = (acc[r] + (xb[at] * tp_h[phi0 + r, nmin]).astype(np.float32)).astype(np.float32)
+                            ob[(phi0 + r) + ls * tid] = acc[r]
+                            done.append(phi0 + r)
+                assert sorted(done) == list(range(up))  # every phase once
+            for phi in range(0 if grouped else up):
                 e, k0 = divmod(phi * down, up)
                 row_s, off = e, e * w + hc
                 acc = np.zeros((nt, 2), np.float32)
@@ -378,6 +420,30 @@ def test_kernel_plan_in_numpy(fmrx, cap_fs, offset, first_pair, chunks):
     x = normalise(raw, U8)
     for segs in (1, 3):
         got = emulate_kernel(x[0::2], x[1::2], d["N"], d["k"], d["table"], d["h"], up, down, n_out, segs, first_pair)
+        assert np.array_equal(got.reshape(-1).view(np.uint32), want.view(np.uint32)), segs
+    assert want.any()
+
+
+SWEEP_RATIOS = sorted({(oracle.MODES[mode][3], cap_fs) + sweep_ratio(mode, cap_fs) for mode, cap_fs in RATE_SWEEP},
+                      key=lambda c: c[2:])
+
+
+@pytest.mark.parametrize("rf_fs,cap_fs,up,down", SWEEP_RATIOS, ids=[f"{c[2]}/{c[3]}" for c in SWEEP_RATIOS])
+def test_kernel_plan_in_numpy_over_the_sweep(fmrx, rf_fs, cap_fs, up, down):
+    """Every (L, M) of tests/test_gpu_rate_sweep.py through the emulation with the phases in the kernel's
+    order and the taps at the byte offsets of rate_taps_by_phase: three chunks (the last one ragged) as one
+    segment and as three.  HC, the row width, L | 1, the history copy and the offsets hold at every L
+    before the GPU runs one; the buffers are exactly rate_lds_bytes long, so an index past them raises."""
+    offset, first_pair = rf_fs // 4 + 50000, 7 * down
+    d = fmrx.rate_design(rf_fs, cap_fs, offset)
+    assert (d["up"], d["down"]) == (up, down)
+    n_out = (64 * 3 - 37) * up
+    raw = iqgen.make("synth:9", 2 * n_out * down // up, rf_fs)
+    want, _, _ = rate_y(raw, U8, rf_fs, cap_fs, offset, first_pair)
+    x = normalise(raw, U8)
+    for segs in (1, 3):
+        got = emulate_kernel(x[0::2], x[1::2], d["N"], d["k"], d["table"], d["h"], up, down, n_out, segs, first_pair,
+                             grouped=True)
         assert np.array_equal(got.reshape(-1).view(np.uint32), want.view(np.uint32)), segs
     assert want.any()
 
