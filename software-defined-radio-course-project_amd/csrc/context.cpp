@@ -39,67 +39,29 @@ int fail(int code, const char* fmt, ...) {
 }
 
 int timing_begin(fmrx_ctx* c, hipStream_t st, TimingPair** ev) {
-    if (!c->timing) return 0;
-    if (c->ev_used == c->evs.size()) {
+    if (!c->diag.timing) return 0;
+    if (c->diag.ev_used == c->diag.evs.size()) {
         TimingPair e{nullptr, nullptr};
         HIPCHK(hipEventCreate(&e.first));
         HIPCHK(hipEventCreate(&e.second));
-        c->evs.push_back(e);
+        c->diag.evs.push_back(e);
     }
-    *ev = &c->evs[c->ev_used++];
+    *ev = &c->diag.evs[c->diag.ev_used++];
     HIPCHK(hipEventRecord((*ev)->first, st));
     return 0;
 }
 
 int reset_state(fmrx_ctx* c) {
-    const int ns = c->cfg.n_streams;
-    c->pll_trig = fmrx_ctx::TrigTrack{};
-    c->rds_trig = fmrx_ctx::TrigTrack{};
-    c->tune_pos = 0;  // the offsets stay (configuration)
-    HIPCHK(hipMemsetAsync(c->d_halo[0].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_halo[1].p, iq_zero_byte(c), c->halo_bytes * ns, c->stream));
-    c->halo_cur = 0;
-    if (c->ratio.on()) {  // the wide stage: history of the format's zero, narrow halo of 0.0f
-        const size_t nh = c->halo_pairs * 8 * ns;
-        HIPCHK(hipMemsetAsync(c->d_wide_hist.p, iq_zero_byte(c), c->ratio.hist_pairs() * c->pair_bytes, c->stream));
-        HIPCHK(hipMemsetAsync(c->d_wide_halo[0].p, 0, nh, c->stream));
-        HIPCHK(hipMemsetAsync(c->d_wide_halo[1].p, 0, nh, c->stream));
-        c->wide_halo_cur = 0;
-    }
-    HIPCHK(hipMemsetAsync(c->d_audio_hist.p, 0, sizeof(float) * c->audio_hist * ns, c->stream));
-    c->audio_hist_stale = false;
-    if (c->d_demod.p)  // the history in front of each stream (every call overwrites the rest)
-        HIPCHK(hipMemset2DAsync(c->d_demod.p, c->demod_stride * sizeof(float), 0, sizeof(float) * kDemodHist, ns,
-                                c->stream));
-    // project.cpp:106-111: integrator 0, phaseEst 0, feedbackI 1, feedbackQ 0,
-    // ncoOut_state 1, trigOffset 0
-    std::vector<float> pll(8 * ns, 0.0f);
-    for (int s = 0; s < ns; s++) {
-        pll[8 * s + 2] = 1.0f;
-        pll[8 * s + 4] = 1.0f;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_pll.p, pll.data(), sizeof(float) * pll.size(),
-                          hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_mix_tail.p, 0, sizeof(float) * kMixTail * ns, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_mono_state.p, 0, sizeof(float) * 8 * ns, c->stream));
-    // RDS (project.cpp:206-226): zero histories, the same PLL start as the pilot PLL
-    HIPCHK(hipMemsetAsync(c->d_rds_dhist.p, 0, sizeof(float) * kRdsDemodHist * ns, c->stream));
-    if (c->d_rds_chan.p) HIPCHK(hipMemsetAsync(c->d_rds_chan.p, 0, sizeof(float) * c->d_rds_chan.n, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_rds_pll.p, pll.data(), sizeof(float) * pll.size(), hipMemcpyHostToDevice,
-                          c->stream));
-    int rc = reset_rds_bits(c);
-    if (rc) return rc;
-    if ((rc = reset_deemph(c))) return rc;
+    // project.cpp:106-111: integrator 0, phaseEst 0, feedbackI 1, feedbackQ 0, ncoOut_state 1,
+    // trigOffset 0; RDS (project.cpp:206-226) starts its PLL the same
+    std::vector<float> pll0(8 * (size_t)c->cfg.n_streams, 0.0f);
+    for (size_t s = 0; s < pll0.size(); s += 8) pll0[s + 2] = pll0[s + 4] = 1.0f;
+    int rc;
+    if ((rc = reset_front(c)) || (rc = reset_wide(c)) || (rc = reset_audio(c, pll0)) || (rc = reset_rds_front(c, pll0)) ||
+        (rc = reset_rds_bits(c)) || (rc = reset_deemph(c)))
+        return rc;
     reset_meter(c);
     HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// The de-emphasis carry back to 63 zeros in front of every row (nothing to do before it was ever on)
-int reset_deemph(fmrx_ctx* c) {
-    c->deemph_cur = 0;
-    if (c->d_deemph_state[0].p)
-        HIPCHK(hipMemsetAsync(c->d_deemph_state[0].p, 0, sizeof(float) * c->d_deemph_state[0].n, c->stream));
     return 0;
 }
 
@@ -265,136 +227,48 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
         cfg->n_streams > max_y)
         return fail(FMRX_EINVAL, "n_streams %d exceeds the device's grid.y limit %d", cfg->n_streams, max_y);
     fmrx_ctx* c = new fmrx_ctx();
+    auto failed = [&](int code) { fmrx_destroy(c); return code; };  // the one failure path from here on
     c->cfg = *cfg;
     c->cfg.rf_taps = g.rf_taps;
     c->cfg.bp_taps = g.bp_taps;
     c->geo = g;
-    mode_constants(cfg->mode, &c->mc);
-    if (!fused_rf_supported(c)) {
-        delete c;
-        return fail(FMRX_EINVAL, "no compiled RF kernel for rf_taps=%d rf_decim=%d", g.rf_taps,
-                    g.rf_decim);
-    }
-    if ((rc = set_device(c))) { delete c; return rc; }
-    if ((rc = knobs_from_env(&c->knobs))) {
-        delete c;
-        return rc;
-    }
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0)
-            c->n_simd = 4 * cus;
-    }
-    // taps, exactly as the reference designs them (project.cpp:37, 97, 104, 117)
-    c->rf.resize(g.rf_taps);
-    design_lpf(c->rf.data(), (float)g.rf_fs, (float)kRfFc, g.rf_taps, 1);
-    c->audio.resize(g.audio_taps_total);
-    design_lpf(c->audio.data(), (float)g.if_fs, (float)kAudioFc, g.audio_taps_total, g.audio_up);
-    c->ch.resize(g.bp_taps);
-    design_bpf(c->ch.data(), (float)g.bp_fs, 22000.0f, 54000.0f, g.bp_taps);
-    c->ca.resize(g.bp_taps);
-    design_bpf(c->ca.data(), (float)g.bp_fs, 18500.0f, 19500.0f, g.bp_taps);
-    std::memset(&c->mono_taps, 0, sizeof c->mono_taps);
-    std::copy(c->rf.begin(), c->rf.end(), c->mono_taps.rf);
-    if (g.audio_up == 1) std::copy(c->audio.begin(), c->audio.end(), c->mono_taps.audio);
-
-    const int ns = cfg->n_streams;
-    auto cleanup = [&](int code) { fmrx_destroy(c); return code; };
+    if (!fused_rf_supported(c))
+        return failed(fail(FMRX_EINVAL, "no compiled RF kernel for rf_taps=%d rf_decim=%d", g.rf_taps, g.rf_decim));
+    if ((rc = set_device(c)) || (rc = knobs_from_env(&c->knobs))) return failed(rc);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0)
+        c->n_simd = 4 * cus;
     // the context stream at the highest priority (the serial PLL of the pipelined stereo engine
     // runs on it, its stage streams at the lowest)
     int prio_lo = 0, prio_hi = 0;
     if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
         hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi) != hipSuccess)
-        return cleanup(fail(FMRX_EHIP, "hipStreamCreate failed"));
-    c->halo_bytes = mono_halo_bytes(g.rf_taps, g.rf_decim, g.audio_down);
-    c->halo_pairs = c->halo_bytes / 2;
-    c->audio_hist = g.audio_taps_total - 1;
-    if ((rc = c->d_halo[0].ensure(c->halo_bytes * ns)) || (rc = c->d_halo[1].ensure(c->halo_bytes * ns)) ||
-        (rc = c->d_audio_hist.ensure((size_t)c->audio_hist * ns)) ||
-        (rc = c->d_audio.ensure(c->audio.size())) || (rc = c->d_rf.ensure(c->rf.size())) ||
-        (rc = c->d_pll.ensure(8 * (size_t)ns)) || (rc = c->d_mix_tail.ensure((size_t)kMixTail * ns)) ||
-        (rc = c->d_mono_state.ensure(8 * (size_t)ns)) || (rc = c->d_sintab.ensure(kSinSize)) ||
-        (rc = c->d_rds_taps.ensure(2 * kRdsTaps)) || (rc = c->d_rds_dhist.ensure((size_t)kRdsDemodHist * ns)) ||
-        (rc = c->d_rds_pll.ensure(8 * (size_t)ns)) || (rc = c->d_rdsb_taps.ensure(kRdsbTaps)) ||
-        (rc = c->d_rdsb_hist.ensure((size_t)kRdsbHist * ns)) || (rc = c->d_rdsb_state.ensure((size_t)kRdsbStateBytes * ns)))
-        return cleanup(rc);
-    // the symbol-rate resampler's prototype: 101 taps a phase at 19 bp_fs, gain 19
-    std::vector<float> rdsb_taps(kRdsbTaps);
-    design_lpf(rdsb_taps.data(), (float)g.bp_fs * (float)kRdsbUp, 3000.0f, kRdsbTaps, kRdsbUp);
-    if (hipMemcpy(c->d_rdsb_taps.p, rdsb_taps.data(), sizeof(float) * rdsb_taps.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail(FMRX_EHIP, "RDS tap upload failed"));
-    c->rds_info.resize((size_t)ns);
-    c->rds_ext.resize((size_t)ns);
-    c->meter_rep.resize((size_t)ns);
-    // RDS taps, project.cpp:211 and :217 (bp_taps = 51 at bp_fs)
-    std::vector<float> rds_taps(2 * kRdsTaps);
-    design_bpf(rds_taps.data(), (float)g.bp_fs, 54000.0f, 60000.0f, kRdsTaps);
-    design_bpf(rds_taps.data() + kRdsTaps, (float)g.bp_fs, 113500.0f, 114500.0f, kRdsTaps);
-    if (hipMemcpy(c->d_rds_taps.p, rds_taps.data(), sizeof(float) * rds_taps.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail(FMRX_EHIP, "RDS tap upload failed"));
-    if (hipMemcpy(c->d_audio.p, c->audio.data(), sizeof(float) * c->audio.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_rf.p, c->rf.data(), sizeof(float) * c->rf.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_sintab.p, synth_sintab(), sizeof(int16_t) * kSinSize, hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail(FMRX_EHIP, "tap upload failed"));
-    if (g.audio_up > 1) {
-        // the rational resampler's prototype by phase: row k0 holds the 51 taps an output of
-        // phase k0 reads, in the order filter.cpp:84 visits them (k = k0, k0 + up, ...)
-        const int up = g.audio_up;
-        std::vector<float> rows((size_t)up * kAudioRow, 0.0f);
-        for (int k0 = 0; k0 < up; k0++)
-            for (int i = 0; i < 51; i++) rows[(size_t)k0 * kAudioRow + i] = c->audio[(size_t)k0 + (size_t)i * up];
-        if ((rc = c->d_audio_rows.ensure(rows.size()))) return cleanup(rc);
-        if (hipMemcpy(c->d_audio_rows.p, rows.data(), sizeof(float) * rows.size(), hipMemcpyHostToDevice) != hipSuccess)
-            return cleanup(fail(FMRX_EHIP, "tap upload failed"));
-    }
-    c->tune_offsets.assign((size_t)ns, 0);
-    c->wide_offsets.assign((size_t)ns, 0);
-    if ((rc = reset_state(c))) return cleanup(rc);
+        return failed(fail(FMRX_EHIP, "hipStreamCreate failed"));
+    if ((rc = init_front(c)) || (rc = init_audio(c)) || (rc = init_rds_front(c)) || (rc = init_rds_bits(c)) ||
+        (rc = reset_state(c)))
+        return failed(rc);
     *out = c;
     return FMRX_OK;
 }
 
+// Every buffer and event of the context frees itself when `delete` runs the members' destructors, so the
+// order here is the invariant: the device is set before anything is freed, and every stream that may
+// still read a buffer is synchronised before the first one goes.  The events are destroyed with their
+// holders after the streams; all of them have completed by then.
 void fmrx_destroy(fmrx_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->d_audio.release(); c->d_rf.release(); c->d_audio_rows.release(); c->d_halo[0].release(); c->d_halo[1].release();
-    c->d_audio_hist.release(); c->d_demod.release(); c->d_channel.release(); c->d_carrier.release();
-    c->d_pll.release(); c->d_mix_tail.release(); c->d_mono_state.release(); c->d_in.release();
-    c->d_out.release(); c->d_f32.release(); c->d_scratch.release(); c->d_sintab.release();
-    c->h_in.release(); c->h_out.release();
-    c->d_pll_side.release(); c->d_pll_side2.release();
-    c->d_rds_taps.release(); c->d_rds_dhist.release(); c->d_rds_chan.release(); c->d_rds_car.release();
-    c->d_rds_pll.release();
-    c->d_rdsb_taps.release(); c->d_rdsb_hist.release(); c->d_rdsb_state.release(); c->d_rdsb_work.release();
-    c->d_rdsb_mix.release(); c->d_rdsb_out.release();
-    c->d_rdss_table.release(); c->d_rdss_carry.release(); c->d_rdss_work.release(); c->d_rdss_in.release();
-    c->d_rdss_blocks.release(); c->d_rdss_counts.release();
-    c->d_tune_tab.release(); c->d_tune_streams.release();
-    c->d_scan_tab.release(); c->d_scan_part.release(); c->d_scan_power.release(); c->d_scan_in.release();
-    c->d_wide_hist.release(); c->d_wide_taps.release(); c->d_wide_tab.release(); c->d_wide_streams.release();
-    c->d_wide_y.release(); c->d_wide_halo[0].release(); c->d_wide_halo[1].release();
-    c->d_deemph_taps.release(); c->d_deemph_state[0].release(); c->d_deemph_state[1].release();
-    c->d_deemph_x.release(); c->d_deemph_tmp.release();
-    c->d_meter_tab.release(); c->d_meter_pow.release();
-    for (auto& e : c->evs) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    c->stage_timer.release();
-    if (c->s_front) (void)hipStreamSynchronize(c->s_front);
-    if (c->s_audio) (void)hipStreamSynchronize(c->s_audio);
-    for (auto e : c->pipe_ev) (void)hipEventDestroy(e);
-    if (c->s_front) (void)hipStreamDestroy(c->s_front);
-    if (c->s_audio) (void)hipStreamDestroy(c->s_audio);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (hipStream_t s : {c->stream, c->stereo.s_front, c->stereo.s_audio})
+        if (s) (void)hipStreamSynchronize(s);
+    for (hipStream_t s : {c->stereo.s_front, c->stereo.s_audio, c->stream})
+        if (s) (void)hipStreamDestroy(s);
     delete c;
 }
 
 int fmrx_history_bytes(const fmrx_ctx* c, size_t* bytes) {
     CtxLock lock_(c);
     if (!c || !bytes) return fail(FMRX_EINVAL, "null argument");
-    *bytes = c->halo_bytes;
+    *bytes = c->front.halo_bytes;
     return FMRX_OK;
 }
 
@@ -406,20 +280,20 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     CtxLock lock_(c);
     if (!c || (!prev && n > 0)) return fail(FMRX_EINVAL, "bad argument");
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
-    if (c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
-    if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_seek: not with de-emphasis on (its carry has no seek)");
-    if (n % c->pair_bytes != 0)
-        return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->pair_bytes);
+    if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
+    if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_seek: not with de-emphasis on (its carry has no seek)");
+    if (n % c->front.pair_bytes != 0)
+        return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->front.pair_bytes);
     int rc = set_device(c);
     if (rc) return rc;
-    const size_t ns = c->cfg.n_streams, hb = c->halo_bytes, m = std::min(n, hb);
-    uint8_t* h = c->d_halo[c->halo_cur].p;
+    const size_t ns = c->cfg.n_streams, hb = c->front.halo_bytes, m = std::min(n, hb);
+    uint8_t* h = c->front.halo.cur();
     if (m < hb) HIPCHK(hipMemset2DAsync(h, hb, iq_zero_byte(c), hb - m, ns, c->stream));
     if (m > 0)
         HIPCHK(hipMemcpy2DAsync(h + (hb - m), hb, prev + (n - m), n, m, ns,
                                 prev_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     if (!prev_on_device) HIPCHK(hipStreamSynchronize(c->stream));  // prev may be freed on return
-    c->audio_hist_stale = true;
+    c->mono.stale = true;
     return FMRX_OK;
 }
 
@@ -441,11 +315,9 @@ int fmrx_set_deemphasis(fmrx_ctx* c, int tau_us) {
     HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the carry
     if (tau_us) {
         const size_t rows = (size_t)c->cfg.n_streams * (size_t)c->cfg.channels;
-        if ((rc = ensure_deemph_taps(c)) || (rc = c->d_deemph_state[0].ensure(rows * kDeemphHist)) ||
-            (rc = c->d_deemph_state[1].ensure(rows * kDeemphHist)))
-            return rc;
+        if ((rc = ensure_deemph_taps(c)) || (rc = c->deemph.state.ensure(rows * kDeemphHist))) return rc;
     }
-    c->deemph_tau = tau_us;
+    c->deemph.tau = tau_us;
     if ((rc = reset_deemph(c))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return FMRX_OK;
@@ -454,7 +326,7 @@ int fmrx_set_deemphasis(fmrx_ctx* c, int tau_us) {
 int fmrx_deemphasis(const fmrx_ctx* c, int* tau_us) {
     CtxLock lock_(c);
     if (!c || !tau_us) return fail(FMRX_EINVAL, "null argument");
-    *tau_us = c->deemph_tau;
+    *tau_us = c->deemph.tau;
     return FMRX_OK;
 }
 
@@ -463,7 +335,7 @@ int fmrx_state_size(const fmrx_ctx* c, size_t* bytes) {
     CtxLock lock_(c);
     if (!c || !bytes) return fail(FMRX_EINVAL, "null argument");
     const size_t ns = c->cfg.n_streams;
-    *bytes = kStateHdrWords * sizeof(uint32_t) + ns * (c->halo_bytes + sizeof(float) * (c->audio_hist + kDemodHist + 8 + kMixTail + 8));
+    *bytes = kStateHdrWords * sizeof(uint32_t) + ns * (c->front.halo_bytes + sizeof(float) * (c->mono.hist_len + kDemodHist + 8 + kMixTail + 8));
     return FMRX_OK;
 }
 
@@ -491,9 +363,9 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
     // the blob, so fmrx_audio_block refuses the stale history there too) and the raw I/Q format
     // (bits 8-15), which must match
     uint32_t hdr[kStateHdrWords] = {kStateMagic, kStateVersion, (uint32_t)c->cfg.mode, (uint32_t)c->cfg.channels,
-                                    (uint32_t)c->geo.rf_taps, (uint32_t)c->cfg.n_streams, (uint32_t)c->halo_bytes,
-                                    (uint32_t)c->audio_hist,
-                                    (c->audio_hist_stale ? 1u : 0u) | ((uint32_t)c->iq_format << 8), 0u};
+                                    (uint32_t)c->geo.rf_taps, (uint32_t)c->cfg.n_streams, (uint32_t)c->front.halo_bytes,
+                                    (uint32_t)c->mono.hist_len,
+                                    (c->mono.stale ? 1u : 0u) | ((uint32_t)c->front.format << 8), 0u};
     if (put) {
         uint32_t got[kStateHdrWords];
         std::memcpy(got, buf, sizeof got);
@@ -504,9 +376,9 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
         // word 8, bits 8-15: the raw I/Q format of the halo bytes (0 = u8: the blobs from before the
         // bits had a meaning carry 0 there and stay valid); checked before the shape, whose halo word
         // the format changes
-        if ((got[8] & ~0xFF01u) == 0u && (got[8] >> 8) != (uint32_t)c->iq_format)
+        if ((got[8] & ~0xFF01u) == 0u && (got[8] >> 8) != (uint32_t)c->front.format)
             return fail(FMRX_ESTATE, "state blob holds input format %u, the context is set to %d", got[8] >> 8,
-                        c->iq_format);
+                        c->front.format);
         if (std::memcmp(hdr + 2, got + 2, 6 * sizeof(uint32_t)) != 0)
             return fail(FMRX_ESTATE, "state blob is for another context shape (mode %u, channels %u, rf_taps %u, "
                         "%u streams)", got[2], got[3], got[4], got[5]);
@@ -516,25 +388,24 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
         std::memcpy(buf, hdr, sizeof hdr);
     }
     const size_t ns = c->cfg.n_streams;
-    if (put && (rc = ensure_demod(c, 1))) return rc;
-    if (!put && !c->d_demod.p && (rc = ensure_demod(c, 1))) return rc;
+    if ((rc = ensure_demod(c, 1))) return rc;  // rows that hold the history at least
     BlobIO b{buf + sizeof hdr, put};
-    if ((rc = b.io(c, c->d_halo[c->halo_cur].p, ns * c->halo_bytes))) return rc;
-    if ((rc = b.io(c, c->d_audio_hist.p, ns * sizeof(float) * c->audio_hist))) return rc;
+    if ((rc = b.io(c, c->front.halo.cur(), ns * c->front.halo_bytes))) return rc;
+    if ((rc = b.io(c, c->mono.hist.p, ns * sizeof(float) * c->mono.hist_len))) return rc;
     // demod history: kDemodHist floats in front of each stream's row (one 2-D copy)
     {
-        const size_t w = sizeof(float) * kDemodHist, pitch = sizeof(float) * c->demod_stride;
-        if (put) HIPCHK(hipMemcpy2DAsync(c->d_demod.p, pitch, b.p, w, w, ns, hipMemcpyHostToDevice, c->stream));
-        else HIPCHK(hipMemcpy2DAsync(b.p, w, c->d_demod.p, pitch, w, ns, hipMemcpyDeviceToHost, c->stream));
+        const size_t w = sizeof(float) * kDemodHist, pitch = sizeof(float) * c->stereo.demod_stride;
+        if (put) HIPCHK(hipMemcpy2DAsync(c->stereo.demod.p, pitch, b.p, w, w, ns, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemcpy2DAsync(b.p, w, c->stereo.demod.p, pitch, w, ns, hipMemcpyDeviceToHost, c->stream));
         b.p += w * ns;
     }
-    if ((rc = b.io(c, c->d_pll.p, ns * sizeof(float) * 8))) return rc;
+    if ((rc = b.io(c, c->stereo.pll.p, ns * sizeof(float) * 8))) return rc;
     // (slots 6-7 of each stream's PLL state are the runners' hand-off within a call, 0 between
     // calls: a blob's values there are not trusted)
     if (put)
-        HIPCHK(hipMemset2DAsync(c->d_pll.p + 6, 8 * sizeof(float), 0, 2 * sizeof(float), ns, c->stream));
-    if ((rc = b.io(c, c->d_mix_tail.p, ns * sizeof(float) * kMixTail))) return rc;
-    if ((rc = b.io(c, c->d_mono_state.p, ns * sizeof(float) * 8))) return rc;
+        HIPCHK(hipMemset2DAsync(c->stereo.pll.p + 6, 8 * sizeof(float), 0, 2 * sizeof(float), ns, c->stream));
+    if ((rc = b.io(c, c->stereo.mix_tail.p, ns * sizeof(float) * kMixTail))) return rc;
+    if ((rc = b.io(c, c->stereo.mono_state.p, ns * sizeof(float) * 8))) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -543,27 +414,27 @@ int state_io(fmrx_ctx* c, uint8_t* buf, size_t bytes, bool put) {
 int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
-    if (c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
-    if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_get_state: not with de-emphasis on (the blob does not hold its carry)");
+    if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_get_state: not with de-emphasis on (the blob does not hold its carry)");
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
 
 int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     CtxLock lock_(c);
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
-    if (c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
-    if (c->deemph_tau) return fail(FMRX_ESTATE, "fmrx_set_state: not with de-emphasis on (the blob does not hold its carry)");
+    if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
+    if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_set_state: not with de-emphasis on (the blob does not hold its carry)");
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
     if (rc == 0) {
         uint32_t flags;
         std::memcpy(&flags, p + 8 * sizeof(uint32_t), sizeof flags);
-        c->audio_hist_stale = (flags & 1u) != 0;
+        c->mono.stale = (flags & 1u) != 0;
         // the streams' trigOffsets (state_io order: halo, audio history, demod history, PLL x 8)
         const size_t ns = c->cfg.n_streams;
         const uint8_t* pll = p + kStateHdrWords * sizeof(uint32_t) +
-                             ns * (c->halo_bytes + sizeof(float) * (c->audio_hist + kDemodHist));
-        fmrx_ctx::TrigTrack t;
+                             ns * (c->front.halo_bytes + sizeof(float) * (c->mono.hist_len + kDemodHist));
+        TrigTrack t;
         t.lo = 16777216.0;
         t.hi = 0.0;
         for (size_t s = 0; s < ns; s++) {
@@ -574,7 +445,7 @@ int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
             t.hi = std::max(t.hi, (double)v);
         }
         if (!t.known) t.lo = t.hi = 0.0;
-        c->pll_trig = t;
+        c->stereo.trig = t;
     }
     return rc;
 }
@@ -586,8 +457,8 @@ int fmrx_synchronize(fmrx_ctx* c) {
     if (e != hipSuccess) {
         // an asynchronous fault of an enqueued launch: the device state no longer follows the
         // host's trigOffset bounds, so the runner choice falls back to "unknown" until a reset
-        c->pll_trig.known = false;
-        c->rds_trig.known = false;
+        c->stereo.trig.known = false;
+        c->rds.trig.known = false;
         return fail(FMRX_EHIP, "stream synchronize failed: %s", hipGetErrorString(e));
     }
     return FMRX_OK;
@@ -601,20 +472,17 @@ int fmrx_kernel_timing(fmrx_ctx* c, int reset, double* avg_ms, long* launches) {
     int rc = set_device(c);
     if (rc) return rc;
     double total = 0.0;
-    if (c->ev_used) HIPCHK(hipEventSynchronize(c->evs[c->ev_used - 1].second));
-    for (size_t i = 0; i < c->ev_used; i++) {
+    if (c->diag.ev_used) HIPCHK(hipEventSynchronize(c->diag.evs[c->diag.ev_used - 1].second));
+    for (size_t i = 0; i < c->diag.ev_used; i++) {
         float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, c->evs[i].first, c->evs[i].second));
+        HIPCHK(hipEventElapsedTime(&ms, c->diag.evs[i].first, c->diag.evs[i].second));
         total += ms;
     }
-    if (avg_ms) *avg_ms = c->ev_used ? total / (double)c->ev_used : 0.0;
-    if (launches) *launches = (long)c->ev_used;
-    if (reset > 0) {  // reset > 0: clear and arm event timing of the fused kernel
-        c->ev_used = 0;
-        c->timing = true;
-    } else if (reset < 0) {  // reset < 0: clear and disarm
-        c->ev_used = 0;
-        c->timing = false;
+    if (avg_ms) *avg_ms = c->diag.ev_used ? total / (double)c->diag.ev_used : 0.0;
+    if (launches) *launches = (long)c->diag.ev_used;
+    if (reset) {  // reset > 0: clear and arm event timing of the fused kernel; reset < 0: clear and disarm
+        c->diag.ev_used = 0;
+        c->diag.timing = reset > 0;
     }
     return FMRX_OK;
 }
@@ -626,7 +494,7 @@ int fmrx_debug_stage_timing(fmrx_ctx* c, int op, double* ms, double* steps, long
     if (!c) return fail(FMRX_EINVAL, "null context");
     int rc = set_device(c);
     if (rc) return rc;
-    StageTimer& T = c->stage_timer;
+    StageTimer& T = c->diag.timer;
     if (op == 1) {
         T.on = true;
         T.used = 0;

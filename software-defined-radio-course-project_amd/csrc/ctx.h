@@ -10,6 +10,7 @@
 #include <limits>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -38,57 +39,74 @@ constexpr int kAudioHist50 = 50;  // demod samples a resampler output reads befo
 // and hipMemcpyAsync, whose DMA beats kernels reading host memory at that size)
 constexpr size_t kPinnedCallBytes = (size_t)4 << 20;
 
-template <class T>
-struct DevBuf {
+// Memory of `count` T that its holder owns, on the device or (kPinned) pinned on the host: grown by
+// ensure() (the old contents are dropped), given back by release() or by the destructor.  Never copied;
+// moved only where a grown buffer replaces the one it preserves (engine.cpp grow_rows).  A context's
+// buffers are freed by `delete` in fmrx_destroy, once the device is set and every stream is drained.
+template <class T, bool kPinned>
+struct Buf {
     T* p = nullptr;
     size_t n = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(Buf&& o) noexcept {  // (so no copy assignment either) o leaves with this one's old memory
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~Buf() { release(); }
     int ensure(size_t count) {
         if (count <= n) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
-            p = nullptr;
-            return fail(FMRX_ENOMEM, "hipMalloc of %zu bytes failed", count * sizeof(T));
-        }
+        release();
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        void* q = nullptr;
+        if ((kPinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes)) != hipSuccess)
+            return fail(FMRX_ENOMEM, "%s of %zu bytes failed", kPinned ? "hipHostMalloc" : "hipMalloc", count * sizeof(T));
+        p = static_cast<T*>(q);
         n = count;
         return 0;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
         p = nullptr;
         n = 0;
     }
 };
-
+template <class T>
+using DevBuf = Buf<T, false>;
 // Pinned host memory, mapped into the device's address space (hipHostMalloc: kernels read and
 // write it through the same pointer): the staging of the host-buffer entry points' small calls
 // (the reference's per-block seam, project.cpp:48-84 / 132-196): the input goes to the device by
 // DMA from it, the kernels write their output into it in place -- one copy operation on the stream
 // and one host memcpy each way.
 template <class T>
-struct PinnedBuf {
-    T* p = nullptr;
-    size_t n = 0;
+using PinnedBuf = Buf<T, true>;
+static_assert(!std::is_copy_constructible_v<DevBuf<float>> && !std::is_copy_assignable_v<DevBuf<float>>);
+static_assert(!std::is_copy_constructible_v<PinnedBuf<float>> && !std::is_copy_assignable_v<PinnedBuf<float>>);
+
+// Two device buffers and a cursor: a launch reads cur() and writes next(), the host flips once the
+// launch is enqueued; a reset rewinds to the first buffer.
+template <class T>
+struct PingPong {
+    DevBuf<T> buf[2];
+    int at = 0;
+    T* cur() const { return buf[at].p; }
+    T* next() const { return buf[at ^ 1].p; }
+    void flip() { at ^= 1; }
+    void rewind() { at = 0; }
     int ensure(size_t count) {
-        if (count <= n) return 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault) !=
-            hipSuccess) {
-            p = nullptr;
-            return fail(FMRX_ENOMEM, "hipHostMalloc of %zu bytes failed", count * sizeof(T));
-        }
-        n = count;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
+        const int rc = buf[0].ensure(count);
+        return rc ? rc : buf[1].ensure(count);
     }
 };
+
+// src into d, grown to count, by a blocking copy (creation's tables; `what` words the failure)
+template <class T>
+int upload(DevBuf<T>& d, const T* src, size_t count, const char* what) {
+    const int rc = d.ensure(count);
+    if (rc) return rc;
+    return hipMemcpy(d.p, src, sizeof(T) * count, hipMemcpyHostToDevice) == hipSuccess ? 0 : fail(FMRX_EHIP, "%s failed", what);
+}
 
 using TimingPair = std::pair<hipEvent_t, hipEvent_t>;
 
@@ -109,143 +127,199 @@ struct CaptureRatio {
     size_t size_factor() const { return (size_t)((down + up - 1) / up); }
 };
 
+// bounds on the streams' trigOffset (PllHint) of the stereo and the RDS PLL: 0 after a reset,
+// advanced by every call's samples (the float increments stick at 2^24), re-read from the
+// blob by fmrx_set_state; unknown after a failed launch
+struct TrigTrack {
+    bool known = true;
+    double lo = 0.0, hi = 0.0;
+    void advance(size_t n) {
+        lo = std::min(lo + (double)n, 16777216.0);
+        hi = std::min(hi + (double)n, 16777216.0);
+    }
+};
+
 // The members of fmrx_ctx (below: the ABI's opaque type lives outside the namespace).
 struct Ctx {
     mutable std::recursive_mutex mu;  // every entry point holds it: one call on a context at a time
     fmrx_config cfg{};
     fmrx_geometry_t geo{};
-    ModeConstants mc{};
     hipStream_t stream = nullptr;
-    // taps (host) and device copies
-    std::vector<float> rf, audio, ch, ca;
-    MonoTaps mono_taps{};
-    DevBuf<float> d_audio, d_rf;
-    DevBuf<float> d_audio_rows;   // modes 2/3: the audio prototype by phase (kAudioRow floats per row)
-    // RF state: the raw bytes preceding the next call, double-buffered
-    size_t halo_bytes = 0;                    // halo_pairs * pair_bytes
-    size_t halo_pairs = 0;
-    int iq_format = kIqU8;                    // fmrx_set_input_format: the raw I/Q format of every stream
-    size_t pair_bytes = 2;                    // bytes an I/Q pair of it
-    DevBuf<uint8_t> d_halo[2];
-    int halo_cur = 0;
-    // audio state of the mono product: last (audio_taps_total - 1) demod samples
-    int audio_hist = 0;
-    DevBuf<float> d_audio_hist;
-    bool audio_hist_stale = false;  // after fmrx_seek, until a fused call refreshes it
-    // stereo engine state
-    DevBuf<float> d_demod;        // n_streams x (kDemodHist + cap_if)
-    size_t demod_stride = 0;
-    DevBuf<float> d_channel, d_carrier;
-    DevBuf<float> d_pll;          // n_streams x 8
-    DevBuf<float> d_mix_tail;     // n_streams x kMixTail
-    DevBuf<float> d_mono_state;   // n_streams x 8
-    // RDS front half state (project.cpp:200-271; not part of the checkpoint blob)
-    DevBuf<float> d_rds_taps;     // 54-60 kHz taps, then 113.5-114.5 kHz taps
-    DevBuf<float> d_rds_dhist;    // n_streams x kRdsDemodHist
-    DevBuf<float> d_rds_chan;     // n_streams x (kRdsChanHist + cap)
-    size_t rds_chan_stride = 0;
-    DevBuf<float> d_rds_car;      // n_streams x cap
-    DevBuf<float> d_rds_pll;      // n_streams x 8
-    // RDS back half state (rds_bits.hip; not part of the checkpoint blob either)
-    DevBuf<float> d_rdsb_taps;    // kRdsbTaps: impulseResponseLPF(19 bp_fs, 3000, 1919, 19)
-    DevBuf<float> d_rdsb_hist;    // n_streams x kRdsbHist mixer samples in front of the next call
-    DevBuf<uint8_t> d_rdsb_state; // n_streams x kRdsbStateBytes
-    DevBuf<uint8_t> d_rdsb_work;  // a call's signs, phases, last chips and symbols
-    DevBuf<float> d_rdsb_mix;     // fmrx_rds_decode*: the front half's mixer rows
-    DevBuf<uint8_t> d_rdsb_out;   // fmrx_rds_decode*: bits, then codes
-    std::vector<uint8_t> rdsb_host;       // their host copy, read by the parser
-    size_t rdsb_pending = 0;              // symbols a stream of a decode enqueued and not yet parsed
-    std::vector<fmrx_rds_info> rds_info;  // n_streams
-    bool rds_on = false;                  // fmrx_set_rds
+    int n_simd = 1024;                        // SIMDs of cfg.device (4 per CU), set at creation
+    // One struct a stage: the buffers, strides, switches, host copies and pending counters it owns.  A
+    // buffer added to one of them needs no edit outside that struct and the stage's own code.
+    // The first: the filter taps on the host and their device copies, designed and uploaded at creation.
+    struct Taps {
+        std::vector<float> rf, audio, ch, ca;
+        MonoTaps mono{};
+        DevBuf<float> d_audio, d_rf;
+        DevBuf<float> d_audio_rows;   // modes 2/3: the audio prototype by phase (kAudioRow floats per row)
+    } taps;
+    // The raw-I/Q front: the raw bytes preceding the next call, double-buffered (in the checkpoint blob;
+    // allocated at creation, regrown by fmrx_set_input_format).
+    struct Front {
+        size_t halo_bytes = 0;        // halo_pairs * pair_bytes
+        size_t halo_pairs = 0;
+        int format = kIqU8;           // fmrx_set_input_format: the raw I/Q format of every stream
+        size_t pair_bytes = 2;        // bytes an I/Q pair of it
+        PingPong<uint8_t> halo;
+    } front;
+    // Audio state of the mono product: the last hist_len (audio_taps_total - 1) demod samples a stream (in the
+    // blob; allocated at creation).
+    struct MonoAudio {
+        int hist_len = 0;
+        DevBuf<float> hist;
+        bool stale = false;           // after fmrx_seek, until a fused call refreshes it
+    } mono;
+    // The stereo engine.  Demod history, PLL state, mix tail and mono state are in the blob and allocated at
+    // creation; the rows grow with the calls; the pipelined engine (run_stereo_pipelined) creates its
+    // front-end / band-pass stream, audio stream and events at the first pipelined call.
+    struct Stereo {
+        DevBuf<float> demod;          // n_streams x (kDemodHist + cap_if)
+        size_t demod_stride = 0;
+        DevBuf<float> channel, carrier;
+        DevBuf<float> pll;            // n_streams x 8
+        DevBuf<float> mix_tail;       // n_streams x kMixTail
+        DevBuf<float> mono_state;     // n_streams x 8
+        DevBuf<double> pll_side;      // PLL side data of one segment (pll_side_doubles)
+        DevBuf<double> pll_side2;     // the pipelined engine's second one (odd chunks: their NCO runs
+                                      //   on the audio stream while the next chunk's PLL fills the first)
+        TrigTrack trig;
+        hipStream_t s_front = nullptr, s_audio = nullptr;  // destroyed by fmrx_destroy, with the context stream
+        std::vector<hipEvent_t> pipe_ev;
+        ~Stereo() {
+            for (auto e : pipe_ev) (void)hipEventDestroy(e);
+        }
+    } stereo;
+    // RDS front half (project.cpp:200-271; not part of the checkpoint blob): taps, history and PLL state at
+    // creation, the rows grown with the calls.
+    struct RdsFront {
+        DevBuf<float> taps;           // 54-60 kHz taps, then 113.5-114.5 kHz taps
+        DevBuf<float> dhist;          // n_streams x kRdsDemodHist
+        DevBuf<float> chan;           // n_streams x (kRdsChanHist + cap)
+        size_t chan_stride = 0;
+        DevBuf<float> car;            // n_streams x cap
+        DevBuf<float> pll;            // n_streams x 8
+        TrigTrack trig;
+    } rds;
+    // RDS back half (rds_bits.hip; not part of the checkpoint blob either): taps, history and state at
+    // creation, the rest grown with the calls.
+    struct RdsBits {
+        DevBuf<float> taps;           // kRdsbTaps: impulseResponseLPF(19 bp_fs, 3000, 1919, 19)
+        DevBuf<float> hist;           // n_streams x kRdsbHist mixer samples in front of the next call
+        DevBuf<uint8_t> state;        // n_streams x kRdsbStateBytes
+        DevBuf<uint8_t> work;         // a call's signs, phases, last chips and symbols
+        DevBuf<float> mix;            // fmrx_rds_decode*: the front half's mixer rows
+        DevBuf<uint8_t> out;          // fmrx_rds_decode*: bits, then codes
+        std::vector<uint8_t> host;    // their host copy, read by the parser
+        size_t pending = 0;           // symbols a stream of a decode enqueued and not yet parsed
+        std::vector<fmrx_rds_info> info;  // n_streams
+        bool on = false;              // fmrx_set_rds
+    } rdsb;
     // RDS block sync (fmrx_set_rds_sync, rds_sync.hip; not part of the checkpoint blob): nothing here is
     // allocated until the switch is first turned on (or fmrx_rds_blocks first runs)
-    bool rds_sync_on = false;             // fmrx_set_rds_sync
-    fmrx_rds_sync_config rdss_cfg{8, 3, 2};  // the constants the streams began with
-    int rdss_table_b = -1;                // the B d_rdss_table holds (-1: none yet)
-    uint64_t rdss_seen = 0;               // bits a stream has been given since the reset
-    uint64_t rdss_judged = 0;             // positions below it are judged
-    DevBuf<uint32_t> d_rdss_table;        // kRdsSyncTable burst patterns
-    DevBuf<uint8_t> d_rdss_carry;         // n_streams x kRdsSyncCarry: the last bits, right-aligned
-    DevBuf<uint32_t> d_rdss_work;         // a call's candidates, records and exact masks
-    DevBuf<uint8_t> d_rdss_in;            // fmrx_rds_blocks: the caller's bit rows
-    DevBuf<fmrx_rds_block_rec> d_rdss_blocks; // the host forms' lists: n_streams x the positions judged
-    DevBuf<uint32_t> d_rdss_counts;       // n_streams
-    std::vector<uint32_t> rdss_counts;    // their host copies: the counts, and rdss_most records a stream
-    std::vector<fmrx_rds_block_rec> rdss_host;
-    size_t rdss_most = 0;
-    bool rdss_pending = false;            // a decode enqueued the stage and has not yet parsed its records
-    size_t rdss_cap = 0, rdss_bits = 0;   //   its list rows and its bits a stream
-    std::vector<fmrx_rds_ext> rds_ext;    // n_streams
-    // staging for the host-buffer entry points
-    DevBuf<uint8_t> d_in;
-    DevBuf<int16_t> d_out;
-    PinnedBuf<uint8_t> h_in, h_out;  // the small host calls' staging (kPinnedCallBytes)
-    DevBuf<float> d_f32;
-    DevBuf<float> d_scratch;
-    DevBuf<double> d_pll_side;    // PLL side data of one segment (pll_side_doubles)
-    DevBuf<double> d_pll_side2;   // the pipelined engine's second one (odd chunks: their NCO runs
-                                  //   on the audio stream while the next chunk's PLL fills the first)
-    DevBuf<int16_t> d_sintab;
-    DevBuf<uint8_t> d_synth_params;  // fmrx_synth_device_streams: SynthParams per stream
-    // kernel timing: pairs of HIP events recorded around each fused-kernel launch on the
-    // context stream (no host sync inside the timed loop); read by fmrx_kernel_timing
-    std::vector<TimingPair> evs;
-    size_t ev_used = 0;
-    bool timing = false;
-    unsigned long long* stamps = nullptr;  // fmrx_debug_mono_stamps (diagnostic)
-    unsigned long long* pll_stats = nullptr;  // fmrx_debug_pll_stats (diagnostic)
-    unsigned* pll_redos = nullptr;            // fmrx_debug_pll_redos (diagnostic)
-    StageTimer stage_timer;                   // fmrx_debug_stage_timing (diagnostic)
-    // the pipelined stereo engine (run_stereo_pipelined): front-end / band-pass stream, audio
-    // stream and their events, created at the first pipelined call
-    hipStream_t s_front = nullptr, s_audio = nullptr;
-    std::vector<hipEvent_t> pipe_ev;
-    int n_simd = 1024;                        // SIMDs of cfg.device (4 per CU), set at creation
-    // off-centre tuning (fmrx_tune): configuration, not part of the state blob
-    bool tuned = false;
-    std::vector<int32_t> tune_offsets;        // n_streams (zeros until fmrx_tune sets them)
-    uint64_t tune_pos = 0;                    // absolute pair index of the next call's first I/Q pair
-    int tune_max_n = 1;                       // the longest rotator period among the streams
-    DevBuf<float> d_tune_tab;                 // the streams' (c, s) tables, one after the other
-    DevBuf<uint32_t> d_tune_streams;          // TunerStream per stream
-    // band scan (fmrx_scan*): scratch of its own, grown on demand; nothing the decode path reads
-    int scan_bins = 0;                        // the transform size d_scan_tab holds (0: none yet)
-    std::vector<float> scan_tab;              // host copy: 2 N twiddle floats, then N window floats
-    DevBuf<float> d_scan_tab;                 // the same on the device
-    DevBuf<float> d_scan_part;                // the launch's partial rows (scan_workgroups x N)
-    DevBuf<float> d_scan_power;               // the host entry points' result, N floats
-    DevBuf<uint8_t> d_scan_in;                // the host entry points' capture
-    // wide captures (fmrx_set_capture_decim, fmrx_set_capture_rate): the capture stage in front of the
-    // tuner (wide.hip or rate.hip, by the ratio); its history, rows and narrow halo are its own, nothing
-    // the ordinary calls read
-    CaptureRatio ratio;                       // cap_fs / rf_fs; 1/1: no wide stage
-    bool wide_tuned = false;                  // fmrx_tune_wide accepted (fmrx_tune turns it off)
-    std::vector<int32_t> wide_offsets;        // n_streams, against cap_fs
-    DevBuf<uint8_t> d_wide_hist;              // the ratio.hist_pairs() raw pairs of the capture in front of the next call
-    DevBuf<float> d_wide_taps;                // the low-pass: 16 down + 1 floats at up = 1, else the RateTap rows by phase
-    DevBuf<float> d_wide_tab;                 // n_streams x kRateMaxN (c, s) pairs: the coarse tables
-    DevBuf<uint32_t> d_wide_streams;          // WideStream per stream
-    DevBuf<float> d_wide_y;                   // n_streams x wide_y_stride floats: one piece's cf32 rows at rf_fs
-    size_t wide_y_stride = 0;
-    DevBuf<uint8_t> d_wide_halo[2];           // the narrow stage's f32 halo (halo_pairs x 8 B a stream)
-    int wide_halo_cur = 0;
-    // FM de-emphasis (fmrx_set_deemphasis, deemph.hip): configuration and a carry of its own; nothing
-    // here is allocated until it is first turned on (or fmrx_deemph first runs)
-    int deemph_tau = 0;                       // 0 off, 50 or 75 us
-    DevBuf<float> d_deemph_taps;              // 2 x kDeemphTaps: the context's audio rate at 50, then at 75 us
-    DevBuf<float> d_deemph_state[2];          // n_streams x channels x kDeemphHist inputs in front of the next call
-    int deemph_cur = 0;
-    DevBuf<float> d_deemph_x;                 // a call's floats in front of the quantiser (4 B a sample and channel)
-    DevBuf<float> d_deemph_tmp;               // fmrx_deemph: the caller's next state, before it is copied back
+    struct RdsSync {
+        bool on = false;                      // fmrx_set_rds_sync
+        fmrx_rds_sync_config cfg{8, 3, 2};    // the constants the streams began with
+        int table_b = -1;                     // the B `table` holds (-1: none yet)
+        uint64_t seen = 0;                    // bits a stream has been given since the reset
+        uint64_t judged = 0;                  // positions below it are judged
+        DevBuf<uint32_t> table;               // kRdsSyncTable burst patterns
+        DevBuf<uint8_t> carry;                // n_streams x kRdsSyncCarry: the last bits, right-aligned
+        DevBuf<uint32_t> work;                // a call's candidates, records and exact masks
+        DevBuf<uint8_t> in;                   // fmrx_rds_blocks: the caller's bit rows
+        DevBuf<fmrx_rds_block_rec> blocks;    // the host forms' lists: n_streams x the positions judged
+        DevBuf<uint32_t> counts;              // n_streams
+        std::vector<uint32_t> counts_host;    // their host copies: the counts, and `most` records a stream
+        std::vector<fmrx_rds_block_rec> host;
+        size_t most = 0;
+        bool pending = false;                 // a decode enqueued the stage and has not yet parsed its records
+        size_t cap = 0, bits = 0;             //   its list rows and its bits a stream
+        std::vector<fmrx_rds_ext> ext;        // n_streams
+    } rdss;
     // subcarrier meter (fmrx_set_meter, meter.hip): no signal state; nothing here is allocated until the
     // switch is first turned on (or fmrx_meter first runs)
-    bool meter_on = false;                    // fmrx_set_meter
-    int meter_p = 0;                          // samples a window (bp_fs / 1000) once d_meter_tab is filled
-    DevBuf<float> d_meter_tab;                // the 14 tables of fmrx_meter_design
-    DevBuf<float> d_meter_pow;                // a call's powers: n_streams x frames x 7
-    std::vector<float> meter_host;            // their host copy
-    size_t meter_pending = 0;                 // frames a stream of a call enqueued and not yet added
-    std::vector<fmrx_meter_report> meter_rep; // n_streams
+    struct Meter {
+        bool on = false;                      // fmrx_set_meter
+        int p = 0;                            // samples a window (bp_fs / 1000) once `tab` is filled
+        DevBuf<float> tab;                    // the 14 tables of fmrx_meter_design
+        DevBuf<float> pow;                    // a call's powers: n_streams x frames x 7
+        std::vector<float> host;              // their host copy
+        size_t pending = 0;                   // frames a stream of a call enqueued and not yet added
+        std::vector<fmrx_meter_report> rep;   // n_streams
+    } meter;
+    // FM de-emphasis (fmrx_set_deemphasis, deemph.hip): configuration and a carry of its own, not in the
+    // blob; nothing here is allocated until it is first turned on (or fmrx_deemph first runs)
+    struct Deemph {
+        int tau = 0;                          // 0 off, 50 or 75 us
+        DevBuf<float> taps;                   // 2 x kDeemphTaps: the context's audio rate at 50, then at 75 us
+        PingPong<float> state;                // n_streams x channels x kDeemphHist inputs in front of the next call
+        DevBuf<float> x;                      // a call's floats in front of the quantiser (4 B a sample and channel)
+        DevBuf<float> tmp;                    // fmrx_deemph: the caller's next state, before it is copied back
+    } deemph;
+    // off-centre tuning (fmrx_tune): configuration, not part of the state blob; the tables are allocated
+    // by the first fmrx_tune or by a format other than u8
+    struct Tuner {
+        bool on = false;
+        std::vector<int32_t> offsets;         // n_streams (zeros until fmrx_tune sets them)
+        uint64_t pos = 0;                     // absolute pair index of the next call's first I/Q pair
+        int max_n = 1;                        // the longest rotator period among the streams
+        DevBuf<float> tab;                    // the streams' (c, s) tables, one after the other
+        DevBuf<uint32_t> streams;             // TunerStream per stream
+    } tune;
+    // wide captures (fmrx_set_capture_decim, fmrx_set_capture_rate): the capture stage in front of the
+    // tuner (wide.hip or rate.hip, by the ratio); its history, rows and narrow halo are its own, nothing
+    // the ordinary calls read or the blob holds; allocated when a ratio other than 1/1 is set
+    struct Wide {
+        CaptureRatio ratio;                   // cap_fs / rf_fs; 1/1: no wide stage
+        bool tuned = false;                   // fmrx_tune_wide accepted (fmrx_tune turns it off)
+        std::vector<int32_t> offsets;         // n_streams, against cap_fs
+        DevBuf<uint8_t> hist;                 // the ratio.hist_pairs() raw pairs of the capture in front of the next call
+        DevBuf<float> taps;                   // the low-pass: 16 down + 1 floats at up = 1, else the RateTap rows by phase
+        DevBuf<float> tab;                    // n_streams x kRateMaxN (c, s) pairs: the coarse tables
+        DevBuf<uint32_t> streams;             // WideStream per stream
+        DevBuf<float> y;                      // n_streams x y_stride floats: one piece's cf32 rows at rf_fs
+        size_t y_stride = 0;
+        PingPong<uint8_t> halo;               // the narrow stage's f32 halo (halo_pairs x 8 B a stream)
+    } wide;
+    // band scan (fmrx_scan*): scratch of its own, grown on demand; nothing the decode path reads
+    struct Scan {
+        int bins = 0;                         // the transform size `tab` holds (0: none yet)
+        std::vector<float> tab_host;          // host copy: 2 N twiddle floats, then N window floats
+        DevBuf<float> tab;                    // the same on the device
+        DevBuf<float> part;                   // the launch's partial rows (scan_workgroups x N)
+        DevBuf<float> power;                  // the host entry points' result, N floats
+        DevBuf<uint8_t> in;                   // the host entry points' capture
+    } scan;
+    // staging for the host-buffer entry points and the primitives' scratch, grown with the calls
+    struct Staging {
+        DevBuf<uint8_t> d_in;
+        DevBuf<int16_t> d_out;
+        PinnedBuf<uint8_t> h_in, h_out;       // the small host calls' staging (kPinnedCallBytes)
+        DevBuf<float> f32;
+        DevBuf<float> scratch;
+    } io;
+    // the synthetic input: the sine table (creation) and fmrx_synth_device_streams' SynthParams per stream
+    struct Synth {
+        DevBuf<int16_t> sintab;
+        DevBuf<uint8_t> params;
+    } synth;
+    // diagnostics.  Kernel timing: pairs of HIP events recorded around each fused-kernel launch on the
+    // context stream (no host sync inside the timed loop); read by fmrx_kernel_timing.  The three raw
+    // pointers are device memory of the caller's: never owned, never freed here.
+    struct Diag {
+        std::vector<TimingPair> evs;
+        size_t ev_used = 0;
+        bool timing = false;
+        unsigned long long* stamps = nullptr;     // fmrx_debug_mono_stamps (caller-owned)
+        unsigned long long* pll_stats = nullptr;  // fmrx_debug_pll_stats (caller-owned)
+        unsigned* pll_redos = nullptr;            // fmrx_debug_pll_redos (caller-owned)
+        StageTimer timer;                         // fmrx_debug_stage_timing
+        ~Diag() {
+            for (auto& e : evs) (void)hipEventDestroy(e.first), (void)hipEventDestroy(e.second);
+            timer.release();
+        }
+    } diag;
     // switches (fmrx_debug_set_knob): the tuning ones from the environment once, at creation;
     // none of them changes the output (the PLL test hooks make the runners redo work)
     struct Knobs {
@@ -260,26 +334,15 @@ struct Ctx {
         int bpf_tile = 1;       // 0: the per-output band-pass kernel
         int halo_kernel = 0;    // 1: the separate halo_kernel after the fused one
     } knobs;
-    // bounds on the streams' trigOffset (PllHint) of the stereo and the RDS PLL: 0 after a reset,
-    // advanced by every call's samples (the float increments stick at 2^24), re-read from the
-    // blob by fmrx_set_state; unknown after a failed launch
-    struct TrigTrack {
-        bool known = true;
-        double lo = 0.0, hi = 0.0;
-        void advance(size_t n) {
-            lo = std::min(lo + (double)n, 16777216.0);
-            hi = std::min(hi + (double)n, 16777216.0);
-        }
-    } pll_trig, rds_trig;
     PllHint hint(const TrigTrack& t) const {
         PllHint h;
         h.n_simd = n_simd;
         h.knobs = knobs.pll;
-        h.redos = pll_redos;
+        h.redos = diag.pll_redos;
         h.known = t.known;
         h.trig_lo = t.lo;
         h.trig_hi = t.hi;
-        h.timer = stage_timer.on ? const_cast<StageTimer*>(&stage_timer) : nullptr;
+        h.timer = diag.timer.on ? const_cast<StageTimer*>(&diag.timer) : nullptr;
         return h;
     }
 };
@@ -308,13 +371,13 @@ class CtxLock {
 };
 
 // The byte that fills a run of x = 0.0 samples of the context's format
-inline int iq_zero_byte(const fmrx_ctx* c) { return c->iq_format == kIqU8 ? 0x80 : 0; }
+inline int iq_zero_byte(const fmrx_ctx* c) { return c->front.format == kIqU8 ? 0x80 : 0; }
 // Bytes a block of one stream's raw I/Q takes in the context's format (geo.block_bytes for u8)
-inline size_t iq_block_bytes(const fmrx_ctx* c) { return c->geo.iq_pairs * c->pair_bytes; }
+inline size_t iq_block_bytes(const fmrx_ctx* c) { return c->geo.iq_pairs * c->front.pair_bytes; }
 // The calls that take raw I/Q run the tuned front end (tuner.hip) while tuning is on, and always
 // for a format other than u8 (the fused kernels read u8 only): with tuning off the context's
 // tables then hold zero offsets, which gives the untuned bits.
-inline bool front_tuned(const fmrx_ctx* c) { return c->tuned || c->iq_format != kIqU8; }
+inline bool front_tuned(const fmrx_ctx* c) { return c->tune.on || c->front.format != kIqU8; }
 // n_streams rows of n_blocks blocks in format bytes must fit size_t with room to spare (a block of
 // f32 is four times a block of u8)
 inline int check_call_size(const fmrx_ctx* c, size_t n_blocks, size_t decim = 1) {
@@ -324,15 +387,18 @@ inline int check_call_size(const fmrx_ctx* c, size_t n_blocks, size_t decim = 1)
     return 0;
 }
 // Wide pairs that n_blocks narrow blocks take (n_blocks a whole number of granules)
-inline size_t wide_pairs_of(const fmrx_ctx* c, size_t n_blocks) { return c->ratio.pairs_of(n_blocks, c->geo.iq_pairs); }
+inline size_t wide_pairs_of(const fmrx_ctx* c, size_t n_blocks) { return c->wide.ratio.pairs_of(n_blocks, c->geo.iq_pairs); }
 inline int set_device(const fmrx_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     return 0;
 }
 
+// Every stage that keeps signal state has an init_ (creation: its tables designed and uploaded, its
+// creation-time buffers allocated) and a reset_ (its start state, enqueued on the context stream) beside
+// its code; fmrx_create and reset_state (context.cpp) call them in turn.  pll0: the PLL start vector.
+
 // ---- context.cpp
 int reset_state(fmrx_ctx* c);
-int reset_deemph(fmrx_ctx* c);  // the de-emphasis carry alone, enqueued on the context stream
 // fmrx_kernel_timing around one launch on st: when timing is armed, begin takes the next event pair
 // and records its first event (*ev, null at the call, stays null otherwise); end records the second
 int timing_begin(fmrx_ctx* c, hipStream_t st, TimingPair** ev);
@@ -342,6 +408,11 @@ inline int timing_end(TimingPair* ev, hipStream_t st) {
 }
 
 // ---- engine.cpp
+int init_audio(fmrx_ctx* c);   // the RF and audio taps, the mono history, the stereo state
+int reset_audio(fmrx_ctx* c, const std::vector<float>& pll0);
+int init_rds_front(fmrx_ctx* c);
+int reset_rds_front(fmrx_ctx* c, const std::vector<float>& pll0);
+int reset_deemph(fmrx_ctx* c);  // the de-emphasis carry alone (nothing to do before it was ever on)
 // RF front end (+ the mono audio stage when `with_audio`); the chunk form serves the stereo pipeline
 int run_fused(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm, float* d_mono, float* d_demod,
               size_t demod_stride, int demod_hist, bool with_audio, size_t b0 = 0, size_t call_blocks = 0,
@@ -353,12 +424,7 @@ int run_stereo_pipelined(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int1
 int run_rds(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_if, float* d_out, float* d_nco,
             float* d_channel);
 int ensure_demod(fmrx_ctx* c, size_t n_if);
-// De-emphasis behind an audio stage (fmrx_set_deemphasis on).  deemph_rows: where the stage's float
-// outlet writes a call of na frames a stream -- the caller's d_mono when a mono call gave one, else the
-// context's scratch, grown to the call.  run_deemph: those rows through deemph.hip into d_pcm on the
-// context stream, the carry moved.  The audio rate the taps are designed for: deemph_audio_fs.
-int deemph_rows(fmrx_ctx* c, size_t na, float* d_mono, float** rows);
-int run_deemph(fmrx_ctx* c, const float* rows, size_t na, int16_t* d_pcm);
+// De-emphasis behind an audio stage (fmrx_set_deemphasis on): the taps, and the audio rate they are designed for
 int ensure_deemph_taps(fmrx_ctx* c);
 inline int deemph_audio_fs(const fmrx_ctx* c) { return c->geo.if_fs / c->geo.audio_down; }  // if_fs holds audio_up
 
@@ -366,16 +432,17 @@ inline int deemph_audio_fs(const fmrx_ctx* c) { return c->geo.if_fs / c->geo.aud
 // blocks of an RDS granule (with a capture rate set: the least common multiple with the wide granule's)
 size_t rds_granule_blocks(const fmrx_ctx* c);
 int check_rds_blocks(const fmrx_ctx* c, size_t n_blocks);
-int reset_rds_bits(fmrx_ctx* c);  // the back half's start state, enqueued on the context stream
+int init_rds_bits(fmrx_ctx* c);
+int reset_rds_bits(fmrx_ctx* c);  // the back half's start state (and the block sync's)
 // front half, bits and codes of the rows at d_demod (whole granules), and their copy to the host, enqueued;
-// rds_decode_finish waits for the stream and parses them into rds_info
+// rds_decode_finish waits for the stream and parses them into rdsb.info
 int rds_decode_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
 int rds_decode_finish(fmrx_ctx* c);
 
 // ---- rds_sync_api.cpp
 void reset_rds_sync(fmrx_ctx* c);  // the carry's counters and the extended infos back to the start
 // the block sync over n_bits more bits a stream at d_bits (rows n_bits apart) and the copy of its counts, enqueued;
-// rds_sync_finish waits for the stream, fetches the records and parses them into rds_ext
+// rds_sync_finish waits for the stream, fetches the records and parses them into rdss.ext
 int rds_sync_enqueue(fmrx_ctx* c, const uint8_t* d_bits, size_t n_bits);
 int rds_sync_finish(fmrx_ctx* c);
 
@@ -388,6 +455,9 @@ int meter_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t
 int meter_finish(fmrx_ctx* c);
 
 // ---- front.cpp
+int init_front(fmrx_ctx* c);   // the halo; the tuner's and the wide stage's per-stream offsets
+int reset_front(fmrx_ctx* c);  // the halo and the position; the offsets stay (configuration)
+int reset_wide(fmrx_ctx* c);   // nothing to do at 1/1
 int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,
                     size_t demod_stride, int demod_hist, bool pre_tail);
 int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, int16_t* d_pcm, float* d_mono);

@@ -11,17 +11,16 @@ using namespace fmrx;
 namespace {
 
 // One launch of the tuner kernel over n_blocks blocks a stream: source rows of `format` (iq_stride
-// bytes apart, 0 for a shared capture), the halo pair `halo` of halo_bytes a stream with *cur the
-// one in front of the call, demod rows out.  Flips *cur and advances the position.
-int launch_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, int format, DevBuf<uint8_t>* halo, int* cur,
-                 size_t halo_bytes, size_t n_blocks, float* d_demod, size_t demod_stride, int demod_hist,
+// bytes apart, 0 for a shared capture), the halo pair `halo` of halo_bytes a stream, its current one
+// in front of the call, demod rows out.  Flips the pair and advances the position.
+int launch_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, int format, PingPong<uint8_t>& halo, size_t halo_bytes, size_t n_blocks, float* d_demod, size_t demod_stride, int demod_hist,
                  bool pre_tail) {
     const int ns = c->cfg.n_streams;
     TunerLaunch L{};
     L.iq = d_iq;
     L.iq_stride = iq_stride;
-    L.halo = halo[*cur].p;
-    L.halo_next = halo[*cur ^ 1].p;
+    L.halo = halo.cur();
+    L.halo_next = halo.next();
     L.halo_bytes = halo_bytes;
     L.stream_bytes = n_blocks * c->geo.iq_pairs * (size_t)iq_pair_bytes(format);
     L.format = format;
@@ -30,16 +29,16 @@ int launch_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, int format,
     L.demod_hist = demod_hist;
     L.pre_tail = pre_tail ? 1 : 0;
     L.n_if = (long long)(n_blocks * c->geo.if_samples);
-    L.segs = tuner_segments(L.n_if, c->geo.rf_taps, c->geo.rf_decim, ns, c->n_simd / 4, c->tune_max_n);
-    L.streams = reinterpret_cast<const TunerStream*>(c->d_tune_streams.p);
-    L.tables = reinterpret_cast<const float2*>(c->d_tune_tab.p);
-    L.first_pair = c->tune_pos;
-    const int st_t = c->stage_timer.begin(c->stream);
-    const int rc = launch_tuner(L, ns, c->geo.rf_taps, c->geo.rf_decim, c->tune_max_n, c->mono_taps, c->stream);
-    c->stage_timer.end(st_t, kStFront, 0.0, c->stream);
+    L.segs = tuner_segments(L.n_if, c->geo.rf_taps, c->geo.rf_decim, ns, c->n_simd / 4, c->tune.max_n);
+    L.streams = reinterpret_cast<const TunerStream*>(c->tune.streams.p);
+    L.tables = reinterpret_cast<const float2*>(c->tune.tab.p);
+    L.first_pair = c->tune.pos;
+    const int st_t = c->diag.timer.begin(c->stream);
+    const int rc = launch_tuner(L, ns, c->geo.rf_taps, c->geo.rf_decim, c->tune.max_n, c->taps.mono, c->stream);
+    c->diag.timer.end(st_t, kStFront, 0.0, c->stream);
     if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "tuned front end launch failed (%d)", rc);
-    *cur ^= 1;
-    c->tune_pos += (uint64_t)n_blocks * c->geo.iq_pairs;
+    halo.flip();
+    c->tune.pos += (uint64_t)n_blocks * c->geo.iq_pairs;
     return 0;
 }
 
@@ -47,38 +46,79 @@ int launch_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, int format,
 
 namespace fmrx {
 
+int init_front(fmrx_ctx* c) {
+    const size_t ns = c->cfg.n_streams;
+    c->front.halo_bytes = mono_halo_bytes(c->geo.rf_taps, c->geo.rf_decim, c->geo.audio_down);
+    c->front.halo_pairs = c->front.halo_bytes / 2;
+    c->tune.offsets.assign(ns, 0);
+    c->wide.offsets.assign(ns, 0);
+    return c->front.halo.ensure(c->front.halo_bytes * ns);
+}
+
+// The halo filled with the format's zero; the position back to 0, the offsets stay (configuration)
+int reset_front(fmrx_ctx* c) {
+    PingPong<uint8_t>& h = c->front.halo;
+    c->tune.pos = 0;
+    for (auto& b : h.buf) HIPCHK(hipMemsetAsync(b.p, iq_zero_byte(c), c->front.halo_bytes * c->cfg.n_streams, c->stream));
+    h.rewind();
+    return 0;
+}
+
+// The wide stage: history of the format's zero, narrow halo of 0.0f
+int reset_wide(fmrx_ctx* c) {
+    auto& w = c->wide;
+    if (!w.ratio.on()) return 0;
+    HIPCHK(hipMemsetAsync(w.hist.p, iq_zero_byte(c), w.ratio.hist_pairs() * c->front.pair_bytes, c->stream));
+    for (auto& b : w.halo.buf) HIPCHK(hipMemsetAsync(b.p, 0, c->front.halo_pairs * 8 * c->cfg.n_streams, c->stream));
+    w.halo.rewind();
+    return 0;
+}
+
 // The tuned front end over n_blocks blocks a stream of the context's format: demod rows out, the
 // halo moved, the position advanced.  iq_stride: bytes between the streams' rows, 0 for a shared
 // capture.  pre_tail: also the 50 demod samples in front of the call (at demod_hist - 50, from the
 // halo).
 int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, float* d_demod,
                     size_t demod_stride, int demod_hist, bool pre_tail) {
-    const size_t unit = 2 * c->pair_bytes;  // the kernel's staging unit: two pairs
+    const size_t unit = 2 * c->front.pair_bytes;  // the kernel's staging unit: two pairs
     if (reinterpret_cast<uintptr_t>(d_iq) % unit != 0 || iq_stride % unit != 0)
         return fail(FMRX_EINVAL, "tuned calls need %zu-byte aligned I/Q rows", unit);
     int rc_size = check_call_size(c, n_blocks);
     if (rc_size) return rc_size;
-    return launch_front(c, d_iq, iq_stride, c->iq_format, c->d_halo, &c->halo_cur, c->halo_bytes, n_blocks, d_demod,
+    return launch_front(c, d_iq, iq_stride, c->front.format, c->front.halo, c->front.halo_bytes, n_blocks, d_demod,
                         demod_stride, demod_hist, pre_tail);
 }
 
+// The taps on the demod rows, the meter (fmrx_set_meter) and the RDS decode (fmrx_set_rds), in that
+// order everywhere; a further tap is one line in each of the three.  check_taps: the call is whole
+// granules of every tap that is on (the RDS decode's refusal first).
+static int check_taps(const fmrx_ctx* c, size_t n_blocks) {
+    const int rc = c->rdsb.on ? check_rds_blocks(c, n_blocks) : 0;
+    return rc || !c->meter.on ? rc : check_meter_blocks(c, n_blocks);
+}
+static int taps_enqueue(fmrx_ctx* c, size_t n_blocks) {
+    const float* rows = c->stereo.demod.p + kDemodHist;
+    const int rc = c->meter.on ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
+    return rc || !c->rdsb.on ? rc : rds_decode_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
+}
+static int taps_finish(fmrx_ctx* c) {
+    const int rc = c->meter.on ? meter_finish(c) : 0;
+    return rc || !c->rdsb.on ? rc : rds_decode_finish(c);
+}
+
 // The audio stage of a call whose front end filled the context's demod rows (mono: the polyphase
-// stage; stereo: the non-pipelined engine).  With fmrx_set_rds on, the RDS decode of the same rows
-// goes on the stream in front of it (the audio stage moves the rows' tail afterwards) and is parsed
-// once the call's work is done; the audio stage reads and writes nothing the decode touches.  With
-// fmrx_set_meter on, the meter reads the same rows first and its powers are added to the reports last.
+// stage; stereo: the non-pipelined engine).  The taps read the same rows on the stream in front of it
+// (the audio stage moves the rows' tail afterwards) and are parsed and added once the call's work is
+// done; the audio stage reads and writes nothing they touch.
 static int run_audio_stage(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
     const size_t n_if = n_blocks * c->geo.if_samples;
-    int rc;
-    if (c->meter_on && (rc = meter_enqueue(c, c->d_demod.p + kDemodHist, c->demod_stride, n_blocks))) return rc;
-    if (c->rds_on && (rc = rds_decode_enqueue(c, c->d_demod.p + kDemodHist, c->demod_stride, n_blocks))) return rc;
+    int rc = taps_enqueue(c, n_blocks);
+    if (rc) return rc;
     if (c->cfg.channels != FMRX_MONO)
         rc = run_stereo_audio(c, n_blocks, d_pcm, d_mono);
     else
-        rc = run_mono_audio(c, c->d_demod.p + kDemodHist, c->demod_stride, n_if, d_pcm, d_mono);
-    if (rc) return rc;
-    if (c->meter_on && (rc = meter_finish(c))) return rc;
-    return c->rds_on ? rds_decode_finish(c) : 0;
+        rc = run_mono_audio(c, c->stereo.demod.p + kDemodHist, c->stereo.demod_stride, n_if, d_pcm, d_mono);
+    return rc ? rc : taps_finish(c);
 }
 
 // A tuned call: the front end for the whole call into the context's demod rows, then the audio
@@ -86,24 +126,24 @@ static int run_audio_stage(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* 
 int run_tuned(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n_blocks, int16_t* d_pcm, float* d_mono) {
     const int ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;
-    int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
-    if (rc || (c->meter_on && (rc = check_meter_blocks(c, n_blocks))) || (rc = ensure_demod(c, n_if))) return rc;
+    int rc = check_taps(c, n_blocks);
+    if (rc || (rc = ensure_demod(c, n_if))) return rc;
     if (c->cfg.channels != FMRX_MONO) {
-        if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, false)))
+        if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->stereo.demod.p, c->stereo.demod_stride, kDemodHist, false)))
             return rc;
         return run_audio_stage(c, n_blocks, d_pcm, d_mono);
     }
     // after fmrx_seek the audio history is rebuilt from the halo, as the fused kernel's pre-roll
     // does: the 50 demod samples in front of the call (all a resampler output reads back)
-    const bool stale = c->audio_hist_stale;
-    if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->d_demod.p, c->demod_stride, kDemodHist, stale)))
+    const bool stale = c->mono.stale;
+    if ((rc = run_tuned_front(c, d_iq, iq_stride, n_blocks, c->stereo.demod.p, c->stereo.demod_stride, kDemodHist, stale)))
         return rc;
     if (stale) {
-        if (launch_copy_streams(c->d_audio_hist.p + (c->audio_hist - kAudioHist50), c->audio_hist,
-                                c->d_demod.p + (kDemodHist - kAudioHist50), c->demod_stride, kAudioHist50, ns,
+        if (launch_copy_streams(c->mono.hist.p + (c->mono.hist_len - kAudioHist50), c->mono.hist_len,
+                                c->stereo.demod.p + (kDemodHist - kAudioHist50), c->stereo.demod_stride, kAudioHist50, ns,
                                 c->stream))
             return fail(FMRX_EHIP, "audio history copy failed");
-        c->audio_hist_stale = false;
+        c->mono.stale = false;
     }
     return run_audio_stage(c, n_blocks, d_pcm, d_mono);
 }
@@ -134,10 +174,10 @@ int tuner_upload(fmrx_ctx* c, const int32_t* offsets_hz) {
     for (size_t s = 0; s < ns; s++) tuner_design(c->geo.rf_fs, offsets_hz[s], nullptr, nullptr, tab.data() + 2 * ts[s].tab);
     // a call in flight may still read the old tables: drain the stream before they are replaced
     HIPCHK(hipStreamSynchronize(c->stream));
-    if ((rc = c->d_tune_tab.ensure(tab.size())) || (rc = c->d_tune_streams.ensure(4 * ns))) return rc;
-    HIPCHK(hipMemcpy(c->d_tune_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_tune_streams.p, ts.data(), sizeof(TunerStream) * ns, hipMemcpyHostToDevice));
-    c->tune_max_n = max_n;
+    if ((rc = c->tune.tab.ensure(tab.size())) || (rc = c->tune.streams.ensure(4 * ns))) return rc;
+    HIPCHK(hipMemcpy(c->tune.tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->tune.streams.p, ts.data(), sizeof(TunerStream) * ns, hipMemcpyHostToDevice));
+    c->tune.max_n = max_n;
     return FMRX_OK;
 }
 
@@ -167,9 +207,9 @@ int check_wide_rf_fs(int rf_fs) {
 }
 
 int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks) {
-    if (n_blocks % c->ratio.blocks != 0)  // an integer ratio's granule is one block
+    if (n_blocks % c->wide.ratio.blocks != 0)  // an integer ratio's granule is one block
         return fail(FMRX_EINVAL, "%zu blocks: a call at %d S/s takes whole granules of %zu blocks", n_blocks,
-                    c->ratio.cap_fs(c->geo.rf_fs), c->ratio.blocks);
+                    c->wide.ratio.cap_fs(c->geo.rf_fs), c->wide.ratio.blocks);
     return 0;
 }
 
@@ -178,38 +218,38 @@ int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks) {
 // reading them as an f32 stream with the wide stage's own halo; the demod rows of the whole call then
 // take the audio stage a tuned call takes.  A piece past the first finds its history in the capture itself.
 int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
-    const CaptureRatio& r = c->ratio;
+    const CaptureRatio& r = c->wide.ratio;
     const int ns = c->cfg.n_streams;
     const size_t ip = c->geo.iq_pairs, n_if = n_blocks * c->geo.if_samples, gran = r.blocks;
-    const size_t hb = r.hist_pairs() * c->pair_bytes;
-    int rc = c->rds_on ? check_rds_blocks(c, n_blocks) : 0;
-    if (rc || (c->meter_on && (rc = check_meter_blocks(c, n_blocks))) || (rc = ensure_demod(c, n_if))) return rc;
+    const size_t hb = r.hist_pairs() * c->front.pair_bytes;
+    int rc = check_taps(c, n_blocks);
+    if (rc || (rc = ensure_demod(c, n_if))) return rc;
     const size_t fit = kWidePieceBytes / ((size_t)ns * ip * 8);
     const size_t piece = std::min(n_blocks, std::max(gran, fit / gran * gran));
-    if (piece * ip * 2 > c->wide_y_stride) {  // grown on demand; a call in flight still reads the old rows
+    if (piece * ip * 2 > c->wide.y_stride) {  // grown on demand; a call in flight still reads the old rows
         HIPCHK(hipStreamSynchronize(c->stream));
-        c->wide_y_stride = 0;
-        if ((rc = c->d_wide_y.ensure((size_t)ns * piece * ip * 2))) return rc;
-        c->wide_y_stride = piece * ip * 2;
+        c->wide.y_stride = 0;
+        if ((rc = c->wide.y.ensure((size_t)ns * piece * ip * 2))) return rc;
+        c->wide.y_stride = piece * ip * 2;
     }
-    const size_t nhb = c->halo_pairs * 8;
+    const size_t nhb = c->front.halo_pairs * 8;
     for (size_t b0 = 0; b0 < n_blocks; b0 += piece) {
         const size_t nb = std::min(piece, n_blocks - b0);
         DdcLaunch L{};
-        L.iq = d_iq + wide_pairs_of(c, b0) * c->pair_bytes;
-        L.hist = b0 == 0 ? c->d_wide_hist.p : L.iq - hb;
-        L.stream_bytes = wide_pairs_of(c, nb) * c->pair_bytes;
-        L.y = c->d_wide_y.p;
-        L.y_stride = c->wide_y_stride;
+        L.iq = d_iq + wide_pairs_of(c, b0) * c->front.pair_bytes;
+        L.hist = b0 == 0 ? c->wide.hist.p : L.iq - hb;
+        L.stream_bytes = wide_pairs_of(c, nb) * c->front.pair_bytes;
+        L.y = c->wide.y.p;
+        L.y_stride = c->wide.y_stride;
         L.n_out = (long long)(nb * ip);
         L.segs = wide_segments(L.n_out, r.up, r.down, ns, c->n_simd / 4);
-        L.format = c->iq_format;
+        L.format = c->front.format;
         L.up = r.up;
         L.down = r.down;
-        L.streams = reinterpret_cast<const WideStream*>(c->d_wide_streams.p);
-        L.tables = reinterpret_cast<const float2*>(c->d_wide_tab.p);
-        L.taps = c->d_wide_taps.p;
-        L.first_pair = c->tune_pos / (uint64_t)r.up * (uint64_t)r.down;  // tune_pos is a multiple of up
+        L.streams = reinterpret_cast<const WideStream*>(c->wide.streams.p);
+        L.tables = reinterpret_cast<const float2*>(c->wide.tab.p);
+        L.taps = c->wide.taps.p;
+        L.first_pair = c->tune.pos / (uint64_t)r.up * (uint64_t)r.down;  // tune_pos is a multiple of up
         TimingPair* ev = nullptr;  // fmrx_kernel_timing: the down-converter's launches
         if ((rc = timing_begin(c, c->stream, &ev))) return rc;
         rc = launch_wide_ddc(L, ns, c->stream);
@@ -217,13 +257,13 @@ int run_wide(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) 
             return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "%sdown-converter launch failed (%d)", r.rational() ? "rational " : "", rc);
         if ((rc = timing_end(ev, c->stream))) return rc;
         // the y rows as an f32 stream, the wide stage's own halo in front of them
-        if ((rc = launch_front(c, reinterpret_cast<const uint8_t*>(c->d_wide_y.p), c->wide_y_stride * sizeof(float), kIqF32,
-                               c->d_wide_halo, &c->wide_halo_cur, nhb, nb, c->d_demod.p + b0 * c->geo.if_samples,
-                               c->demod_stride, kDemodHist, false)))
+        if ((rc = launch_front(c, reinterpret_cast<const uint8_t*>(c->wide.y.p), c->wide.y_stride * sizeof(float), kIqF32,
+                               c->wide.halo, nhb, nb, c->stereo.demod.p + b0 * c->geo.if_samples,
+                               c->stereo.demod_stride, kDemodHist, false)))
             return rc;
     }
     // the next call's history: the capture's last raw pairs (a granule holds more than that)
-    HIPCHK(hipMemcpyAsync(c->d_wide_hist.p, d_iq + wide_pairs_of(c, n_blocks) * c->pair_bytes - hb, hb,
+    HIPCHK(hipMemcpyAsync(c->wide.hist.p, d_iq + wide_pairs_of(c, n_blocks) * c->front.pair_bytes - hb, hb,
                           hipMemcpyDeviceToDevice, c->stream));
     return run_audio_stage(c, n_blocks, d_pcm, nullptr);
 }
@@ -268,14 +308,14 @@ int set_capture_stage(fmrx_ctx* c, int up, int down, size_t blocks) {
         if (up != 1) rate_taps_by_phase(h.data(), up, down, hp.data());
         const void* taps = up == 1 ? (const void*)h.data() : (const void*)hp.data();
         const size_t tap_floats = up == 1 ? h.size() : 2 * hp.size();
-        if ((rc = c->d_wide_hist.ensure((size_t)rate_hist_pairs(up, down) * c->pair_bytes)) || (rc = c->d_wide_taps.ensure(tap_floats)) ||
-            (rc = c->d_wide_tab.ensure(2 * (size_t)kRateMaxN * ns)) || (rc = c->d_wide_streams.ensure(2 * ns)) ||
-            (rc = c->d_wide_halo[0].ensure(c->halo_pairs * 8 * ns)) || (rc = c->d_wide_halo[1].ensure(c->halo_pairs * 8 * ns)))
+        if ((rc = c->wide.hist.ensure((size_t)rate_hist_pairs(up, down) * c->front.pair_bytes)) || (rc = c->wide.taps.ensure(tap_floats)) ||
+            (rc = c->wide.tab.ensure(2 * (size_t)kRateMaxN * ns)) || (rc = c->wide.streams.ensure(2 * ns)) ||
+            (rc = c->wide.halo.ensure(c->front.halo_pairs * 8 * ns)))
             return rc;
-        HIPCHK(hipMemcpy(c->d_wide_taps.p, taps, sizeof(float) * tap_floats, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->wide.taps.p, taps, sizeof(float) * tap_floats, hipMemcpyHostToDevice));
     }
-    c->ratio = CaptureRatio{up, down, blocks};
-    c->wide_tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
+    c->wide.ratio = CaptureRatio{up, down, blocks};
+    c->wide.tuned = false;  // offsets are against cap_fs: fmrx_tune_wide again
     return reset_state(c);
 }
 
@@ -297,21 +337,21 @@ int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
     if (!offsets_hz) {  // tuning off: the untuned kernels, exactly as before
-        if (c->iq_format != kIqU8) {
+        if (c->front.format != kIqU8) {
             const int rc = upload_zero_offsets(c);
             if (rc) return rc;
         }
-        c->tuned = false;
-        c->wide_tuned = false;
-        c->tune_pos = first_pair;
+        c->tune.on = false;
+        c->wide.tuned = false;
+        c->tune.pos = first_pair;
         return FMRX_OK;
     }
     const int rc = tuner_upload(c, offsets_hz);
     if (rc) return rc;
-    c->tune_offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
-    c->tune_pos = first_pair;
-    c->tuned = true;
-    c->wide_tuned = false;  // the tables are no longer the fine offsets of fmrx_tune_wide
+    c->tune.offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
+    c->tune.pos = first_pair;
+    c->tune.on = true;
+    c->wide.tuned = false;  // the tables are no longer the fine offsets of fmrx_tune_wide
     return FMRX_OK;
 }
 
@@ -332,14 +372,14 @@ int fmrx_set_input_format(fmrx_ctx* c, int format) {
     int rc = set_device(c);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));  // a call in flight still reads the halo
-    if (format != c->iq_format) {
-        const size_t ns = c->cfg.n_streams, hb = c->halo_pairs * (size_t)pb;
-        if (format != kIqU8 && !c->tuned && (rc = upload_zero_offsets(c))) return rc;
-        if ((rc = c->d_halo[0].ensure(hb * ns)) || (rc = c->d_halo[1].ensure(hb * ns))) return rc;
-        if (c->ratio.on() && (rc = c->d_wide_hist.ensure(c->ratio.hist_pairs() * (size_t)pb))) return rc;
-        c->iq_format = format;
-        c->pair_bytes = (size_t)pb;
-        c->halo_bytes = hb;
+    if (format != c->front.format) {
+        const size_t ns = c->cfg.n_streams, hb = c->front.halo_pairs * (size_t)pb;
+        if (format != kIqU8 && !c->tune.on && (rc = upload_zero_offsets(c))) return rc;
+        if ((rc = c->front.halo.ensure(hb * ns))) return rc;
+        if (c->wide.ratio.on() && (rc = c->wide.hist.ensure(c->wide.ratio.hist_pairs() * (size_t)pb))) return rc;
+        c->front.format = format;
+        c->front.pair_bytes = (size_t)pb;
+        c->front.halo_bytes = hb;
     }
     return reset_state(c);
 }
@@ -347,16 +387,16 @@ int fmrx_set_input_format(fmrx_ctx* c, int format) {
 int fmrx_input_format(const fmrx_ctx* c, int* format) {
     CtxLock lock_(c);
     if (!c || !format) return fail(FMRX_EINVAL, "null argument");
-    *format = c->iq_format;
+    *format = c->front.format;
     return FMRX_OK;
 }
 
 int fmrx_tuner_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    if (offsets_hz) std::copy(c->tune_offsets.begin(), c->tune_offsets.end(), offsets_hz);
-    if (next_pair) *next_pair = c->tune_pos;
-    if (enabled) *enabled = c->tuned ? 1 : 0;
+    if (offsets_hz) std::copy(c->tune.offsets.begin(), c->tune.offsets.end(), offsets_hz);
+    if (next_pair) *next_pair = c->tune.pos;
+    if (enabled) *enabled = c->tune.on ? 1 : 0;
     return FMRX_OK;
 }
 
@@ -393,7 +433,7 @@ int fmrx_set_capture_decim(fmrx_ctx* c, int decim) {
     if (!c) return fail(FMRX_EINVAL, "null context");
     const int rc = check_capture_decim(decim, true);
     if (rc) return rc;
-    if (decim == 1 && !c->ratio.on()) return FMRX_OK;  // the default: nothing anywhere changes
+    if (decim == 1 && !c->wide.ratio.on()) return FMRX_OK;  // the default: nothing anywhere changes
     if (decim > 1 && !tuner_supported(c->geo.rf_taps, c->geo.rf_decim))
         return fail(FMRX_EINVAL, "no tuned RF kernel for rf_taps=%d rf_decim=%d: no wide captures", c->geo.rf_taps,
                     c->geo.rf_decim);
@@ -423,31 +463,31 @@ int fmrx_set_capture_rate(fmrx_ctx* c, int cap_fs) {
 int fmrx_capture_decim(const fmrx_ctx* c, int* decim) {
     CtxLock lock_(c);
     if (!c || !decim) return fail(FMRX_EINVAL, "null argument");
-    *decim = c->ratio.rational() ? 0 : c->ratio.down;  // D, 1 with no wide stage, 0 at a rational rate
+    *decim = c->wide.ratio.rational() ? 0 : c->wide.ratio.down;  // D, 1 with no wide stage, 0 at a rational rate
     return FMRX_OK;
 }
 
 int fmrx_capture_rate(const fmrx_ctx* c, int* cap_fs, int* up, int* down) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    if (cap_fs) *cap_fs = c->ratio.cap_fs(c->geo.rf_fs);
-    if (up) *up = c->ratio.up;
-    if (down) *down = c->ratio.down;
+    if (cap_fs) *cap_fs = c->wide.ratio.cap_fs(c->geo.rf_fs);
+    if (up) *up = c->wide.ratio.up;
+    if (down) *down = c->wide.ratio.down;
     return FMRX_OK;
 }
 
 int fmrx_wide_granule(const fmrx_ctx* c, size_t* blocks, size_t* wide_pairs) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    if (blocks) *blocks = c->ratio.blocks;
-    if (wide_pairs) *wide_pairs = wide_pairs_of(c, c->ratio.blocks);
+    if (blocks) *blocks = c->wide.ratio.blocks;
+    if (wide_pairs) *wide_pairs = wide_pairs_of(c, c->wide.ratio.blocks);
     return FMRX_OK;
 }
 
 int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
     CtxLock lock_(c);
     if (!c || !offsets_hz) return fail(FMRX_EINVAL, "null argument");
-    const CaptureRatio& r = c->ratio;
+    const CaptureRatio& r = c->wide.ratio;
     if (!r.on()) return fail(FMRX_ESTATE, "fmrx_tune_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
     if (first_pair % (uint64_t)r.down != 0) {
         if (r.rational())
@@ -470,22 +510,22 @@ int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) 
         ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
     }
     if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
-    HIPCHK(hipMemcpy(c->d_wide_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_wide_streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
-    c->tune_offsets = fine;  // the existing tuner state: the fine parts at rf_fs
-    c->tune_pos = first_pair / (uint64_t)r.down * (uint64_t)r.up;
-    c->tuned = true;
-    c->wide_offsets.assign(offsets_hz, offsets_hz + ns);
-    c->wide_tuned = true;
+    HIPCHK(hipMemcpy(c->wide.tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->wide.streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
+    c->tune.offsets = fine;  // the existing tuner state: the fine parts at rf_fs
+    c->tune.pos = first_pair / (uint64_t)r.down * (uint64_t)r.up;
+    c->tune.on = true;
+    c->wide.offsets.assign(offsets_hz, offsets_hz + ns);
+    c->wide.tuned = true;
     return FMRX_OK;
 }
 
 int fmrx_wide_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    if (offsets_hz) std::copy(c->wide_offsets.begin(), c->wide_offsets.end(), offsets_hz);
-    if (next_pair) *next_pair = c->tune_pos / (uint64_t)c->ratio.up * (uint64_t)c->ratio.down;
-    if (enabled) *enabled = c->wide_tuned ? 1 : 0;
+    if (offsets_hz) std::copy(c->wide.offsets.begin(), c->wide.offsets.end(), offsets_hz);
+    if (next_pair) *next_pair = c->tune.pos / (uint64_t)c->wide.ratio.up * (uint64_t)c->wide.ratio.down;
+    if (enabled) *enabled = c->wide.tuned ? 1 : 0;
     return FMRX_OK;
 }
 

@@ -14,15 +14,15 @@ constexpr double kPowerFloor = 1e-30;  // below it a sum counts as this (no log 
 
 // the tables on the device, once a context
 int ensure_meter_tables(fmrx_ctx* c) {
-    if (c->meter_p) return 0;
+    if (c->meter.p) return 0;
     int P = 0;
     if (!meter_design(c->geo.bp_fs, &P, nullptr)) return fail(FMRX_EINVAL, "no meter design at bp_fs %d", c->geo.bp_fs);
     std::vector<float> tab((size_t)2 * kMeterTones * (size_t)P);
     meter_design(c->geo.bp_fs, nullptr, tab.data());
-    int rc = c->d_meter_tab.ensure(tab.size());
+    int rc = c->meter.tab.ensure(tab.size());
     if (rc) return rc;
-    HIPCHK(hipMemcpy(c->d_meter_tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    c->meter_p = P;
+    HIPCHK(hipMemcpy(c->meter.tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    c->meter.p = P;
     return 0;
 }
 
@@ -39,8 +39,8 @@ int run_meter(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_b
     MeterLaunch L{};
     L.demod = d_demod;
     L.demod_stride = demod_stride;
-    L.tables = c->d_meter_tab.p;
-    L.P = c->meter_p;
+    L.tables = c->meter.tab.p;
+    L.P = c->meter.p;
     L.frames = (int)frames;
     L.power = d_power;
     if ((rc = launch_meter(L, c->cfg.n_streams, c->stream)))
@@ -78,30 +78,30 @@ int check_meter_blocks(const fmrx_ctx* c, size_t n_blocks) {
 }
 
 void reset_meter(fmrx_ctx* c) {
-    for (auto& r : c->meter_rep) r = fmrx_meter_report{};
-    c->meter_pending = 0;
+    c->meter.rep.assign((size_t)c->cfg.n_streams, fmrx_meter_report{});  // sized here: creation resets
+    c->meter.pending = 0;
 }
 
 int meter_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks) {
     const size_t ns = c->cfg.n_streams, frames = meter_frames(c, n_blocks);
-    c->meter_pending = 0;
+    c->meter.pending = 0;
     int rc;
-    if ((rc = c->d_meter_pow.ensure(ns * frames * kMeterTones))) return rc;
-    if ((rc = run_meter(c, d_demod, demod_stride, n_blocks, c->d_meter_pow.p))) return rc;
-    c->meter_pending = frames;
+    if ((rc = c->meter.pow.ensure(ns * frames * kMeterTones))) return rc;
+    if ((rc = run_meter(c, d_demod, demod_stride, n_blocks, c->meter.pow.p))) return rc;
+    c->meter.pending = frames;
     return 0;
 }
 
 int meter_finish(fmrx_ctx* c) {
-    const size_t ns = c->cfg.n_streams, frames = c->meter_pending;
+    const size_t ns = c->cfg.n_streams, frames = c->meter.pending;
     if (frames == 0) return 0;
-    c->meter_pending = 0;
-    c->meter_host.resize(ns * frames * kMeterTones);
-    HIPCHK(hipMemcpyAsync(c->meter_host.data(), c->d_meter_pow.p, sizeof(float) * c->meter_host.size(), hipMemcpyDeviceToHost,
+    c->meter.pending = 0;
+    c->meter.host.resize(ns * frames * kMeterTones);
+    HIPCHK(hipMemcpyAsync(c->meter.host.data(), c->meter.pow.p, sizeof(float) * c->meter.host.size(), hipMemcpyDeviceToHost,
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (size_t s = 0; s < ns; s++) {
-        int rc = fmrx_meter_accumulate(&c->meter_rep[s], c->meter_host.data() + s * frames * kMeterTones, frames);
+        int rc = fmrx_meter_accumulate(&c->meter.rep[s], c->meter.host.data() + s * frames * kMeterTones, frames);
         if (rc) return rc;
     }
     return 0;
@@ -133,10 +133,10 @@ int fmrx_meter(fmrx_ctx* c, const float* demod, size_t n_blocks, float* power) {
     if ((rc = set_device(c))) return rc;
     const size_t ns = c->cfg.n_streams, n_if = n_blocks * c->geo.if_samples;
     const size_t n_pow = ns * meter_frames(c, n_blocks) * kMeterTones;
-    if ((rc = c->d_f32.ensure(ns * n_if)) || (rc = c->d_meter_pow.ensure(n_pow))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_f32.p, demod, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_meter(c, c->d_f32.p, n_if, n_blocks, c->d_meter_pow.p))) return rc;
-    HIPCHK(hipMemcpyAsync(power, c->d_meter_pow.p, sizeof(float) * n_pow, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = c->io.f32.ensure(ns * n_if)) || (rc = c->meter.pow.ensure(n_pow))) return rc;
+    HIPCHK(hipMemcpyAsync(c->io.f32.p, demod, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_meter(c, c->io.f32.p, n_if, n_blocks, c->meter.pow.p))) return rc;
+    HIPCHK(hipMemcpyAsync(power, c->meter.pow.p, sizeof(float) * n_pow, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return FMRX_OK;
 }
@@ -183,7 +183,7 @@ int fmrx_set_meter(fmrx_ctx* c, int on) {
         int rc = set_device(c);
         if (rc || (rc = ensure_meter_tables(c))) return rc;
     }
-    c->meter_on = on != 0;
+    c->meter.on = on != 0;
     return FMRX_OK;
 }
 
@@ -191,7 +191,7 @@ int fmrx_meter_get(const fmrx_ctx* c, int stream, fmrx_meter_report* out) {
     CtxLock lock_(c);
     if (!c || !out) return fail(FMRX_EINVAL, "null argument");
     if (stream < 0 || stream >= c->cfg.n_streams) return fail(FMRX_EINVAL, "stream %d of %d", stream, c->cfg.n_streams);
-    *out = c->meter_rep[(size_t)stream];
+    *out = c->meter.rep[(size_t)stream];
     return FMRX_OK;
 }
 

@@ -52,29 +52,26 @@ int fmrx_pll(fmrx_ctx* c, float* d_io, int n, float freq, float fs, float nco_sc
     int rc = set_device(c);
     if (rc) return rc;
     // single stream with a 6-float state: stage through the 8-float layout of the kernel
-    rc = c->d_scratch.ensure(8);
+    rc = c->io.scratch.ensure(8);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_scratch.p, d_st, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->io.scratch.p, d_st, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     // slots 6-7 are the runners' (6: the demoted hand-off, read by every runner launch): zero
-    HIPCHK(hipMemsetAsync(c->d_scratch.p + 6, 0, 2 * sizeof(float), c->stream));
-    if ((rc = c->d_pll_side.ensure(pll_side_doubles(n, 1)))) return rc;
+    HIPCHK(hipMemsetAsync(c->io.scratch.p + 6, 0, 2 * sizeof(float), c->stream));
+    if ((rc = c->stereo.pll_side.ensure(pll_side_doubles(n, 1)))) return rc;
     // the state is the caller's: its trigOffset (read back, 4 bytes) is the hint when it is in the
     // float increments' domain (an integer in [0, 2^24]); unknown otherwise (every runner launched
     // for every segment, each taking its own streams)
     float trig = -1.0f;
     HIPCHK(hipMemcpyAsync(&trig, d_st + 5, sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    PllHint hint;
-    hint.n_simd = c->n_simd;
-    hint.knobs = c->knobs.pll;
-    hint.known = trig >= 0.0f && trig <= 16777216.0f && trig == std::floor(trig);
-    hint.trig_lo = hint.trig_hi = hint.known ? (double)trig : 0.0;
-    hint.timer = c->stage_timer.on ? &c->stage_timer : nullptr;
-    hint.redos = c->pll_redos;  // fmrx_debug_pll_redos: as stream 0
+    TrigTrack t;
+    t.known = trig >= 0.0f && trig <= 16777216.0f && trig == std::floor(trig);
+    t.lo = t.hi = t.known ? (double)trig : 0.0;
+    const PllHint hint = c->hint(t);  // fmrx_debug_pll_redos: as stream 0
     const PllLoop loop{freq, fs, nco_scale, phase_adjust, norm_bw};
-    if (launch_pll(d_io, n, 1, (size_t)n, loop, c->d_scratch.p, c->d_pll_side.p, c->stream, hint, c->pll_stats))
+    if (launch_pll(d_io, n, 1, (size_t)n, loop, c->io.scratch.p, c->stereo.pll_side.p, c->stream, hint, c->diag.pll_stats))
         return fail(FMRX_EHIP, "launch failed");
-    HIPCHK(hipMemcpyAsync(d_st, c->d_scratch.p, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_st, c->io.scratch.p, 6 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     return FMRX_OK;
 }
 
@@ -125,20 +122,20 @@ int fmrx_deemph(fmrx_ctx* c, const float* d_in, size_t n, int tau_us, float* d_s
     if (d_out == d_in) return fail(FMRX_EINVAL, "fmrx_deemph does not run in place");
     if (n == 0) return FMRX_OK;
     int rc = set_device(c);
-    if (rc || (rc = ensure_deemph_taps(c)) || (rc = c->d_deemph_tmp.ensure(kDeemphHist))) return rc;
+    if (rc || (rc = ensure_deemph_taps(c)) || (rc = c->deemph.tmp.ensure(kDeemphHist))) return rc;
     DeemphLaunch D{};
     D.in = d_in;
     D.in_stride = n;
     D.nch = 1;
     D.n = n;
-    D.h = c->d_deemph_taps.p + (tau_us == 75 ? kDeemphTaps : 0);
+    D.h = c->deemph.taps.p + (tau_us == 75 ? kDeemphTaps : 0);
     D.state_in = d_state;
-    D.state_out = c->d_deemph_tmp.p;  // a first chunk may still read d_state when the last one is done
+    D.state_out = c->deemph.tmp.p;  // a first chunk may still read d_state when the last one is done
     D.out = d_out;
     D.pcm = d_pcm;
     D.out_stride = n;
     if (launch_deemph(D, 1, c->stream)) return fail(FMRX_EHIP, "de-emphasis launch failed");
-    HIPCHK(hipMemcpyAsync(d_state, c->d_deemph_tmp.p, sizeof(float) * kDeemphHist, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_state, c->deemph.tmp.p, sizeof(float) * kDeemphHist, hipMemcpyDeviceToDevice, c->stream));
     return FMRX_OK;
 }
 
@@ -180,7 +177,7 @@ int fmrx_synth_device(fmrx_ctx* c, uint64_t seed, int rf_fs, uint64_t first_pair
     if (rc) return rc;
     SynthParams p;
     synth_setup(seed, rf_fs, &p);
-    return launch_synth(p, c->d_sintab.p, first_pair, n_pairs, d_out, c->stream)
+    return launch_synth(p, c->synth.sintab.p, first_pair, n_pairs, d_out, c->stream)
                ? fail(FMRX_EHIP, "synth launch failed")
                : 0;
 }
@@ -197,12 +194,12 @@ int fmrx_synth_device_streams(fmrx_ctx* c, const uint64_t* seeds, size_t n_seeds
     if (rc) return rc;
     std::vector<SynthParams> ps(n_seeds);
     for (size_t k = 0; k < n_seeds; k++) synth_setup(seeds[k], rf_fs, &ps[k]);
-    if ((rc = c->d_synth_params.ensure(sizeof(SynthParams) * n_seeds))) return rc;
+    if ((rc = c->synth.params.ensure(sizeof(SynthParams) * n_seeds))) return rc;
     // ps is pageable host memory: the stream is drained before it goes out of scope
-    HIPCHK(hipMemcpyAsync(c->d_synth_params.p, ps.data(), sizeof(SynthParams) * n_seeds, hipMemcpyHostToDevice,
+    HIPCHK(hipMemcpyAsync(c->synth.params.p, ps.data(), sizeof(SynthParams) * n_seeds, hipMemcpyHostToDevice,
                           c->stream));
-    if (launch_synth_streams(reinterpret_cast<const SynthParams*>(c->d_synth_params.p), (int)n_seeds,
-                             c->d_sintab.p, first_pair, n_pairs, d_out, stride_bytes, c->stream)) {
+    if (launch_synth_streams(reinterpret_cast<const SynthParams*>(c->synth.params.p), (int)n_seeds,
+                             c->synth.sintab.p, first_pair, n_pairs, d_out, stride_bytes, c->stream)) {
         (void)hipStreamSynchronize(c->stream);  // the copy from ps may still be in flight
         return fail(FMRX_EHIP, "synth launch failed");
     }
@@ -218,7 +215,7 @@ int fmrx_debug_mono_stamps(fmrx_ctx* c, unsigned long long* d_stamps, size_t n_w
     if (needed) *needed = (size_t)c->cfg.n_streams * 256 * (size_t)mono_wg_per_cu(c->geo.rf_decim);
     if (d_stamps && needed && n_workgroups < *needed)
         return fail(FMRX_EINVAL, "stamp buffer holds %zu workgroups, up to %zu launch", n_workgroups, *needed);
-    c->stamps = d_stamps;
+    c->diag.stamps = d_stamps;
     return FMRX_OK;
 }
 
@@ -226,7 +223,7 @@ int fmrx_debug_mono_stamps(fmrx_ctx* c, unsigned long long* d_stamps, size_t n_w
 int fmrx_debug_pll_redos(fmrx_ctx* c, unsigned* d_counts) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    c->pll_redos = d_counts;
+    c->diag.pll_redos = d_counts;
     return FMRX_OK;
 }
 
@@ -234,7 +231,7 @@ int fmrx_debug_pll_redos(fmrx_ctx* c, unsigned* d_counts) {
 int fmrx_debug_pll_stats(fmrx_ctx* c, unsigned long long* d_counts) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
-    c->pll_stats = d_counts;
+    c->diag.pll_stats = d_counts;
     return FMRX_OK;
 }
 

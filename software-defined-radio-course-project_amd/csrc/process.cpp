@@ -10,7 +10,7 @@ using namespace fmrx;
 namespace {
 
 int check_wide_tuned(const fmrx_ctx* c, const char* who) {
-    if (!c->ratio.on() || !c->wide_tuned)
+    if (!c->wide.ratio.on() || !c->wide.tuned)
         return fail(FMRX_ESTATE, "%s: wide tuning is off (fmrx_set_capture_decim, fmrx_tune_wide first)", who);
     return 0;
 }
@@ -46,19 +46,19 @@ int staged_call(fmrx_ctx* c, const void* in, size_t in_bytes, bool upload, DevBu
                 bool pinned_ok, Enqueue enqueue) {
     const bool pinned = pinned_ok && in_bytes <= kPinnedCallBytes;
     int rc;
-    if (pinned && ((rc = c->h_in.ensure(in_bytes)) || (rc = c->h_out.ensure(out_n * sizeof(T))))) return rc;
-    if (upload && (rc = c->d_in.ensure(in_bytes))) return rc;
+    if (pinned && ((rc = c->io.h_in.ensure(in_bytes)) || (rc = c->io.h_out.ensure(out_n * sizeof(T))))) return rc;
+    if (upload && (rc = c->io.d_in.ensure(in_bytes))) return rc;
     if (!pinned && (rc = d_res.ensure(out_n))) return rc;
     const void* src = in;
     if (pinned) {
-        std::memcpy(c->h_in.p, in, in_bytes);
-        src = c->h_in.p;
+        std::memcpy(c->io.h_in.p, in, in_bytes);
+        src = c->io.h_in.p;
     }
     if (upload) {
-        HIPCHK(hipMemcpyAsync(c->d_in.p, src, in_bytes, hipMemcpyHostToDevice, c->stream));
-        src = c->d_in.p;
+        HIPCHK(hipMemcpyAsync(c->io.d_in.p, src, in_bytes, hipMemcpyHostToDevice, c->stream));
+        src = c->io.d_in.p;
     }
-    T* res = pinned ? reinterpret_cast<T*>(c->h_out.p) : d_res.p;
+    T* res = pinned ? reinterpret_cast<T*>(c->io.h_out.p) : d_res.p;
     if ((rc = enqueue(src, res, pinned))) return rc;
     if (pinned) {
         if ((rc = wait_small(c))) return rc;
@@ -74,7 +74,7 @@ int staged_call(fmrx_ctx* c, const void* in, size_t in_bytes, bool upload, DevBu
 int process_host(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm, bool shared) {
     CtxLock lock_(c);
     if (!c || !iq || !pcm) return fail(FMRX_EINVAL, "null argument");
-    if (shared && !c->tuned) return fail(FMRX_ESTATE, "fmrx_process_shared: tuning is off (fmrx_tune first)");
+    if (shared && !c->tune.on) return fail(FMRX_ESTATE, "fmrx_process_shared: tuning is off (fmrx_tune first)");
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
@@ -82,7 +82,7 @@ int process_host(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm, 
     const size_t ns = c->cfg.n_streams;
     const size_t in_bytes = (shared ? 1 : ns) * n_blocks * iq_block_bytes(c);
     auto on_device = shared ? fmrx_process_shared_device : fmrx_process_device;
-    return staged_call(c, iq, in_bytes, true, c->d_out, pcm, ns * n_blocks * c->geo.pcm_samples, true,
+    return staged_call(c, iq, in_bytes, true, c->io.d_out, pcm, ns * n_blocks * c->geo.pcm_samples, true,
                        [&](const void* d_iq, int16_t* d_pcm, bool) {
                            return on_device(c, static_cast<const uint8_t*>(d_iq), n_blocks, d_pcm);
                        });
@@ -110,7 +110,7 @@ int fmrx_process_device_ex(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, in
     if ((rc = ensure_demod(c, n_if))) return rc;
     const int K = stereo_chunks(c, n_blocks);
     if (K > 1) return run_stereo_pipelined(c, d_iq, n_blocks, d_pcm, d_mono, K);
-    if ((rc = run_fused(c, d_iq, n_blocks, nullptr, nullptr, c->d_demod.p, c->demod_stride,
+    if ((rc = run_fused(c, d_iq, n_blocks, nullptr, nullptr, c->stereo.demod.p, c->stereo.demod_stride,
                         kDemodHist, false)))
         return rc;
     return run_stereo_audio(c, n_blocks, d_pcm, d_mono);
@@ -123,7 +123,7 @@ int fmrx_process_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16
 int fmrx_process_shared_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm) {
     CtxLock lock_(c);
     if (!c || !d_iq || !d_pcm) return fail(FMRX_EINVAL, "null argument");
-    if (!c->tuned) return fail(FMRX_ESTATE, "fmrx_process_shared_device: tuning is off (fmrx_tune first)");
+    if (!c->tune.on) return fail(FMRX_ESTATE, "fmrx_process_shared_device: tuning is off (fmrx_tune first)");
     if (n_blocks == 0) return FMRX_OK;
     int rc = set_device(c);
     if (rc) return rc;
@@ -136,9 +136,9 @@ int fmrx_process_wide_device(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, 
     int rc = check_wide_tuned(c, "fmrx_process_wide_device");
     if (rc) return rc;
     if (n_blocks == 0) return FMRX_OK;
-    if (reinterpret_cast<uintptr_t>(d_iq) % (2 * c->pair_bytes) != 0)
-        return fail(FMRX_EINVAL, "wide calls need a %zu-byte aligned capture", 2 * c->pair_bytes);
-    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, c->ratio.size_factor())) || (rc = set_device(c)))
+    if (reinterpret_cast<uintptr_t>(d_iq) % (2 * c->front.pair_bytes) != 0)
+        return fail(FMRX_EINVAL, "wide calls need a %zu-byte aligned capture", 2 * c->front.pair_bytes);
+    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, c->wide.ratio.size_factor())) || (rc = set_device(c)))
         return rc;
     return run_wide(c, d_iq, n_blocks, d_pcm);
 }
@@ -160,10 +160,10 @@ int fmrx_process_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* 
     if (rc) return rc;
     if (n_blocks == 0) return FMRX_OK;
     if ((rc = set_device(c))) return rc;
-    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, c->ratio.size_factor()))) return rc;
-    const size_t in_bytes = wide_pairs_of(c, n_blocks) * c->pair_bytes;
+    if ((rc = check_wide_blocks(c, n_blocks)) || (rc = check_call_size(c, n_blocks, c->wide.ratio.size_factor()))) return rc;
+    const size_t in_bytes = wide_pairs_of(c, n_blocks) * c->front.pair_bytes;
     const size_t out_n = (size_t)c->cfg.n_streams * n_blocks * c->geo.pcm_samples;
-    return staged_call(c, iq, in_bytes, true, c->d_out, pcm, out_n, false, [&](const void* d_iq, int16_t* d_pcm, bool) {
+    return staged_call(c, iq, in_bytes, true, c->io.d_out, pcm, out_n, false, [&](const void* d_iq, int16_t* d_pcm, bool) {
         return fmrx_process_wide_device(c, static_cast<const uint8_t*>(d_iq), n_blocks, d_pcm);
     });
 }
@@ -180,7 +180,7 @@ int fmrx_rf_block(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, float* demod)
     const size_t n_if = n_blocks * c->geo.if_samples;
     // pinned staging: the input by DMA (the fused kernel's staging reads host memory 4x slower),
     // the demod in place
-    return staged_call(c, iq, ns * n_blocks * iq_block_bytes(c), true, c->d_f32, demod, ns * n_if, true,
+    return staged_call(c, iq, ns * n_blocks * iq_block_bytes(c), true, c->io.f32, demod, ns * n_if, true,
                        [&](const void* src, float* d_demod, bool) {
                            const uint8_t* d_iq = static_cast<const uint8_t*>(src);
                            return front_tuned(c) ? run_tuned_front(c, d_iq, n_blocks * iq_block_bytes(c), n_blocks,
@@ -198,7 +198,7 @@ int fmrx_audio_block(fmrx_ctx* c, const float* demod, size_t n_blocks, int16_t* 
     if (rc) return rc;
     const size_t ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;
-    if (c->cfg.channels == FMRX_MONO && c->audio_hist_stale)
+    if (c->cfg.channels == FMRX_MONO && c->mono.stale)
         return fail(FMRX_ESTATE, "no audio history after fmrx_seek (run a fused call first)");
     // small calls: the demod through the pinned staging (stereo: read there by the band-pass
     // kernel; mono: one copy), the PCM written by the audio kernel into pinned memory in place
@@ -206,19 +206,19 @@ int fmrx_audio_block(fmrx_ctx* c, const float* demod, size_t n_blocks, int16_t* 
         const float* src = static_cast<const float*>(staged);
         int rc;
         if (c->cfg.channels == FMRX_MONO) {
-            if ((rc = c->d_f32.ensure(ns * n_if))) return rc;
-            HIPCHK(hipMemcpyAsync(c->d_f32.p, src, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
-            return run_mono_audio(c, c->d_f32.p, n_if, n_if, d_pcm, nullptr);
+            if ((rc = c->io.f32.ensure(ns * n_if))) return rc;
+            HIPCHK(hipMemcpyAsync(c->io.f32.p, src, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
+            return run_mono_audio(c, c->io.f32.p, n_if, n_if, d_pcm, nullptr);
         }
         if ((rc = ensure_demod(c, n_if))) return rc;
         if (!pinned)
-            HIPCHK(hipMemcpy2DAsync(c->d_demod.p + kDemodHist, c->demod_stride * sizeof(float), src,
+            HIPCHK(hipMemcpy2DAsync(c->stereo.demod.p + kDemodHist, c->stereo.demod_stride * sizeof(float), src,
                                     n_if * sizeof(float), n_if * sizeof(float), ns,
                                     hipMemcpyHostToDevice, c->stream));
         // pinned: the band-pass kernel reads the staging buffer itself (one launch fewer)
         return run_stereo_audio(c, n_blocks, d_pcm, nullptr, pinned ? src : nullptr);
     };
-    return staged_call(c, demod, sizeof(float) * ns * n_if, false, c->d_out, pcm, ns * n_blocks * c->geo.pcm_samples, true,
+    return staged_call(c, demod, sizeof(float) * ns * n_if, false, c->io.d_out, pcm, ns * n_blocks * c->geo.pcm_samples, true,
                        audio);
 }
 
@@ -232,12 +232,12 @@ int fmrx_rds_block(fmrx_ctx* c, const float* demod, size_t n_blocks, float* rds,
     if (rc) return rc;
     const size_t ns = c->cfg.n_streams;
     const size_t n = ns * n_blocks * c->geo.if_samples;
-    if ((rc = c->d_f32.ensure(n)) || (rc = c->d_scratch.ensure(3 * n))) return rc;
-    float* d_rds = c->d_scratch.p;
-    float* d_nco = nco ? c->d_scratch.p + n : nullptr;
-    float* d_ch = channel ? c->d_scratch.p + 2 * n : nullptr;
-    HIPCHK(hipMemcpyAsync(c->d_f32.p, demod, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_rds(c, c->d_f32.p, n / ns, n / ns, d_rds, d_nco, d_ch))) return rc;
+    if ((rc = c->io.f32.ensure(n)) || (rc = c->io.scratch.ensure(3 * n))) return rc;
+    float* d_rds = c->io.scratch.p;
+    float* d_nco = nco ? c->io.scratch.p + n : nullptr;
+    float* d_ch = channel ? c->io.scratch.p + 2 * n : nullptr;
+    HIPCHK(hipMemcpyAsync(c->io.f32.p, demod, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_rds(c, c->io.f32.p, n / ns, n / ns, d_rds, d_nco, d_ch))) return rc;
     HIPCHK(hipMemcpyAsync(rds, d_rds, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     if (nco) HIPCHK(hipMemcpyAsync(nco, d_nco, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     if (channel) HIPCHK(hipMemcpyAsync(channel, d_ch, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));

@@ -19,15 +19,15 @@ int run_rds_bits(fmrx_ctx* c, const float* d_mix, size_t mix_stride, size_t n_bl
     if (n_if > (size_t)std::numeric_limits<int>::max() / kRdsbUp)
         return fail(FMRX_EINVAL, "%zu blocks: too many samples for one RDS call", n_blocks);
     const size_t n_out = n_if * kRdsbUp / (size_t)down, n_win = n_out / kRdsbWin, n_sym = n_win * kRdsbSyms;
-    int rc = c->d_rdsb_work.ensure(ns * (n_out + n_sym + 2 * n_win));
+    int rc = c->rdsb.work.ensure(ns * (n_out + n_sym + 2 * n_win));
     if (rc) return rc;
     RdsBitsLaunch L{};
     L.mix = d_mix;
     L.mix_stride = mix_stride;
-    L.hist = c->d_rdsb_hist.p;
-    L.state = c->d_rdsb_state.p;
-    L.taps = c->d_rdsb_taps.p;
-    L.sign = c->d_rdsb_work.p;
+    L.hist = c->rdsb.hist.p;
+    L.state = c->rdsb.state.p;
+    L.taps = c->rdsb.taps.p;
+    L.sign = c->rdsb.work.p;
     L.sym = L.sign + ns * n_out;
     L.winp = L.sym + ns * n_sym;
     L.lastchip = L.winp + ns * n_win;
@@ -88,7 +88,7 @@ namespace fmrx {
 size_t rds_granule_blocks(const fmrx_ctx* c) {
     const size_t per_window = (size_t)(kRdsbWin / kRdsbUp) * (size_t)(c->geo.bp_fs / 2000);  // mixer samples a window
     const size_t g = std::lcm((size_t)c->geo.if_samples, per_window) / (size_t)c->geo.if_samples;
-    return std::lcm(g, c->ratio.blocks);
+    return std::lcm(g, c->wide.ratio.blocks);
 }
 
 int check_rds_blocks(const fmrx_ctx* c, size_t n_blocks) {
@@ -98,14 +98,26 @@ int check_rds_blocks(const fmrx_ctx* c, size_t n_blocks) {
     return 0;
 }
 
+// the symbol-rate resampler's prototype: 101 taps a phase at 19 bp_fs, gain 19
+int init_rds_bits(fmrx_ctx* c) {
+    const size_t ns = c->cfg.n_streams;
+    std::vector<float> taps(kRdsbTaps);
+    design_lpf(taps.data(), (float)c->geo.bp_fs * (float)kRdsbUp, 3000.0f, kRdsbTaps, kRdsbUp);
+    c->rdsb.info.resize(ns);
+    c->rdss.ext.resize(ns);
+    int rc = c->rdsb.hist.ensure((size_t)kRdsbHist * ns);
+    if (!rc) rc = c->rdsb.state.ensure((size_t)kRdsbStateBytes * ns);
+    return rc ? rc : upload(c->rdsb.taps, taps.data(), taps.size(), "RDS tap upload");
+}
+
 int reset_rds_bits(fmrx_ctx* c) {
     const size_t ns = c->cfg.n_streams;
-    HIPCHK(hipMemsetAsync(c->d_rdsb_hist.p, 0, sizeof(float) * kRdsbHist * ns, c->stream));
+    HIPCHK(hipMemsetAsync(c->rdsb.hist.p, 0, sizeof(float) * kRdsbHist * ns, c->stream));
     // zero symbols and bit count; the sign and the chip in front of the stream count as 1
-    HIPCHK(hipMemsetAsync(c->d_rdsb_state.p, 0, (size_t)kRdsbStateBytes * ns, c->stream));
-    HIPCHK(hipMemset2DAsync(c->d_rdsb_state.p, kRdsbStateBytes, 1, 2, ns, c->stream));
-    for (auto& io : c->rds_info) fmrx_rds_info_init(&io);
-    c->rdsb_pending = 0;
+    HIPCHK(hipMemsetAsync(c->rdsb.state.p, 0, (size_t)kRdsbStateBytes * ns, c->stream));
+    HIPCHK(hipMemset2DAsync(c->rdsb.state.p, kRdsbStateBytes, 1, 2, ns, c->stream));
+    for (auto& io : c->rdsb.info) fmrx_rds_info_init(&io);
+    c->rdsb.pending = 0;
     reset_rds_sync(c);
     return 0;
 }
@@ -114,28 +126,28 @@ int rds_decode_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, s
     const size_t ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;
     const size_t n_sym = n_if * kRdsbUp / (size_t)(c->geo.bp_fs / 2000) / kRdsbWin * kRdsbSyms;
-    c->rdsb_pending = 0;
+    c->rdsb.pending = 0;
     int rc;
-    if ((rc = c->d_rdsb_mix.ensure(ns * n_if)) || (rc = c->d_rdsb_out.ensure(2 * ns * n_sym))) return rc;
-    if ((rc = run_rds(c, d_demod, demod_stride, n_if, c->d_rdsb_mix.p, nullptr, nullptr))) return rc;
-    if ((rc = run_rds_bits(c, c->d_rdsb_mix.p, n_if, n_blocks, c->d_rdsb_out.p, c->d_rdsb_out.p + ns * n_sym, nullptr,
+    if ((rc = c->rdsb.mix.ensure(ns * n_if)) || (rc = c->rdsb.out.ensure(2 * ns * n_sym))) return rc;
+    if ((rc = run_rds(c, d_demod, demod_stride, n_if, c->rdsb.mix.p, nullptr, nullptr))) return rc;
+    if ((rc = run_rds_bits(c, c->rdsb.mix.p, n_if, n_blocks, c->rdsb.out.p, c->rdsb.out.p + ns * n_sym, nullptr,
                            nullptr)))
         return rc;
-    c->rdsb_host.resize(2 * ns * n_sym);
-    HIPCHK(hipMemcpyAsync(c->rdsb_host.data(), c->d_rdsb_out.p, 2 * ns * n_sym, hipMemcpyDeviceToHost, c->stream));
-    c->rdsb_pending = n_sym;
+    c->rdsb.host.resize(2 * ns * n_sym);
+    HIPCHK(hipMemcpyAsync(c->rdsb.host.data(), c->rdsb.out.p, 2 * ns * n_sym, hipMemcpyDeviceToHost, c->stream));
+    c->rdsb.pending = n_sym;
     // the block sync over the same bits (fmrx_set_rds_sync), behind the copy
-    if (c->rds_sync_on && (rc = rds_sync_enqueue(c, c->d_rdsb_out.p, n_sym))) return rc;
+    if (c->rdss.on && (rc = rds_sync_enqueue(c, c->rdsb.out.p, n_sym))) return rc;
     return 0;
 }
 
 int rds_decode_finish(fmrx_ctx* c) {
-    const size_t ns = c->cfg.n_streams, n = c->rdsb_pending;
+    const size_t ns = c->cfg.n_streams, n = c->rdsb.pending;
     if (n == 0) return 0;
-    c->rdsb_pending = 0;
+    c->rdsb.pending = 0;
     HIPCHK(hipStreamSynchronize(c->stream));
     for (size_t s = 0; s < ns; s++) {
-        int rc = fmrx_rds_parse(&c->rds_info[s], c->rdsb_host.data() + s * n, c->rdsb_host.data() + (ns + s) * n, n);
+        int rc = fmrx_rds_parse(&c->rdsb.info[s], c->rdsb.host.data() + s * n, c->rdsb.host.data() + (ns + s) * n, n);
         if (rc) return rc;
     }
     return rds_sync_finish(c);
@@ -172,18 +184,18 @@ int fmrx_rds_bits(fmrx_ctx* c, const float* rds, size_t n_blocks, uint8_t* bits,
     const size_t ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;
     const size_t n_out = n_if * kRdsbUp / (size_t)(c->geo.bp_fs / 2000), n_win = n_out / kRdsbWin, n_sym = n_win * kRdsbSyms;
-    if ((rc = c->d_f32.ensure(ns * n_if)) || (rc = c->d_rdsb_out.ensure(ns * (2 * n_sym + 2 * n_win))) ||
-        (y && (rc = c->d_scratch.ensure(ns * n_out))))
+    if ((rc = c->io.f32.ensure(ns * n_if)) || (rc = c->rdsb.out.ensure(ns * (2 * n_sym + 2 * n_win))) ||
+        (y && (rc = c->io.scratch.ensure(ns * n_out))))
         return rc;
-    uint8_t* d_bits = c->d_rdsb_out.p;
+    uint8_t* d_bits = c->rdsb.out.p;
     uint8_t* d_codes = d_bits + ns * n_sym;
     uint8_t* d_win = d_codes + ns * n_sym;
-    HIPCHK(hipMemcpyAsync(c->d_f32.p, rds, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_rds_bits(c, c->d_f32.p, n_if, n_blocks, d_bits, d_codes, d_win, y ? c->d_scratch.p : nullptr))) return rc;
+    HIPCHK(hipMemcpyAsync(c->io.f32.p, rds, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_rds_bits(c, c->io.f32.p, n_if, n_blocks, d_bits, d_codes, d_win, y ? c->io.scratch.p : nullptr))) return rc;
     if (bits) HIPCHK(hipMemcpyAsync(bits, d_bits, ns * n_sym, hipMemcpyDeviceToHost, c->stream));
     if (codes) HIPCHK(hipMemcpyAsync(codes, d_codes, ns * n_sym, hipMemcpyDeviceToHost, c->stream));
     if (win) HIPCHK(hipMemcpyAsync(win, d_win, ns * 2 * n_win, hipMemcpyDeviceToHost, c->stream));
-    if (y) HIPCHK(hipMemcpyAsync(y, c->d_scratch.p, sizeof(float) * ns * n_out, hipMemcpyDeviceToHost, c->stream));
+    if (y) HIPCHK(hipMemcpyAsync(y, c->io.scratch.p, sizeof(float) * ns * n_out, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return FMRX_OK;
 }
@@ -239,9 +251,9 @@ int fmrx_rds_decode(fmrx_ctx* c, const float* demod, size_t n_blocks) {
     if (rc || n_blocks == 0) return rc;
     if ((rc = set_device(c))) return rc;
     const size_t n = (size_t)c->cfg.n_streams * n_blocks * c->geo.if_samples;
-    if ((rc = c->d_f32.ensure(n))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_f32.p, demod, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    if ((rc = rds_decode_enqueue(c, c->d_f32.p, n_blocks * c->geo.if_samples, n_blocks))) return rc;
+    if ((rc = c->io.f32.ensure(n))) return rc;
+    HIPCHK(hipMemcpyAsync(c->io.f32.p, demod, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = rds_decode_enqueue(c, c->io.f32.p, n_blocks * c->geo.if_samples, n_blocks))) return rc;
     return rds_decode_finish(c);
 }
 
@@ -249,14 +261,14 @@ int fmrx_rds_info_get(const fmrx_ctx* c, int stream, fmrx_rds_info* out) {
     CtxLock lock_(c);
     if (!c || !out) return fail(FMRX_EINVAL, "null argument");
     if (stream < 0 || stream >= c->cfg.n_streams) return fail(FMRX_EINVAL, "stream %d of %d", stream, c->cfg.n_streams);
-    *out = c->rds_info[(size_t)stream];
+    *out = c->rdsb.info[(size_t)stream];
     return FMRX_OK;
 }
 
 int fmrx_set_rds(fmrx_ctx* c, int on) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null argument");
-    c->rds_on = on != 0;
+    c->rdsb.on = on != 0;
     return FMRX_OK;
 }
 

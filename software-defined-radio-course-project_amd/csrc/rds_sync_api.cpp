@@ -57,20 +57,20 @@ int sync_prepare(fmrx_ctx* c, const fmrx_rds_sync_config* cfg) {
     if (!cfg) cfg = &def;
     int rc = check_sync_config(cfg);
     if (rc) return rc;
-    const auto& cur = c->rdss_cfg;
-    if (c->rdss_seen && (cur.J != cfg->J || cur.V != cfg->V || cur.B != cfg->B))
+    const auto& cur = c->rdss.cfg;
+    if (c->rdss.seen && (cur.J != cfg->J || cur.V != cfg->V || cur.B != cfg->B))
         return fail(FMRX_EINVAL, "RDS sync config changed inside a stream (J %d V %d B %d, now %d %d %d): fmrx_reset first", cur.J,
                     cur.V, cur.B, cfg->J, cfg->V, cfg->B);
-    if ((rc = c->d_rdss_table.ensure(kRdsSyncTable)) || (rc = c->d_rdss_carry.ensure((size_t)kRdsSyncCarry * c->cfg.n_streams)))
+    if ((rc = c->rdss.table.ensure(kRdsSyncTable)) || (rc = c->rdss.carry.ensure((size_t)kRdsSyncCarry * c->cfg.n_streams)))
         return rc;
-    if (c->rdss_table_b != cfg->B) {
+    if (c->rdss.table_b != cfg->B) {
         uint32_t tab[kRdsSyncTable];
         if (!sync_design(cfg->B, tab, nullptr)) return fail(FMRX_ESTATE, "RDS sync: two bursts of length <= %d share a syndrome", cfg->B);
-        HIPCHK(hipMemcpyAsync(c->d_rdss_table.p, tab, sizeof tab, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->rdss.table.p, tab, sizeof tab, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));  // tab is on this call's stack
-        c->rdss_table_b = cfg->B;
+        c->rdss.table_b = cfg->B;
     }
-    c->rdss_cfg = *cfg;
+    c->rdss.cfg = *cfg;
     return 0;
 }
 
@@ -79,18 +79,18 @@ int sync_prepare(fmrx_ctx* c, const fmrx_rds_sync_config* cfg) {
 int run_rds_sync(fmrx_ctx* c, const uint8_t* d_bits, size_t bits_stride, size_t n_new, bool flush, fmrx_rds_block_rec* d_blocks,
                  size_t max_blocks, uint32_t* d_counts) {
     const size_t ns = c->cfg.n_streams;
-    const int J = c->rdss_cfg.J;
+    const int J = c->rdss.cfg.J;
     const uint64_t keep = 25 + 52 * (uint64_t)J, ahead = 26 * (uint64_t)J;
     if (n_new > ((size_t)1 << 30)) return fail(FMRX_EINVAL, "%zu bits: too many for one RDS sync call", n_new);
-    const uint64_t seen = c->rdss_seen, total = seen + n_new;
+    const uint64_t seen = c->rdss.seen, total = seen + n_new;
     const uint64_t n_carry = std::min(seen, keep), base = seen - n_carry;
     const uint64_t upto = flush ? total : (total > ahead ? total - ahead : 0);  // positions below it are judged after this call
-    const uint64_t from = c->rdss_judged, to = std::max(from, upto);
+    const uint64_t from = c->rdss.judged, to = std::max(from, upto);
     RdsSyncLaunch L{};
     L.bits = d_bits;
     L.bits_stride = bits_stride;
-    L.carry = c->d_rdss_carry.p;
-    L.table = c->d_rdss_table.p;
+    L.carry = c->rdss.carry.p;
+    L.table = c->rdss.table.p;
     L.base = base;
     L.n_carry = (int)n_carry;
     L.n_new = (int)n_new;
@@ -99,55 +99,55 @@ int run_rds_sync(fmrx_ctx* c, const uint8_t* d_bits, size_t bits_stride, size_t 
     L.n_judge = (int)(to - from);
     L.n_keep = (int)std::min<uint64_t>(total, keep);
     L.J = J;
-    L.V = c->rdss_cfg.V;
+    L.V = c->rdss.cfg.V;
     L.max_blocks = (unsigned)std::min<size_t>(max_blocks, 0xFFFFFFFFu);
-    int rc = c->d_rdss_work.ensure(ns * (5 * (size_t)L.n_dom + (size_t)L.n_judge) + 1);
+    int rc = c->rdss.work.ensure(ns * (5 * (size_t)L.n_dom + (size_t)L.n_judge) + 1);
     if (rc) return rc;
-    L.cand = c->d_rdss_work.p;
+    L.cand = c->rdss.work.p;
     L.rec = L.cand + ns * 4 * (size_t)L.n_dom;
     L.exact = reinterpret_cast<uint8_t*>(L.rec + ns * (size_t)L.n_judge);  // ns x n_dom bytes in ns x n_dom words
     L.blocks = d_blocks;
     L.counts = d_counts;
     if ((rc = launch_rds_sync(L, (int)ns, c->stream)))
         return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "RDS sync launch failed (%d)", rc);
-    c->rdss_seen = total;
-    c->rdss_judged = to;
+    c->rdss.seen = total;
+    c->rdss.judged = to;
     return 0;
 }
 
 // positions a call of n_new bits (or a flush) judges: the rows a caller's record list needs at most
 size_t sync_judged(const fmrx_ctx* c, size_t n_new, bool flush) {
-    const uint64_t ahead = 26 * (uint64_t)c->rdss_cfg.J, total = c->rdss_seen + n_new;
+    const uint64_t ahead = 26 * (uint64_t)c->rdss.cfg.J, total = c->rdss.seen + n_new;
     const uint64_t upto = flush ? total : (total > ahead ? total - ahead : 0);
-    return upto > c->rdss_judged ? (size_t)(upto - c->rdss_judged) : 0;
+    return upto > c->rdss.judged ? (size_t)(upto - c->rdss.judged) : 0;
 }
 
 // the host forms' tail: counts, then each stream's first min(count, cap) records (one 2-D copy)
 int fetch_blocks(fmrx_ctx* c, size_t cap, fmrx_rds_block_rec* blocks, size_t max_blocks, uint32_t* counts) {
     const size_t ns = c->cfg.n_streams;
-    c->rdss_counts.resize(ns);
-    HIPCHK(hipMemcpyAsync(c->rdss_counts.data(), c->d_rdss_counts.p, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, c->stream));
+    c->rdss.counts_host.resize(ns);
+    HIPCHK(hipMemcpyAsync(c->rdss.counts_host.data(), c->rdss.counts.p, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     size_t most = 0;
-    for (size_t s = 0; s < ns; s++) most = std::max<size_t>(most, std::min<size_t>(c->rdss_counts[s], cap));
-    c->rdss_host.resize(ns * most);
+    for (size_t s = 0; s < ns; s++) most = std::max<size_t>(most, std::min<size_t>(c->rdss.counts_host[s], cap));
+    c->rdss.host.resize(ns * most);
     if (most)
-        HIPCHK(hipMemcpy2D(c->rdss_host.data(), most * sizeof(fmrx_rds_block_rec), c->d_rdss_blocks.p, cap * sizeof(fmrx_rds_block_rec),
+        HIPCHK(hipMemcpy2D(c->rdss.host.data(), most * sizeof(fmrx_rds_block_rec), c->rdss.blocks.p, cap * sizeof(fmrx_rds_block_rec),
                            most * sizeof(fmrx_rds_block_rec), ns, hipMemcpyDeviceToHost));
-    c->rdss_most = most;
+    c->rdss.most = most;
     for (size_t s = 0; s < ns; s++) {
-        if (counts) counts[s] = c->rdss_counts[s];
+        if (counts) counts[s] = c->rdss.counts_host[s];
         if (blocks && max_blocks)
-            std::memcpy(blocks + s * max_blocks, c->rdss_host.data() + s * most,
-                        sizeof(fmrx_rds_block_rec) * std::min<size_t>({(size_t)c->rdss_counts[s], cap, max_blocks}));
+            std::memcpy(blocks + s * max_blocks, c->rdss.host.data() + s * most,
+                        sizeof(fmrx_rds_block_rec) * std::min<size_t>({(size_t)c->rdss.counts_host[s], cap, max_blocks}));
     }
     return 0;
 }
 
 int parse_fetched(fmrx_ctx* c, size_t cap, uint64_t n_bits, int flush) {
     for (size_t s = 0; s < (size_t)c->cfg.n_streams; s++) {
-        int rc = fmrx_rds_parse_blocks(&c->rds_ext[s], c->rdss_host.data() + s * c->rdss_most,
-                                       std::min<size_t>(c->rdss_counts[s], cap), n_bits, flush);
+        int rc = fmrx_rds_parse_blocks(&c->rdss.ext[s], c->rdss.host.data() + s * c->rdss.most,
+                                       std::min<size_t>(c->rdss.counts_host[s], cap), n_bits, flush);
         if (rc) return rc;
     }
     return 0;
@@ -274,31 +274,31 @@ void ext_close(fmrx_rds_ext* x, uint64_t before, bool all) {
 namespace fmrx {
 
 void reset_rds_sync(fmrx_ctx* c) {
-    c->rdss_seen = 0;
-    c->rdss_judged = 0;
-    c->rdss_pending = false;
-    for (auto& x : c->rds_ext) fmrx_rds_ext_init(&x);
+    c->rdss.seen = 0;
+    c->rdss.judged = 0;
+    c->rdss.pending = false;
+    for (auto& x : c->rdss.ext) fmrx_rds_ext_init(&x);
 }
 
 int rds_sync_enqueue(fmrx_ctx* c, const uint8_t* d_bits, size_t n_bits) {
     const size_t ns = c->cfg.n_streams;
-    c->rdss_pending = false;
+    c->rdss.pending = false;
     int rc = sync_prepare(c, nullptr);
     if (rc) return rc;
     const size_t cap = sync_judged(c, n_bits, false);
-    if ((rc = c->d_rdss_blocks.ensure(ns * cap)) || (rc = c->d_rdss_counts.ensure(ns))) return rc;
-    if ((rc = run_rds_sync(c, d_bits, n_bits, n_bits, false, c->d_rdss_blocks.p, cap, c->d_rdss_counts.p))) return rc;
-    c->rdss_pending = true;
-    c->rdss_cap = cap;
-    c->rdss_bits = n_bits;
+    if ((rc = c->rdss.blocks.ensure(ns * cap)) || (rc = c->rdss.counts.ensure(ns))) return rc;
+    if ((rc = run_rds_sync(c, d_bits, n_bits, n_bits, false, c->rdss.blocks.p, cap, c->rdss.counts.p))) return rc;
+    c->rdss.pending = true;
+    c->rdss.cap = cap;
+    c->rdss.bits = n_bits;
     return 0;
 }
 
 int rds_sync_finish(fmrx_ctx* c) {
-    if (!c->rdss_pending) return 0;
-    c->rdss_pending = false;
-    int rc = fetch_blocks(c, c->rdss_cap, nullptr, 0, nullptr);
-    return rc ? rc : parse_fetched(c, c->rdss_cap, c->rdss_bits, 0);
+    if (!c->rdss.pending) return 0;
+    c->rdss.pending = false;
+    int rc = fetch_blocks(c, c->rdss.cap, nullptr, 0, nullptr);
+    return rc ? rc : parse_fetched(c, c->rdss.cap, c->rdss.bits, 0);
 }
 
 }  // namespace fmrx
@@ -337,27 +337,27 @@ int fmrx_rds_blocks(fmrx_ctx* c, const fmrx_rds_sync_config* cfg, const uint8_t*
     const size_t ns = c->cfg.n_streams;
     if (n_bits > ((size_t)1 << 30)) return fail(FMRX_EINVAL, "%zu bits: too many for one RDS sync call", n_bits);
     const size_t cap = sync_judged(c, n_bits, false);
-    if ((rc = c->d_rdss_in.ensure(ns * n_bits)) || (rc = c->d_rdss_blocks.ensure(ns * cap)) || (rc = c->d_rdss_counts.ensure(ns)))
+    if ((rc = c->rdss.in.ensure(ns * n_bits)) || (rc = c->rdss.blocks.ensure(ns * cap)) || (rc = c->rdss.counts.ensure(ns)))
         return rc;
-    if (n_bits) HIPCHK(hipMemcpyAsync(c->d_rdss_in.p, bits, ns * n_bits, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_rds_sync(c, c->d_rdss_in.p, n_bits, n_bits, false, c->d_rdss_blocks.p, cap, c->d_rdss_counts.p))) return rc;
+    if (n_bits) HIPCHK(hipMemcpyAsync(c->rdss.in.p, bits, ns * n_bits, hipMemcpyHostToDevice, c->stream));
+    if ((rc = run_rds_sync(c, c->rdss.in.p, n_bits, n_bits, false, c->rdss.blocks.p, cap, c->rdss.counts.p))) return rc;
     return fetch_blocks(c, cap, blocks, max_blocks, counts);
 }
 
 int fmrx_rds_blocks_flush(fmrx_ctx* c, fmrx_rds_block_rec* blocks, size_t max_blocks, uint32_t* counts) {
     CtxLock lock_(c);
     if (!c || (!blocks && max_blocks)) return fail(FMRX_EINVAL, "null argument");
-    if (c->rdss_seen == 0) {  // nothing given since the reset: nothing pending (and perhaps nothing allocated)
+    if (c->rdss.seen == 0) {  // nothing given since the reset: nothing pending (and perhaps nothing allocated)
         if (counts) std::memset(counts, 0, sizeof(uint32_t) * (size_t)c->cfg.n_streams);
         return FMRX_OK;
     }
     int rc = set_device(c);
     if (rc) return rc;
     const size_t ns = c->cfg.n_streams, cap = sync_judged(c, 0, true);
-    if ((rc = c->d_rdss_blocks.ensure(ns * cap)) || (rc = c->d_rdss_counts.ensure(ns))) return rc;
-    if ((rc = run_rds_sync(c, nullptr, 0, 0, true, c->d_rdss_blocks.p, cap, c->d_rdss_counts.p))) return rc;
+    if ((rc = c->rdss.blocks.ensure(ns * cap)) || (rc = c->rdss.counts.ensure(ns))) return rc;
+    if ((rc = run_rds_sync(c, nullptr, 0, 0, true, c->rdss.blocks.p, cap, c->rdss.counts.p))) return rc;
     if ((rc = fetch_blocks(c, cap, blocks, max_blocks, counts))) return rc;
-    return c->rds_sync_on ? parse_fetched(c, cap, 0, 1) : FMRX_OK;
+    return c->rdss.on ? parse_fetched(c, cap, 0, 1) : FMRX_OK;
 }
 
 int fmrx_rds_ext_init(fmrx_rds_ext* io) {
@@ -404,7 +404,7 @@ int fmrx_set_rds_sync(fmrx_ctx* c, int on) {
         int rc = set_device(c);
         if (rc || (rc = sync_prepare(c, nullptr))) return rc;
     }
-    c->rds_sync_on = on != 0;
+    c->rdss.on = on != 0;
     return FMRX_OK;
 }
 
@@ -412,7 +412,7 @@ int fmrx_rds_ext_get(const fmrx_ctx* c, int stream, fmrx_rds_ext* out) {
     CtxLock lock_(c);
     if (!c || !out) return fail(FMRX_EINVAL, "null argument");
     if (stream < 0 || stream >= c->cfg.n_streams) return fail(FMRX_EINVAL, "stream %d of %d", stream, c->cfg.n_streams);
-    *out = c->rds_ext[(size_t)stream];
+    *out = c->rdss.ext[(size_t)stream];
     return FMRX_OK;
 }
 

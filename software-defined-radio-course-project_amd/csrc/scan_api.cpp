@@ -18,17 +18,17 @@ int psd_run(fmrx_ctx* c, const float* d_x, size_t n, int freq_bins, float fs, fl
         return fail(FMRX_EINVAL, "freq_bins must be a power of two in [2, %d]", kPsdMaxBins);
     const size_t nseg = n / (size_t)N;
     if (nseg < 1) return fail(FMRX_EINVAL, "need at least freq_bins samples");
-    int rc = c->d_scratch.ensure((size_t)N + nseg * (N / 2));
+    int rc = c->io.scratch.ensure((size_t)N + nseg * (N / 2));
     if (rc) return rc;
     std::vector<float> hann(N);
     for (int i = 0; i < N; i++) {
         const double s = std::sin(i * 3.14159265358979323846 / N);  // PI, dy4.h:14
         hann[i] = (float)(s * s);
     }
-    HIPCHK(hipMemcpyAsync(c->d_scratch.p, hann.data(), sizeof(float) * N, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->io.scratch.p, hann.data(), sizeof(float) * N, hipMemcpyHostToDevice, c->stream));
     // psd_seg = (4 / (Fs * freq_bins)) * |X|^2 (fourier.cpp:103)
     const double scale = 4.0 / ((double)fs * (double)N);
-    if (launch_psd(d_x, (int)nseg, N, c->d_scratch.p, scale, c->d_scratch.p + N, d_psd, c->stream))
+    if (launch_psd(d_x, (int)nseg, N, c->io.scratch.p, scale, c->io.scratch.p + N, d_psd, c->stream))
         return fail(FMRX_EHIP, "PSD launch failed");
     HIPCHK(hipStreamSynchronize(c->stream));  // the window lives in host memory until here
     return 0;
@@ -50,10 +50,10 @@ int fmrx_estimate_psd(fmrx_ctx* c, const float* samples, size_t n, int freq_bins
     if (rc) return rc;
     if (freq_bins < 2) return fail(FMRX_EINVAL, "freq_bins must be >= 2");
     const size_t used = n / (size_t)freq_bins * (size_t)freq_bins;
-    if ((rc = c->d_f32.ensure(used + (size_t)freq_bins / 2))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_f32.p, samples, sizeof(float) * used, hipMemcpyHostToDevice, c->stream));
-    if ((rc = psd_run(c, c->d_f32.p, used, freq_bins, fs, c->d_f32.p + used))) return rc;
-    HIPCHK(hipMemcpy(psd, c->d_f32.p + used, sizeof(float) * (freq_bins / 2), hipMemcpyDeviceToHost));
+    if ((rc = c->io.f32.ensure(used + (size_t)freq_bins / 2))) return rc;
+    HIPCHK(hipMemcpyAsync(c->io.f32.p, samples, sizeof(float) * used, hipMemcpyHostToDevice, c->stream));
+    if ((rc = psd_run(c, c->io.f32.p, used, freq_bins, fs, c->io.f32.p + used))) return rc;
+    HIPCHK(hipMemcpy(psd, c->io.f32.p + used, sizeof(float) * (freq_bins / 2), hipMemcpyDeviceToHost));
     const float df = fs / (float)freq_bins;  // fourier.cpp:42-50
     for (int i = 0; i < freq_bins / 2; i++) freq[i] = (float)i * df;
     return FMRX_OK;
@@ -79,22 +79,22 @@ int scan_check_size(int fft_bins, size_t n_pairs) {
 int scan_run(fmrx_ctx* c, const uint8_t* d_iq, size_t n_pairs, int N, float* d_power) {
     int rc;
     const size_t nseg = n_pairs / (size_t)N;
-    if (c->scan_bins != N) {  // tables of this size: stream-ordered behind a scan still in flight
-        c->scan_bins = 0;
+    if (c->scan.bins != N) {  // tables of this size: stream-ordered behind a scan still in flight
+        c->scan.bins = 0;
         HIPCHK(hipStreamSynchronize(c->stream));  // the host copy is replaced below
-        c->scan_tab.resize(3 * (size_t)N);
-        scan_tables(N, c->scan_tab.data(), c->scan_tab.data() + 2 * (size_t)N);
-        if ((rc = c->d_scan_tab.ensure(3 * (size_t)kScanMaxBins))) return rc;
-        HIPCHK(hipMemcpyAsync(c->d_scan_tab.p, c->scan_tab.data(), sizeof(float) * c->scan_tab.size(),
+        c->scan.tab_host.resize(3 * (size_t)N);
+        scan_tables(N, c->scan.tab_host.data(), c->scan.tab_host.data() + 2 * (size_t)N);
+        if ((rc = c->scan.tab.ensure(3 * (size_t)kScanMaxBins))) return rc;
+        HIPCHK(hipMemcpyAsync(c->scan.tab.p, c->scan.tab_host.data(), sizeof(float) * c->scan.tab_host.size(),
                               hipMemcpyHostToDevice, c->stream));
-        c->scan_bins = N;
+        c->scan.bins = N;
     }
-    if (reinterpret_cast<uintptr_t>(d_iq) % c->pair_bytes != 0)
-        return fail(FMRX_EINVAL, "scan: the capture must be aligned to one %zu-byte I/Q pair", c->pair_bytes);
-    const int G = scan_workgroups(N, nseg, c->n_simd / 4, c->iq_format);
+    if (reinterpret_cast<uintptr_t>(d_iq) % c->front.pair_bytes != 0)
+        return fail(FMRX_EINVAL, "scan: the capture must be aligned to one %zu-byte I/Q pair", c->front.pair_bytes);
+    const int G = scan_workgroups(N, nseg, c->n_simd / 4, c->front.format);
     if (G < 1) return fail(FMRX_EHIP, "scan: no resident workgroup for %d bins", N);
-    if ((rc = c->d_scan_part.ensure((size_t)G * N))) return rc;
-    rc = launch_scan(d_iq, c->iq_format, nseg, N, c->d_scan_tab.p, c->d_scan_tab.p + 2 * (size_t)N, c->d_scan_part.p, G, d_power,
+    if ((rc = c->scan.part.ensure((size_t)G * N))) return rc;
+    rc = launch_scan(d_iq, c->front.format, nseg, N, c->scan.tab.p, c->scan.tab.p + 2 * (size_t)N, c->scan.part.p, G, d_power,
                      c->stream);
     if (rc) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "scan launch failed");
     return 0;
@@ -114,12 +114,12 @@ int fmrx_scan_spectrum(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, int fft_b
     if (!c || !iq || !power) return fail(FMRX_EINVAL, "null argument");
     int rc = scan_check_size(fft_bins, n_pairs);
     if (rc || (rc = set_device(c))) return rc;
-    const size_t nseg = n_pairs / (size_t)fft_bins, bytes = c->pair_bytes * nseg * (size_t)fft_bins;
-    if ((rc = c->d_scan_in.ensure(bytes)) || (rc = c->d_scan_power.ensure(kScanMaxBins))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_scan_in.p, iq, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = scan_run(c, c->d_scan_in.p, nseg * (size_t)fft_bins, fft_bins, c->d_scan_power.p))) return rc;
+    const size_t nseg = n_pairs / (size_t)fft_bins, bytes = c->front.pair_bytes * nseg * (size_t)fft_bins;
+    if ((rc = c->scan.in.ensure(bytes)) || (rc = c->scan.power.ensure(kScanMaxBins))) return rc;
+    HIPCHK(hipMemcpyAsync(c->scan.in.p, iq, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = scan_run(c, c->scan.in.p, nseg * (size_t)fft_bins, fft_bins, c->scan.power.p))) return rc;
     std::vector<float> got((size_t)fft_bins);  // the caller's buffer is written only on success
-    HIPCHK(hipMemcpyAsync(got.data(), c->d_scan_power.p, sizeof(float) * fft_bins, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(got.data(), c->scan.power.p, sizeof(float) * fft_bins, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     std::copy(got.begin(), got.end(), power);
     if (n_segments) *n_segments = nseg;
@@ -261,8 +261,8 @@ int fmrx_scan_wide(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_sc
                    int max_out, int* n_found) {
     CtxLock lock_(c);
     if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
-    if (!c->ratio.on()) return fail(FMRX_ESTATE, "fmrx_scan_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
-    return scan_both(c, iq, n_pairs, c->ratio.cap_fs(c->geo.rf_fs), cfg_in, out, max_out, n_found);
+    if (!c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_scan_wide: the capture decimation is 1 (fmrx_set_capture_decim first)");
+    return scan_both(c, iq, n_pairs, c->wide.ratio.cap_fs(c->geo.rf_fs), cfg_in, out, max_out, n_found);
 }
 
 int fmrx_scan(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_config* cfg_in, fmrx_station* out,
@@ -271,7 +271,7 @@ int fmrx_scan(fmrx_ctx* c, const uint8_t* iq, size_t n_pairs, const fmrx_scan_co
     if (!c || !iq || !n_found) return fail(FMRX_EINVAL, "null argument");
     // kept as it was: on a context at a rational rate this call has always scanned at the capture's rate,
     // as fmrx_scan_wide does, and at rf_fs on every other (fmrx.h promises rf_fs throughout)
-    const int fs = c->ratio.rational() ? c->ratio.cap_fs(c->geo.rf_fs) : c->geo.rf_fs;
+    const int fs = c->wide.ratio.rational() ? c->wide.ratio.cap_fs(c->geo.rf_fs) : c->geo.rf_fs;
     return scan_both(c, iq, n_pairs, fs, cfg_in, out, max_out, n_found);
 }
 
