@@ -144,10 +144,27 @@ void launch_pll_sat(dim3 grid, dim3 block, hipStream_t s, const float* io, int n
 void launch_pll_pred(int waves, hipStream_t s, const float* io, int n, int n_streams, int spw, size_t stride,
                      const double* side, size_t seg, double step, float norm_bw, const float* st, float* out,
                      size_t ostride, int* fail, float2* rec, size_t rb, int inject, int sat_ok, int pipe_on);
-// pll_pred.hip: the three-wave runner for one stream a workgroup (spw == 1) from trigOffset 2^20,
+// The arguments of a self-certifying runner launch (pll_pipe.hip, pll_idx.hip, pll_cnt.hip) and of
+// the demoted kernel that follows it (pll_demote.hip): samples [0, n) of io (stream stride `stride`)
+// from the state st; their trigArgs to out (stride ostride), the exact end state to st.  inject /
+// miss: the test hooks below; stats, redos (may be null): fmrx_debug_pll_stats / _redos.
+struct PllRunnerArgs {
+    hipStream_t s;
+    const float* io;
+    int n, n_streams;
+    size_t stride;
+    double step;
+    float norm_bw;
+    float* st;
+    float* out;
+    size_t ostride;
+    int inject, miss;
+    unsigned long long* stats;
+    unsigned* redos;
+};
+// pll_pipe.hip: the three-wave runner for one stream a workgroup (spw == 1) from trigOffset 2^20,
 // the stick included (pll_pipe_stream), self-certifying (no check / resume kernel): one launch runs
-// samples [0, n) of io (stream stride `stride`) from the state st and writes their trigArgs to out
-// (stride ostride) and the exact end state to st.  Its forms (pll_forms.h kPllForms: domains and
+// the whole range and leaves the exact end state.  Its forms (pll_forms.h kPllForms: domains and
 // interval lengths), by default: 22, 3 candidates, 256-step intervals (trigOffset from 2^22); 23,
 // the same at the stuck trigOffset 2^24; 25, the same in 128-step intervals (short calls); 21, 5
 // candidates, 128 steps ([2^21, 2^22)); 20, 5 candidates, 16 steps ([2^20, 2^21)); 24, the same
@@ -155,37 +172,30 @@ void launch_pll_pred(int waves, hipStream_t s, const float* io, int n, int n_str
 // exact path (a wrong host hint costs speed, not bits).  miss >= 1 / inject >= 0 (test hooks):
 // a forced miss on interval `miss` / interval 1 + (inject + s) % intervals, so the exact redo
 // runs.  stats (may be null): += batches redone exactly, batches run.
-void launch_pll_pipe(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step, float norm_bw,
-                     float* st, float* out, size_t ostride, int inject, int miss, int form,
-                     unsigned long long* stats, unsigned* redos = nullptr);
+void launch_pll_pipe(const PllRunnerArgs& a, int form);
 
-// pll_pred.hip: the index runner (one stream a workgroup: the chain and four evaluator waves
+// pll_idx.hip: the index runner (one stream a workgroup: the chain and four evaluator waves
 // for forms 17 / 18, three for form 19 -- a CU a stream, two of the five waves sharing a SIMD),
-// self-certifying like launch_pll_pipe, same arguments; form 17: 32 candidates ([2^17, 2^18)),
+// self-certifying like launch_pll_pipe; form 17: 32 candidates ([2^17, 2^18)),
 // 18: 32 ([2^18, 2^19)), 19: 16 ([2^19, 2^20)).  A stream outside the form's domain runs the
 // range exactly.  Returns non-zero when the form's workgroup cannot be resident on one CU (its
 // registers) or the launch fails.
-int launch_pll_idx(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step, float norm_bw,
-                   float* st, float* out, size_t ostride, int inject, int miss, int form, unsigned long long* stats,
-                   unsigned* redos = nullptr);
-// pll_pred.hip: the count runner (pll_cnt_kernel: the chain picks each step's e by one compare of
+int launch_pll_idx(const PllRunnerArgs& a, int form);
+// pll_cnt.hip: the count runner (pll_cnt_kernel: the chain picks each step's e by one compare of
 // the phase against a row of exact thresholds and a bit count), one stream a workgroup of five
-// waves (a CU), self-certifying, same arguments as launch_pll_idx; form 17 / 18: [2^17, 2^18) /
+// waves (a CU), self-certifying, returns as launch_pll_idx; form 17 / 18: [2^17, 2^18) /
 // [2^18, 2^19), 31 candidates, 16-step intervals; 19: [2^19, 2^20), 15, 64 steps; 20: [2^20,
 // 2^21), 15, 128 steps; 21: [2^21, 2^22), 7, 64 steps (pll_forms.h kPllForms, by default).
-int launch_pll_cnt(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step, float norm_bw,
-                   float* st, float* out, size_t ostride, int inject, int miss, int form, unsigned long long* stats,
-                   unsigned* redos = nullptr);
+int launch_pll_cnt(const PllRunnerArgs& a, int form);
 // pll_demote.hip: the rest of a self-certifying runner launch's range for the streams it demoted
-// (pll_device.h pll_demote): the same arguments as the runner launch it follows on stream s.  That
-// launch leaves each stream's first step for this kernel in the PLL state's slot 6 (int bits; 0:
+// (pll_device.h pll_demote): the arguments of the runner launch it follows on stream s (miss and
+// redos unused).  That launch leaves each stream's first step for this kernel in the PLL state's slot 6 (int bits; 0:
 // not demoted), which this kernel clears.  One stream a workgroup: a speculative chain
 // (pll_spec_lane_kernel's step) checked a sub-segment behind by the other waves, which also form
 // its side data; a batch that does not verify is recomputed exactly and the chain resumes after it.
 // Only a range of at least kPllDemoteMinIntervals of its form's intervals can demote: the plan
 // queues pll_demoted_kernel after exactly those (PllStep::demote_after, or once a call).
-int launch_pll_demoted(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step,
-                       float norm_bw, float* st, float* out, size_t ostride, int inject, unsigned long long* stats);
+int launch_pll_demoted(const PllRunnerArgs& a);
 // fmrx_debug_pll_redos: per stream kPllRedoSlots u32, by the trigOffset range r of the runner's
 // launch (0 [2^17, 2^20), 1 [2^20, 2^21), 2 [2^21, 2^22), 3 from 2^22, the stick included):
 // slot r the intervals the self-certifying runners redid exactly, slot 4 + r the steps they ran

@@ -1,8 +1,8 @@
 // pll.hip — the PLL (src/filter.cpp:136-174) of the stereo pilot and the RDS carrier: the
 // segment kernels (side data, the lane / many-stream speculative runners, the parallel check, the
 // certified resume) and launch_pll, which runs the plan of pll_plan.cpp.  The other runners are
-// translation units of their own (pll_sat.hip, pll_pred.hip, pll_demote.hip: built without the
-// SLP vectoriser; these kernels are faster with it, see the Makefile); the NCO pass that ends a
+// translation units of their own (pll_sat.hip, pll_pred.hip, pll_pipe.hip, pll_idx.hip, pll_cnt.hip,
+// pll_demote.hip: built without the SLP vectoriser; these kernels are faster with it, see the Makefile); the NCO pass that ends a
 // call is stereo.hip's (launch_nco_pass), beside the audio kernel that inlines it.
 #include <hip/hip_runtime.h>
 
@@ -610,28 +610,26 @@ void launch_segment_stage(const PllCall& c, const PllStep& p, int kind) {
     }
 }
 
-int launch_demoted(const PllCall& c, const PllStep& p) {
-    return launch_pll_demoted(c.s, c.io + p.off, (int)p.len, c.n_streams, c.stride, c.step, c.norm_bw, c.st,
-                              c.out + p.off, c.ostride, c.inject, c.stats);
+// The arguments of a Range step's launches: the form's runner and the demoted kernel after it.
+PllRunnerArgs runner_args(const PllCall& c, const PllStep& p) {
+    return {c.s, c.io + p.off, (int)p.len, c.n_streams, c.stride, c.step, c.norm_bw, c.st, c.out + p.off, c.ostride,
+            c.inject, c.pipe_miss, c.stats, c.redos};
 }
+
+int launch_demoted(const PllCall& c, const PllStep& p) { return launch_pll_demoted(runner_args(c, p)); }
 
 // A Range step: the form's self-certifying launch on its runner, then (demote_after) the demoted
 // kernel over the rest of the range of the streams that launch demoted.
 int launch_range(const PllCall& c, const PllStep& p) {
-    const float* x = c.io + p.off;
-    float* out = c.out + p.off;
-    const int m = (int)p.len;
+    const PllRunnerArgs a = runner_args(c, p);
     int rc = 0;
     if (p.cnt)
-        rc |= launch_pll_cnt(c.s, x, m, c.n_streams, c.stride, c.step, c.norm_bw, c.st, out, c.ostride, c.inject,
-                             c.pipe_miss, p.form, c.stats, c.redos);
+        rc |= launch_pll_cnt(a, p.form);
     else if (p.form < 20)
-        rc |= launch_pll_idx(c.s, x, m, c.n_streams, c.stride, c.step, c.norm_bw, c.st, out, c.ostride, c.inject,
-                             c.pipe_miss, p.form, c.stats, c.redos);
+        rc |= launch_pll_idx(a, p.form);
     else
-        launch_pll_pipe(c.s, x, m, c.n_streams, c.stride, c.step, c.norm_bw, c.st, out, c.ostride, c.inject,
-                        c.pipe_miss, p.form, c.stats, c.redos);
-    if (p.demote_after) rc |= launch_demoted(c, p);
+        launch_pll_pipe(a, p.form);
+    if (p.demote_after) rc |= launch_pll_demoted(a);
     return rc;
 }
 

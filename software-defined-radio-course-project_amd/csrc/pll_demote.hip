@@ -1,7 +1,7 @@
 // pll_demote.hip — the PLL (src/filter.cpp:157-171) of a stream a self-certifying runner demoted.
 //
-// The runners of pll_pred.hip select each step's e among candidates predicted from the phase one
-// or two intervals back.  On an unlocked loop (no pilot, heavy noise, random bytes; the PLL of
+// The runners of pll_pipe.hip, pll_idx.hip and pll_cnt.hip select each step's e among candidates
+// predicted from the phase one or two intervals back.  On an unlocked loop (no pilot, heavy noise, random bytes; the PLL of
 // modes 2 and 3, which the reference hands the upsampled if_fs, project.cpp:166,348,357) the phase
 // moves many candidate cells an interval, nearly every interval misses and is redone on the exact
 // path: ~400 ns a step (profiles/r06/unlocked.json, before this kernel).  pll_demote (pll_device.h)
@@ -417,18 +417,16 @@ pll_demoted_kernel(const float* io, int n, size_t stride, double step, float nor
 
 }  // namespace
 
-int launch_pll_demoted(hipStream_t s, const float* io, int n, int n_streams, size_t stride, double step,
-                       float norm_bw, float* st, float* out, size_t ostride, int inject,
-                       unsigned long long* stats) {
-    if (n <= 0) return 0;
+int launch_pll_demoted(const PllRunnerArgs& a) {
+    if (a.n <= 0) return 0;
     static const int resident = [] {
         int nb = 0;
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pll_demoted_kernel, 64 * kDemW, 0) == hipSuccess
                    ? nb : 0;
     }();
     if (resident < 1) return -1;
-    hipLaunchKernelGGL(pll_demoted_kernel, dim3(n_streams), dim3(64 * kDemW), 0, s, io, n, stride, step, norm_bw, st,
-                       out, ostride, inject, stats);
+    hipLaunchKernelGGL(pll_demoted_kernel, dim3(a.n_streams), dim3(64 * kDemW), 0, a.s, a.io, a.n, a.stride, a.step,
+                       a.norm_bw, a.st, a.out, a.ostride, a.inject, a.stats);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -1,7 +1,8 @@
 // pll_device.h — device pieces of the stereo pilot PLL (src/filter.cpp:136-174) shared by
-// pll.hip (the runners, check and resume kernels) and pll_sat.hip (the saturated-segment
-// runner, built as its own translation unit: see the Makefile).  The regime boundaries and launch
-// constants the kernels share with the host's plan are pll_forms.h's.
+// pll.hip (the runners, check and resume kernels), pll_sat.hip (the saturated-segment runner, built
+// as its own translation unit: see the Makefile) and, through pll_runner.h, the predicted-trigArg
+// runners.  The regime boundaries and launch constants the kernels share with the host's plan are
+// pll_forms.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,8 +71,8 @@ __device__ __noinline__ PllPair pll_redo(PllState p, PllCtx ctx, const float* xb
     return PllPair{p, ctx};
 }
 
-// Demotion of a self-certifying runner's stream (pll_pred.hip): the chain keeps the verdicts of
-// its last 32 intervals as bits; past kPllDemoteMisses misses among them the trigArgs are not
+// Demotion of a self-certifying runner's stream (pll_pipe.hip, pll_idx.hip, pll_cnt.hip): the chain
+// keeps the verdicts of its last 32 intervals as bits; past kPllDemoteMisses misses among them the trigArgs are not
 // where the candidates are predicted (an unlocked loop: no pilot, noise, mode 2/3's if_fs, whose
 // phase moves many candidate cells an interval) and the runner leaves the rest of its range to
 // pll_demoted_kernel (pll_demote.hip: a speculative chain checked behind it, ~lane-runner speed)

@@ -603,13 +603,16 @@ def test_pll_speculation_fallbacks(fmrx, orc, monkeypatch, env, n_streams, nb):
         assert np.array_equal(out2[0], want2)
 
 
-@pytest.mark.parametrize("skew", [4194304.0, 1048576.0, 16777216.0])
+@pytest.mark.parametrize("skew", [4194304.0, 1048576.0, 16777216.0, 200000.0, 600000.0])
 def test_pll_wrong_hint_fails_safe(fmrx, orc, monkeypatch, skew):
     """The host picks a segment's runners from its trigOffset bounds (ctx.h TrigTrack).  With
     the bounds deliberately wrong (test hook knob pll_hint_skew: the host believes the streams
     are `skew` samples further on), the runners launched leave the streams alone; the pre-pass's
     fail[] sentinel (0) then makes pll_kernel resume each such stream's whole segment on the
-    certified path: slower, bit-identical (stats: every checked batch resumed)."""
+    certified path: slower, bit-identical (stats: every checked batch resumed).  A self-certifying
+    launch finds its streams outside its form's domain and runs its range exactly: the three-wave
+    forms with the skews from 2^20 on, the index form [2^17, 2^18) with 200,000 and the count form
+    [2^19, 2^20) with 600,000 (19,200 steps a stream: inside that form's range throughout)."""
     knobs(monkeypatch, fmrx, pll_hint_skew=skew)
     nb, bb, n_streams = 30, 12800, 3
     ins = np.stack([iqgen.make(f"synth:{950 + s}", nb * bb) for s in range(n_streams)])
@@ -890,7 +893,7 @@ def test_pll_primitive_states(fmrx, orc, trig, phase, freq, fs, n, offset):
 @pytest.mark.parametrize("sat,pipe", [("1", "1"), ("1", "0"), ("0", "0")])
 def test_pll_saturated_runner(fmrx, orc, monkeypatch, inject, sat, pipe, freq, nco_scale):
     """A segment that starts with trigOffset stuck at 2^24 (filter.cpp:165-166 in float, 69.9 s
-    into a stream): the three-wave runner (pll_pred.hip pll_pipe_kernel, which takes one stream
+    into a stream): the three-wave runner (pll_pipe.hip pll_pipe_kernel, which takes one stream
     a workgroup), with it off the saturated-segment runner (pll_sat.hip), with both off the
     two-wave predicted runner; and a corrupted runner batch (check + certified resume).  The
     speculation counters must show every batch verified without the corruption -- a runner
@@ -926,7 +929,7 @@ def test_pll_saturated_runner(fmrx, orc, monkeypatch, inject, sat, pipe, freq, n
 @pytest.mark.parametrize("pred,pipe", [("1", "1"), ("1", "0"), ("0", "0")])
 def test_pll_predicted_runner(fmrx, orc, monkeypatch, trig0, inject, pred, pipe):
     """Segments from trigOffset 2^20 up to the 2^24 stick: the predicted-trigArg runners
-    (pll_pred.hip: three waves one stream a workgroup -- five candidates in 16-step intervals from
+    (pll_pipe.hip: three waves one stream a workgroup -- five candidates in 16-step intervals from
     2^20, in 64-step ones from 2^21, three candidates from 2^22; knob pll_pipe=0: the two-wave
     runner throughout; knob pll_pred=0: the lane runner), starting at 2^20, at 2^21 + 33, 100 steps
     below 2^22 (its form runs on past it), at 2^22 + 17, and 5,000 steps below the stick (its pr
@@ -1001,7 +1004,7 @@ def test_pll_pipe_redo(fmrx, orc, monkeypatch, trig0, miss, stick):
 @pytest.mark.parametrize("inject", [None, "5"])
 @pytest.mark.parametrize("idx", ["1", "0", "2", None])
 def test_pll_index_runner(fmrx, orc, monkeypatch, trig0, inject, idx):
-    """trigOffset in [2^17, 2^20): the index runner (pll_pred.hip pll_idx_kernel: the chain forms
+    """trigOffset in [2^17, 2^20): the index runner (pll_idx.hip pll_idx_kernel: the chain forms
     trigArg itself and reads its e from a lane of a candidate row -- 32 candidates from 2^17 and
     from 2^18, 16 from 2^19; knob pll_idx=1: from 2^18 only, the lane runner below), starting at
     2^17 (the default, knob pll_idx=2 or unset, starts there; with 1 the lane runner hands over at
@@ -1039,15 +1042,16 @@ def test_pll_index_runner(fmrx, orc, monkeypatch, trig0, inject, idx):
 
 
 @pytest.mark.parametrize("trig0", [131072.0, 262177.0, 524188.0, 700000.0, 1048500.0, 1048576.0, 1500000.0,
-                                   2097100.0, 3000000.0])
+                                   2097100.0, 3000000.0, 262124.0])
 @pytest.mark.parametrize("hook", [None, ("pll_inject", 5), ("pll_pipe_miss", 1), ("pll_pipe_miss", 300)])
 @pytest.mark.parametrize("cnt", [31, 0])
 def test_pll_count_runner(fmrx, orc, monkeypatch, trig0, hook, cnt):
-    """trigOffset in [2^17, 2^22) on the count runner (pll_pred.hip pll_cnt_kernel: one compare
+    """trigOffset in [2^17, 2^22) on the count runner (pll_cnt.hip pll_cnt_kernel: one compare
     of the phase against a row of exact thresholds and a bit count pick each step's e; knob
     pll_cnt = 31: every form from 2^17 to 2^22 on it, 0: none -- the index and three-wave runners),
     starting at each form's edge, just below the next edge (the call crosses into the next form)
-    and inside; with a forced miss (pll_inject: counted as resumed; pll_pipe_miss k: interval k
+    and inside, and 20 steps below 2^18 (a launch of fewer than two intervals: every step exactly);
+    with a forced miss (pll_inject: counted as resumed; pll_pipe_miss k: interval k
     redone, k past the last: the last) the interval is redone exactly.  Bit-exact against the
     oracle, state included."""
     knobs(monkeypatch, fmrx, pll_cnt=cnt)
@@ -1640,7 +1644,7 @@ def test_pll_demoted_small_shapes(fmrx, orc, monkeypatch, trig0, ni, inject):
         20 (nbt = 1 with an exact tail), 252 / 260, 508 / 516 (one / two / three sub-segments'
         edges with a tail), 528 (a last sub-segment of one batch), 772, 1028 and 1300 (four and six
         sub-segments: the ring of four side slots wraps);
-      * a runner leaves only while a whole interval is still ahead (dem_i < ni, pll_pred.hip), so m
+      * a runner leaves only while a whole interval is still ahead (dem_i < ni, pll_runner.h), so m
         below an interval (4, 12; 16 and 20 too in the 64-step form) runs undemoted: nbt = 0 cannot
         be reached through the library;
       * launch_pll gives a 64-step form's tail of >= 48 steps to a 16-step launch of its own, so

@@ -1,4 +1,4 @@
-// tools/ubench_chain.hip — what does the three-wave PLL runner's chain step cost (pll_pred.hip
+// tools/ubench_chain.hip — what does the three-wave PLL runner's chain step cost (pll_pipe.hip
 // pll_pipe_kernel)?  One workgroup; wave 0 runs batches of 16 chain steps (two sign masks, two
 // bitfield inserts, (Ki e, Kp e), three float updates) with the candidate data
 //   mode 0: in registers (the same every batch),

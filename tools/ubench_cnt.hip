@@ -2,7 +2,7 @@
 // piece (round 4's verdict: "report the chain's measured dependent latency beside the instruction
 // count").  One workgroup; wave 0 runs batches of 16 chain steps with the step data in registers
 // (the same every batch), the other waves idle at one barrier a batch or busy with f64 FMAs.
-//   mode 0: pll_idx_kernel's step (pll_pred.hip): e = v_readlane(row, s) with s from the previous
+//   mode 0: pll_idx_kernel's step (pll_idx.hip): e = v_readlane(row, s) with s from the previous
 //           step's v_readfirstlane, (Ki e, Kp e), the three float updates, trigArg =
 //           float(P + (double)phase) (cvt, add_f64, cvt), its lane index (sub, readfirstlane);
 //   mode 1: mode 0 without the f64 trigArg: the index from the float phase's bits (sub only);
@@ -118,7 +118,7 @@ constexpr int NB = 16;
                    [f3] "v"(F[q + 3])                                                                     \
                  : "s40", "s41", "s42", "s44", "s45", "v254", "v255", "exec")
 
-// pll_pred.hip's chain blocks (FMRX_CHAIN_STEP3 / STEP5), verbatim
+// pll_pipe.hip's chain blocks (FMRX_CHAIN_STEP3 / STEP5), verbatim
 #define PT_TAIL(P, Q)                                            \
     "v_pk_mul_f32 v[254:255], v[252:253], %[kk] op_sel_hi:[0,1]\n" \
     "v_add_f32 %[ig], %[ig], v254\n"                             \

@@ -1,6 +1,6 @@
 // tools/ubench_noise.hip — what slows the serial PLL chain when other work shares its CU (the
 // stage kernels beside the runners in configs[4]).  One workgroup: wave 0 runs the stick form's
-// chain (the four-step asm block of pll_pred.hip, its e from LDS in 16-byte bursts, as
+// chain (the four-step asm block of pll_pipe.hip, its e from LDS in 16-byte bursts, as
 // tools/ubench_stick.hip mode 1) for a fixed number of 16-step batches; waves 1 .. K run one kind
 // of noise until the chain is done:
 //   kind 0: none (the K waves exit at once),

@@ -1,4 +1,4 @@
-// tools/ubench_stick.hip — where the stick form's chain (pll_pred.hip pll_pipe_kernel<..., STK>)
+// tools/ubench_stick.hip — where the stick form's chain (pll_pipe.hip pll_pipe_kernel<..., STK>)
 // gets its three e a step from, and what that costs the one wave that runs the chain.  Wave 0
 // runs batches of 16 steps of the three-candidate four-step asm block (chain4_3, the two
 // thresholds constant) with the 48 floats of a batch's e from:
