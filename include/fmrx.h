@@ -429,6 +429,72 @@ int fmrx_meter_detect(const fmrx_meter_report* report, const fmrx_meter_config* 
 int fmrx_set_meter(fmrx_ctx* ctx, int on);
 int fmrx_meter_get(const fmrx_ctx* ctx, int stream, fmrx_meter_report* out);
 
+/* ---- soft stereo: every stereo stream blended toward mono by its pilot's signal-to-noise ratio ------ */
+/* No counterpart in the reference.  The L-R channel carries about 20 dB more noise than L+R, so a receiver
+ * blends a weak station toward mono instead of switching (csrc/blend.hip).  The stage is
+ * defined exactly -- float32 throughout, products and sums rounded separately, no FMA -- so the GPU is
+ * checked without a tolerance.  A call is a whole number of RDS granules (fmrx_rds_granule: 24, 24, 3, 1
+ * blocks in modes 0..3); a granule holds Gm = 1, 1, 20, 20 meter frames and A = 3072, 3072, 56448, 56448
+ * audio frames.
+ * Thresholds (fmrx_blend_design: host only, no context, in double until stored):
+ *   T[j] = (float)(0.5 * 10^((lo_db + j (hi_db - lo_db) / 15) / 10)),  j = 0..15
+ * (the 0.5 folds the mean of the two guard bins into the threshold).  Both bounds finite, in [-20, 60],
+ * lo_db < hi_db, else FMRX_EINVAL and nothing written; defaults 10 and 22 dB.
+ * Levels, per stream and meter frame f counted from the last fmrx_reset, from the meter's power[f][tone]:
+ *   a_f = power[f][19 kHz],  g_f = fl(power[f][17 kHz] + power[f][21 kHz]),  both 0 for f < 0
+ *   S_f = fl(fl(fl(a_{f-3} + a_{f-2}) + a_{f-1}) + a_f),  G_f the same over g
+ *   l_f = #{ j : S_f >= fl(T[j] G_f) }  in 0..16 (a NaN compares false),  l_{-1} = 0
+ * so a stream starts mono and ramps up.  Carry, 8 floats a stream: a_{f-3}, a_{f-2}, a_{f-1}, g_{f-3}, g_{f-2},
+ * g_{f-1} of the next frame f, the last level as a float (anything outside 0..16 counts as 0), 0.  Zeros
+ * are the power-on state; any split of a stream into calls gives the same levels.
+ * Apply, for audio frame n of a stream counted from the reset, all in integers:
+ *   r = n / A,  a = n mod A,  u = a Gm,  f = r Gm + u / A,  t = u mod A,  q = l_{f-1} (A - t) + l_f t
+ *   k = fl((float)(16 A - q) c),  c = (float)(1.0 / (32.0 A))
+ * With (R, L) the floats in front of the quantiser: where q == 16 A the pair passes bit for bit; elsewhere
+ * d = fl(L - R), e = fl(k d), L' = fl(L - e), R' = fl(R + e): k = 0 is full stereo, k = 0.5 mono.  The result
+ * goes to de-emphasis if that is on, otherwise to fmrx_quantize's quantiser; the PCM stays interleaved R, L.
+ * (The sign and payload of a NaN that the arithmetic itself makes, Inf - Inf, are IEEE 754's to leave open and
+ * stay open here; the quantiser sends every NaN to 0.)                                                  */
+typedef struct { float lo_db, hi_db; } fmrx_blend_config;
+typedef struct { uint64_t frames; uint64_t level_frames[17]; } fmrx_blend_report;   /* frames at each level */
+int fmrx_blend_config_default(fmrx_blend_config* cfg);
+int fmrx_blend_design(const fmrx_blend_config* cfg /* NULL: defaults */, float* T16);
+/* The levels primitive, any F >= 1.  power: n_streams x F x 7 (fmrx_meter's); carry: n_streams x 8 floats,
+ * in and out; levels: n_streams x (F + 1) bytes, entry 0 the carried-in level, entry 1 + f frame f's.      */
+int fmrx_blend_levels(fmrx_ctx* ctx, const fmrx_blend_config* cfg, const float* power, size_t F, float* carry,
+                      uint8_t* levels);
+int fmrx_blend_levels_device(fmrx_ctx* ctx, const fmrx_blend_config* cfg, const float* d_power, size_t F,
+                             float* d_carry, uint8_t* d_levels);   /* async on the context stream */
+/* The apply primitive (STEREO contexts; async on the context stream).  d_rl: n_streams rows of n (R, L)
+ * float pairs, n a whole number of granules' audio frames, the first being frame 0 of a granule, 16-byte
+ * aligned; d_levels: n_streams rows of n Gm / A + 1 bytes as fmrx_blend_levels writes them (values 0..16);
+ * d_out: the blended floats (may be NULL, may be d_rl); d_pcm: their S16 (may be NULL).                   */
+int fmrx_blend_apply_device(fmrx_ctx* ctx, const float* d_rl, size_t n, const uint8_t* d_levels, float* d_out,
+                            int16_t* d_pcm);
+/* on != 0 (STEREO contexts; FMRX_EINVAL on a MONO one): the calls whose front end writes demod rows (tuned
+ * fmrx_process / _device / _device_ex, fmrx_process_shared / _device, fmrx_process_wide / _device) run the
+ * meter kernel over those rows (one launch, shared with fmrx_set_meter, whose reports are what they were),
+ * the levels kernel behind it, route the (right, left) floats in front of the quantiser into the scratch
+ * de-emphasis uses and run the apply kernel on them; the level bytes are copied back once the call's work
+ * is enqueued (a host synchronisation, as with fmrx_set_meter) and counted in the stream's report.  Such a
+ * call must be whole granules (FMRX_EINVAL and nothing runs otherwise).  While it is on, the calls without
+ * demod rows -- untuned fmrx_process / _device / _device_ex and fmrx_audio_block -- return FMRX_ESTATE,
+ * launch nothing and leave their output untouched (fmrx_tune(ctx, zeros, pos) gives the untuned bits
+ * through the tuned front end), and so do fmrx_get_state, fmrx_set_state and fmrx_seek (the blob does not
+ * hold the carry).  cfg NULL: the defaults; a bad cfg: FMRX_EINVAL, nothing changed.  fmrx_reset clears the
+ * carry and the reports and keeps the switch and the config; fmrx_set_stereo_blend, with any value, clears
+ * the carry and the reports and changes nothing else.  Off (the default): no call launches, allocates or
+ * copies anything more, every output bit is what it was.                                                 */
+int fmrx_set_stereo_blend(fmrx_ctx* ctx, int on, const fmrx_blend_config* cfg /* NULL: defaults */);
+int fmrx_stereo_blend(const fmrx_ctx* ctx, int* on, fmrx_blend_config* cfg);
+/* The end of a stream that is no whole granule (the CLI's last blocks).  on != 0, with soft stereo on (else
+ * FMRX_ESTATE): the blended calls take any block count and run the apply kernel at every stream's last
+ * level throughout (l_{f-1} = l_f = the level of the last frame counted, 0 after a reset); the meter and
+ * the levels kernel do not run for the stage, the carry and the reports stay as they are.  fmrx_reset and
+ * fmrx_set_stereo_blend turn it off.                                                                     */
+int fmrx_blend_hold(fmrx_ctx* ctx, int on);
+int fmrx_blend_get(const fmrx_ctx* ctx, int stream, fmrx_blend_report* out);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

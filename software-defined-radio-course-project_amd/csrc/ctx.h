@@ -1,6 +1,6 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, blend_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -257,6 +257,26 @@ struct Ctx {
         DevBuf<float> x;                      // a call's floats in front of the quantiser (4 B a sample and channel)
         DevBuf<float> tmp;                    // fmrx_deemph: the caller's next state, before it is copied back
     } deemph;
+    // soft stereo (fmrx_set_stereo_blend, blend.hip): configuration and a carry of its own, not in the blob;
+    // nothing here is allocated until the switch is first turned on (or a blend primitive first runs)
+    struct Blend {
+        bool on = false;                      // fmrx_set_stereo_blend
+        fmrx_blend_config cfg{10.0f, 22.0f};
+        unsigned A = 0, Gm = 0;               // audio frames and meter frames a granule (set at creation)
+        float c = 0.0f;                       // (float)(1.0 / (32.0 A))
+        DevBuf<float> thr;                    // the 16 thresholds of cfg
+        PingPong<float> carry;                // n_streams x kBlendCarry
+        DevBuf<uint8_t> levels;               // a call's level rows: n_streams x (frames + 1)
+        std::vector<uint8_t> host;            // their host copy (frames a stream)
+        size_t pending = 0;                   // frames a stream of a call enqueued and not yet counted
+        std::vector<fmrx_blend_report> rep;   // n_streams
+        bool hold = false;                    // fmrx_blend_hold: calls run at the streams' last levels
+        std::vector<uint8_t> last;            // n_streams: the level of the last frame counted (0 after a reset)
+        std::vector<uint8_t> hold_rows;       // a held call's level rows on the host
+        DevBuf<float> prim_thr, prim_carry;   // the primitives': a caller's thresholds, the next carry before it is copied back
+        fmrx_blend_config prim_cfg{0.0f, 0.0f};  // the config prim_thr holds (lo == hi: none yet)
+        DevBuf<float> prim_pow;               // fmrx_blend_levels: the caller's powers
+    } blend;
     // off-centre tuning (fmrx_tune): configuration, not part of the state blob; the tables are allocated
     // by the first fmrx_tune or by a format other than u8
     struct Tuner {
@@ -453,6 +473,20 @@ void reset_meter(fmrx_ctx* c);                               // the reports back
 // meter_finish waits for the stream and adds them to the streams' reports
 int meter_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
 int meter_finish(fmrx_ctx* c);
+
+// ---- blend_api.cpp
+void init_blend(fmrx_ctx* c);                                // the mode's A, Gm and c; nothing allocated
+int check_blend_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole granules: the RDS granule's blocks
+int reset_blend(fmrx_ctx* c);                                // the carry (once it exists) and the reports back to the start
+// the levels kernel over the powers the meter kernel left in meter.pow for this call, enqueued, the carry moved;
+// blend_apply: the call's (right, left) rows through the apply kernel (out and pcm as BlendApplyLaunch's);
+// blend_finish copies the level bytes back, waits for the stream and counts them in the streams' reports
+int blend_enqueue(fmrx_ctx* c, size_t n_blocks);
+inline bool blend_metered(const fmrx_ctx* c) { return c->blend.on && !c->blend.hold; }  // the call's levels come from the meter
+int blend_apply(fmrx_ctx* c, float* rows, size_t na, bool in_place, int16_t* d_pcm);
+int blend_finish(fmrx_ctx* c);
+// "<who>: not with soft stereo on" as FMRX_ESTATE while the switch is on, else 0
+int refuse_blend(const fmrx_ctx* c, const char* who, const char* why);
 
 // ---- front.cpp
 int init_front(fmrx_ctx* c);   // the halo; the tuner's and the wide stage's per-stream offsets

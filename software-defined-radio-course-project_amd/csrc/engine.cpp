@@ -243,13 +243,15 @@ int reset_deemph(fmrx_ctx* c) {
     return 0;
 }
 
-// deemph_rows: where an audio stage's float outlet writes a call of na frames a stream while de-emphasis
-// is on (null while it is off) -- the caller's d_mono when a mono call gave one, else the context's
-// scratch, grown to the call.  run_deemph: those rows through deemph.hip into d_pcm on the context
-// stream, the carry moved.
-static int deemph_rows(fmrx_ctx* c, size_t na, float* d_mono, float** rows) {
+// The floats in front of the quantiser, one route for the stages that work on them: soft stereo
+// (blend.hip, stereo contexts) and then de-emphasis (deemph.hip).  quant_rows: where an audio stage's float
+// outlet writes a call of na frames a stream while either is on (null while both are off) -- the caller's
+// d_mono when a mono call gave one, else the context's scratch, grown to the call.  run_quant_rows: those
+// rows through the stages that are on into d_pcm on the context stream, the carries moved: the apply
+// kernel in place on the scratch when de-emphasis follows, writing the PCM itself otherwise.
+static int quant_rows(fmrx_ctx* c, size_t na, float* d_mono, float** rows) {
     *rows = nullptr;
-    if (!c->deemph.tau) return 0;
+    if (!c->deemph.tau && !c->blend.on) return 0;
     if (c->cfg.channels == FMRX_MONO && d_mono) {
         *rows = d_mono;
         return 0;
@@ -276,6 +278,14 @@ static int run_deemph(fmrx_ctx* c, const float* rows, size_t na, int16_t* d_pcm)
     return 0;
 }
 
+static int run_quant_rows(fmrx_ctx* c, float* rows, size_t na, int16_t* d_pcm) {
+    if (c->blend.on) {
+        const int rc = blend_apply(c, rows, na, c->deemph.tau != 0, d_pcm);
+        if (rc || !c->deemph.tau) return rc;
+    }
+    return run_deemph(c, rows, na, d_pcm);
+}
+
 // RF front end (+ the mono audio stage when `pcm` is non-null and the mode allows it).
 // Chunk form (the stereo pipeline, run_stereo_pipelined): blocks [b0, b0 + n_blocks) of a call of
 // call_blocks blocks a stream starting at d_iq, on stream `st`; the halo of a chunk past the first
@@ -296,7 +306,7 @@ int run_fused(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm,
     L.mono = d_mono;
     // de-emphasis on: the kernel's float outlet feeds deemph.hip, which then writes the call's PCM
     float* dx = nullptr;
-    int rc = with_audio ? deemph_rows(c, n_blocks * c->geo.audio_frames, d_mono, &dx) : 0;
+    int rc = with_audio ? quant_rows(c, n_blocks * c->geo.audio_frames, d_mono, &dx) : 0;
     if (rc) return rc;
     if (dx) L.mono = dx;
     L.demod = d_demod ? d_demod + b0 * c->geo.if_samples : nullptr;
@@ -331,7 +341,7 @@ int run_fused(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, int16_t* d_pcm,
     if (rc != 0) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "fused kernel launch failed (%d)", rc);
     if ((rc = timing_end(ev, st))) return rc;
     if (with_audio) c->mono.stale = false;  // demod_tail rewrote the audio history
-    if (dx && (rc = run_deemph(c, dx, n_blocks * c->geo.audio_frames, d_pcm))) return rc;
+    if (dx && (rc = run_quant_rows(c, dx, n_blocks * c->geo.audio_frames, d_pcm))) return rc;
     if (!last) return 0;
     if (!L.halo_next) {  // the whole call's tail (every chunk's bytes are in d_iq)
         rc = launch_halo_update(d_iq, call_blocks * bb, c->front.halo.cur(), c->front.halo.next(),
@@ -362,7 +372,7 @@ int run_mono_audio(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_
     P.down = c->geo.audio_down;
     P.n_out = (int)na;
     float* dx = nullptr;  // de-emphasis on: the float outlet feeds deemph.hip, which then writes d_pcm
-    int rc = deemph_rows(c, na, d_mono, &dx);
+    int rc = quant_rows(c, na, d_mono, &dx);
     if (rc) return rc;
     P.out = dx ? dx : d_mono;
     P.out_stride = na;
@@ -373,7 +383,7 @@ int run_mono_audio(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_
         rc = launch_copy_streams(c->mono.hist.p, c->mono.hist_len, d_demod + (n_if - (at - 1)), demod_stride,
                                  at - 1, ns, c->stream);
     if (rc) return fail(FMRX_EHIP, "mono audio stage launch failed");
-    return dx ? run_deemph(c, dx, na, d_pcm) : 0;
+    return dx ? run_quant_rows(c, dx, na, d_pcm) : 0;
 }
 
 // Stereo engine on c->stereo.demod (history in front, n_if new samples per stream).
@@ -400,10 +410,10 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
         return fail(FMRX_EHIP, "PLL launch failed");
     }
     c->stereo.trig.advance(n_if);
-    // de-emphasis on: the audio kernels' (right, left) outlet feeds deemph.hip, which then writes d_pcm
+    // soft stereo or de-emphasis on: the audio kernels' (right, left) outlet feeds run_quant_rows, which then writes d_pcm
     const size_t na = n_blocks * c->geo.audio_frames;
     float* dx = nullptr;
-    if ((rc = deemph_rows(c, na, nullptr, &dx))) return rc;
+    if ((rc = quant_rows(c, na, nullptr, &dx))) return rc;
     const AudioLaunch A = audio_launch(c, n_blocks, d_pcm, d_mono, dx);
     const int t_au = c->diag.timer.begin(c->stream);
     if (small) {
@@ -411,7 +421,7 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
                                       pilot.phase_adjust, c->stereo.pll.p, kDemodHist, c->stream))
             return fail(FMRX_EHIP, "stereo audio launch failed");
         c->diag.timer.end(t_au, kStAudio, 0.0, c->stream);
-        return dx ? run_deemph(c, dx, na, d_pcm) : 0;
+        return dx ? run_quant_rows(c, dx, na, d_pcm) : 0;
     }
     if (launch_stereo_audio(A, ns, c->stream)) return fail(FMRX_EHIP, "stereo audio launch failed");
     c->diag.timer.end(t_au, kStAudio, 0.0, c->stream);
@@ -420,7 +430,7 @@ int run_stereo_audio(fmrx_ctx* c, size_t n_blocks, int16_t* d_pcm, float* d_mono
     if (launch_copy_streams(c->stereo.demod.p, c->stereo.demod_stride, c->stereo.demod.p + n_if, c->stereo.demod_stride, kDemodHist, ns,
                             c->stream))
         return fail(FMRX_EHIP, "demod history copy failed");
-    return dx ? run_deemph(c, dx, na, d_pcm) : 0;
+    return dx ? run_quant_rows(c, dx, na, d_pcm) : 0;
 }
 
 namespace {
@@ -536,7 +546,7 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
     // whole call on the context stream once it has waited for the audio stream
     const size_t na = n_blocks * c->geo.audio_frames;
     float* dx = nullptr;
-    if ((rc = deemph_rows(c, na, nullptr, &dx))) return rc;
+    if ((rc = quant_rows(c, na, nullptr, &dx))) return rc;
     const AudioLaunch A = audio_launch(c, n_blocks, d_pcm, d_mono, dx);
     // the PLL of chunk 0 in two launches when its streams start below 2^18: the lane runner's
     // segments and the index runner's [2^17, 2^18) form first (issue-bound: a front-end wave
@@ -632,7 +642,7 @@ int run_stereo_pipelined_body(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks,
         return fail(FMRX_EHIP, "demod history copy failed");
     HIPCHK(hipEventRecord(ev_end, c->stereo.s_audio));
     HIPCHK(hipStreamWaitEvent(c->stream, ev_end, 0));
-    return dx ? run_deemph(c, dx, na, d_pcm) : 0;
+    return dx ? run_quant_rows(c, dx, na, d_pcm) : 0;
 }
 }  // namespace
 

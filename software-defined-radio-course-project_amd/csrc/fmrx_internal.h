@@ -354,6 +354,34 @@ struct MeterLaunch {
 };
 int launch_meter(const MeterLaunch& L, int n_streams, hipStream_t s);
 
+// ---- soft stereo (blend.hip) -------------------------------------------------
+constexpr int kBlendSteps = 16;      // thresholds; a level is 0 .. 16
+constexpr int kBlendCarry = 8;       // floats a stream: a of the last three frames, g of them, the last level, 0
+constexpr int kBlendPer = 4;         // consecutive (right, left) frames a lane of the apply kernel
+// the 16 thresholds of fmrx_blend_design (host only, in double until stored); false, nothing written:
+// a bound that is not finite, outside [-20, 60], or lo_db >= hi_db
+bool blend_design(float lo_db, float hi_db, float* T16);
+struct BlendLevelsLaunch {
+    const float* power;     // n_streams x frames x kMeterTones (the meter's)
+    int frames;             // frames a stream, >= 1
+    const float* thr;       // kBlendSteps thresholds
+    const float* carry_in;  // n_streams x kBlendCarry
+    float* carry_out;       // n_streams x kBlendCarry (never carry_in)
+    uint8_t* levels;        // n_streams x (frames + 1): entry 0 the carried-in level, entry 1 + f frame f's
+};
+int launch_blend_levels(const BlendLevelsLaunch& L, int n_streams, hipStream_t s);
+struct BlendApplyLaunch {
+    const float2* in;       // n_streams rows of n (right, left) frames, 16-byte aligned, n even
+    unsigned n;             // frames a row; the first is frame 0 of a granule
+    unsigned A, Gm;         // audio frames and meter frames a granule
+    float c;                // (float)(1.0 / (32.0 A))
+    const uint8_t* levels;  // n_streams rows of level_stride bytes: entry f the level in front of meter frame f
+    size_t level_stride;    //   (at least the row's meter frames + 1)
+    float2* out;            // optional floats (may be `in`)
+    int16_t* pcm;           // optional S16 pairs, row s at pcm + 2 n s
+};
+int launch_blend_apply(const BlendApplyLaunch& L, int n_streams, hipStream_t s);
+
 // ---- spectrum tooling and the arctan demodulator ------------------
 constexpr int kPsdMaxBins = 8192;  // N complex doubles in LDS per segment
 int launch_demod_arctan(float* out, double* prev, const float* i, const float* q, int n, hipStream_t s);

@@ -89,20 +89,26 @@ int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n
                         demod_stride, demod_hist, pre_tail);
 }
 
-// The taps on the demod rows, the meter (fmrx_set_meter) and the RDS decode (fmrx_set_rds), in that
-// order everywhere; a further tap is one line in each of the three.  check_taps: the call is whole
-// granules of every tap that is on (the RDS decode's refusal first).
+// The taps on the demod rows, the meter (fmrx_set_meter), soft stereo's levels (fmrx_set_stereo_blend) and
+// the RDS decode (fmrx_set_rds), in that order everywhere; a further tap is one line in each of the three.
+// check_taps: the call is whole granules of every tap that is on (the RDS decode's refusal first).  The
+// levels read the meter's powers: one meter launch serves both, and only fmrx_set_meter has them copied
+// back and added to its reports.
 static int check_taps(const fmrx_ctx* c, size_t n_blocks) {
-    const int rc = c->rdsb.on ? check_rds_blocks(c, n_blocks) : 0;
-    return rc || !c->meter.on ? rc : check_meter_blocks(c, n_blocks);
+    int rc = c->rdsb.on ? check_rds_blocks(c, n_blocks) : 0;
+    if (!rc && c->meter.on) rc = check_meter_blocks(c, n_blocks);
+    return rc || !blend_metered(c) ? rc : check_blend_blocks(c, n_blocks);
 }
 static int taps_enqueue(fmrx_ctx* c, size_t n_blocks) {
     const float* rows = c->stereo.demod.p + kDemodHist;
-    const int rc = c->meter.on ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
+    int rc = c->meter.on || blend_metered(c) ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
+    if (!rc && c->blend.on) rc = blend_enqueue(c, n_blocks);
     return rc || !c->rdsb.on ? rc : rds_decode_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
 }
 static int taps_finish(fmrx_ctx* c) {
-    const int rc = c->meter.on ? meter_finish(c) : 0;
+    int rc = c->meter.on ? meter_finish(c) : 0;
+    if (!c->meter.on) c->meter.pending = 0;  // powers soft stereo alone asked for: nothing to report
+    if (!rc && c->blend.on) rc = blend_finish(c);
     return rc || !c->rdsb.on ? rc : rds_decode_finish(c);
 }
 

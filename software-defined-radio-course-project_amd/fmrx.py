@@ -180,6 +180,21 @@ class Subcarriers(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+BLEND_STEPS = 16  # thresholds of soft stereo; a level is 0 .. 16
+BLEND_CARRY = 8   # floats of carry a stream (include/fmrx.h: a and g of the last three frames, the level, 0)
+BLEND_PER = 4     # csrc/fmrx_internal.h kBlendPer: consecutive (right, left) frames a lane of the apply kernel
+
+
+class BlendConfig(C.Structure):
+    """fmrx_blend_config: the pilot signal-to-noise ratios (dB) of level 1 and of level 16."""
+    _fields_ = [("lo_db", C.c_float), ("hi_db", C.c_float)]
+
+
+class BlendReport(C.Structure):
+    """fmrx_blend_report: a stream's meter frames, and how many of them sat at each level 0 .. 16."""
+    _fields_ = [("frames", C.c_uint64), ("level_frames", C.c_uint64 * (BLEND_STEPS + 1))]
+
+
 _vp, _sz, _fp, _i16p, _u8p =C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every function declared in include/fmrx.h
@@ -267,6 +282,15 @@ PROTOTYPES = {
     "fmrx_meter_detect": (C.c_int, [C.POINTER(MeterReport), C.POINTER(MeterConfig), C.POINTER(Subcarriers)]),
     "fmrx_set_meter": (C.c_int, [_vp, C.c_int]),
     "fmrx_meter_get": (C.c_int, [_vp, C.c_int, C.POINTER(MeterReport)]),
+    "fmrx_blend_config_default": (C.c_int, [C.POINTER(BlendConfig)]),
+    "fmrx_blend_design": (C.c_int, [C.POINTER(BlendConfig), _vp]),
+    "fmrx_blend_levels": (C.c_int, [_vp, C.POINTER(BlendConfig), _vp, _sz, _vp, _vp]),
+    "fmrx_blend_levels_device": (C.c_int, [_vp, C.POINTER(BlendConfig), _vp, _sz, _vp, _vp]),
+    "fmrx_blend_apply_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmrx_set_stereo_blend": (C.c_int, [_vp, C.c_int, C.POINTER(BlendConfig)]),
+    "fmrx_stereo_blend": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(BlendConfig)]),
+    "fmrx_blend_hold": (C.c_int, [_vp, C.c_int]),
+    "fmrx_blend_get": (C.c_int, [_vp, C.c_int, C.POINTER(BlendReport)]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -450,6 +474,25 @@ def meter_detect(report: MeterReport, pilot_min_snr_db: float | None = None, rds
     return out.as_dict()
 
 
+def blend_config(lo_db: float | None = None, hi_db: float | None = None) -> BlendConfig:
+    """fmrx_blend_config_default (10 and 22 dB) with the bounds given replaced."""
+    cfg = BlendConfig()
+    _check(lib().fmrx_blend_config_default(C.byref(cfg)))
+    if lo_db is not None:
+        cfg.lo_db = lo_db
+    if hi_db is not None:
+        cfg.hi_db = hi_db
+    return cfg
+
+
+def blend_design(lo_db: float | None = None, hi_db: float | None = None) -> np.ndarray:
+    """fmrx_blend_design: the 16 float32 thresholds of soft stereo (a bound left None keeps its default).
+    Host only."""
+    T = np.zeros(BLEND_STEPS, np.float32)
+    _check(lib().fmrx_blend_design(C.byref(blend_config(lo_db, hi_db)), _np_ptr(T)))
+    return T
+
+
 def iq_pair_bytes(fmt: int) -> int:
     """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
     n = lib().fmrx_iq_pair_bytes(fmt)
@@ -568,7 +611,7 @@ PROBE_FRAMES = 16  # frames (64 ms each) decode_stations(probe=True) meters befo
 
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
                     capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, probe: bool = False,
-                    rds_sync: bool = False, **cfg):
+                    rds_sync: bool = False, blend: bool = False, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
@@ -584,9 +627,15 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     (None in infos otherwise).  The result gains a trailing list, levels: meter_detect's dict a station
     (None where the capture holds no whole frame: everything is then decoded as without probe).
     rds_sync=True (with rds=True; a ValueError without): the block sync runs behind the bits (set_rds_sync) and
-    is flushed at the end, and infos holds RdsExt.as_dict()'s extended dict a station instead."""
+    is flushed at the end, and infos holds RdsExt.as_dict()'s extended dict a station instead.
+    blend=True (with channels=STEREO; a ValueError without): soft stereo (set_stereo_blend, the default
+    thresholds) blends every station decoded in stereo toward mono by its pilot; the capture is trimmed to whole
+    RDS granules and the result gains a last list, blends: Receiver.blend_report's dict a station (None for a
+    station that probe=True routed to mono, which stays mono)."""
     if rds_sync and not rds:
         raise ValueError("rds_sync needs rds")
+    if blend and channels != STEREO:
+        raise ValueError("blend needs channels=STEREO")
     if capture_rate is not None and capture_decim != 1:
         raise ValueError("capture_rate and capture_decim exclude each other")
     fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
@@ -603,14 +652,14 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
             rx.set_capture_decim(capture_decim)
 
     def run(sel, ch, want_rds, meter=False):
-        """The stations sel in one context of ch channels: (pcm rows, infos or None, levels or None)."""
+        """The stations sel in one context of ch channels: (pcm rows, infos or None, levels or None, blends or None)."""
         data = iq
         with Receiver(mode, ch, rf_taps=rf_taps, n_streams=len(sel)) as rx:
             configure(rx)
             getattr(rx, tune)([stations[k].offset_hz for k in sel])
             if deemphasis_us and not meter:
                 rx.set_deemphasis(deemphasis_us)
-            if rds or meter:
+            if rds or meter or blend:
                 blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
                 per = rx.rds_granule // blocks * pairs * 2  # elements of the capture an RDS granule (whole frames) takes
                 n = data.size // per
@@ -618,13 +667,16 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
                     frames = rx.rds_granule * rx.geo.if_samples // (METER_WINDOWS * (rx.geo.bp_fs // 1000))
                     n = min(n, max(1, PROBE_FRAMES // frames))
                     if n == 0:
-                        return None, None, None
+                        return None, None, None, None
                 data = data[: n * per]
             if want_rds:
                 rx.set_rds(True)
                 rx.set_rds_sync(rds_sync)
             if meter:
                 rx.set_meter(True)
+            blended = blend and ch == STEREO and not meter
+            if blended:
+                rx.set_stereo_blend(True)
             pcm = getattr(rx, process)(data).reshape(len(sel), -1)
             if want_rds and rds_sync:
                 rx.rds_blocks_flush()
@@ -632,38 +684,40 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
             else:
                 infos = [rx.rds_info(k).as_dict() for k in range(len(sel))] if want_rds else None
             levels = [meter_detect(rx.meter_report(k)) for k in range(len(sel))] if meter else None
-        return pcm, infos, levels
+            blends = [rx.blend_report(k) for k in range(len(sel))] if blended else None
+        return pcm, infos, levels, blends
 
     with Receiver(mode, channels, rf_taps=rf_taps) as rx:
         configure(rx)
         stations = getattr(rx, scan)(iq, **cfg)
-    tail = ([],) if probe else ()
+    tail = (([],) if probe else ()) + (([],) if blend else ())
     if not stations:
         return (([], np.zeros((0, 0), np.int16), []) if rds else ([], np.zeros((0, 0), np.int16))) + tail
     everyone = list(range(len(stations)))
     if not probe:
-        pcm, infos, _ = run(everyone, channels, rds)
-        return (stations, pcm, infos) if rds else (stations, pcm)
+        pcm, infos, _, blends = run(everyone, channels, rds)
+        return ((stations, pcm, infos) if rds else (stations, pcm)) + ((blends,) if blend else ())
     levels = run(everyone, MONO, False, meter=True)[2]
     groups: dict = {}
     for k in everyone:
         key = (channels == STEREO, rds) if levels is None else (bool(levels[k]["stereo"]) and channels == STEREO,
                                                                 bool(levels[k]["rds"]) and rds)
         groups.setdefault(key, []).append(k)
-    rows, infos = [None] * len(stations), [None] * len(stations)
+    rows, infos, blends = [None] * len(stations), [None] * len(stations), [None] * len(stations)
     # the groups' contexts side by side, a thread each (a context has a stream of its own and the library's
     # calls release the GIL), so that their serial PLL chains overlap as they do inside one context
     with ThreadPoolExecutor(max_workers=len(groups)) as pool:
         done = list(pool.map(lambda kv: run(kv[1], STEREO if kv[0][0] else MONO, kv[0][1]), groups.items()))
-    for ((stereo, with_rds), sel), (pcm, inf, _) in zip(groups.items(), done):
+    for ((stereo, with_rds), sel), (pcm, inf, _, bl) in zip(groups.items(), done):
         if channels == STEREO and not stereo:
             pcm = np.repeat(pcm, 2, axis=1)  # mono into R and L
         for i, k in enumerate(sel):
             rows[k] = pcm[i]
             infos[k] = inf[i] if with_rds else None
+            blends[k] = bl[i] if bl else None
     pcm = np.stack(rows)
     levels = [None] * len(stations) if levels is None else levels
-    return (stations, pcm, infos, levels) if rds else (stations, pcm, levels)
+    return ((stations, pcm, infos, levels) if rds else (stations, pcm, levels)) + ((blends,) if blend else ())
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:
@@ -936,6 +990,55 @@ class Receiver:
         rep = MeterReport()
         _check(lib().fmrx_meter_get(self.h, int(stream), C.byref(rep)))
         return rep
+
+    # ---- soft stereo
+    def set_stereo_blend(self, on: bool, lo_db: float | None = None, hi_db: float | None = None) -> None:
+        """fmrx_set_stereo_blend: blend every stream toward mono by its pilot's signal-to-noise ratio in the
+        tuned, shared and wide calls (STEREO contexts); a bound left None keeps its default (10 / 22 dB)."""
+        _check(lib().fmrx_set_stereo_blend(self.h, int(bool(on)), C.byref(blend_config(lo_db, hi_db))))
+
+    def blend_hold(self, on: bool) -> None:
+        """fmrx_blend_hold: blended calls of any block count at every stream's last level (a stream's end)."""
+        _check(lib().fmrx_blend_hold(self.h, int(bool(on))))
+
+    def stereo_blend(self) -> tuple[bool, float, float]:
+        """(on, lo_db, hi_db) as fmrx_stereo_blend reports them."""
+        on, cfg = C.c_int(), BlendConfig()
+        _check(lib().fmrx_stereo_blend(self.h, C.byref(on), C.byref(cfg)))
+        return bool(on.value), cfg.lo_db, cfg.hi_db
+
+    def blend_levels(self, power: np.ndarray, carry: np.ndarray | None = None, lo_db: float | None = None,
+                     hi_db: float | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """fmrx_blend_levels: power (n_streams, F, 7) as the meter gives it and the carry (n_streams, 8; None:
+        zeros, the power-on state) -> (levels uint8 (n_streams, F + 1), entry 0 the carried-in level; the next carry)."""
+        p = np.ascontiguousarray(power, np.float32)
+        if p.ndim != 3 or p.shape[0] != self.n_streams or p.shape[1] < 1 or p.shape[2] != METER_TONES:
+            raise FmrxError(FMRX_EINVAL, f"power of shape {p.shape}: expected ({self.n_streams}, F >= 1, {METER_TONES})")
+        c = np.zeros((self.n_streams, BLEND_CARRY), np.float32) if carry is None else np.array(carry, np.float32, order="C")
+        if c.shape != (self.n_streams, BLEND_CARRY):
+            raise FmrxError(FMRX_EINVAL, f"carry of shape {c.shape}: expected ({self.n_streams}, {BLEND_CARRY})")
+        lv = np.zeros((self.n_streams, p.shape[1] + 1), np.uint8)
+        _check(lib().fmrx_blend_levels(self.h, C.byref(blend_config(lo_db, hi_db)), _np_ptr(p), p.shape[1], _np_ptr(c), _np_ptr(lv)))
+        return lv, c
+
+    def blend_levels_device(self, d_power: int, frames: int, d_carry: int, d_levels: int, lo_db: float | None = None,
+                            hi_db: float | None = None) -> None:
+        _check(lib().fmrx_blend_levels_device(self.h, C.byref(blend_config(lo_db, hi_db)), d_power, frames, d_carry, d_levels))
+
+    def blend_apply(self, d_rl: int, n: int, d_levels: int, d_out: int | None = None, d_pcm: int | None = None) -> None:
+        """fmrx_blend_apply_device: n (R, L) float pairs a stream (whole granules) blended by the level rows;
+        d_out (may be d_rl) takes the floats, d_pcm their S16.  Async on the context stream."""
+        _check(lib().fmrx_blend_apply_device(self.h, d_rl, n, d_levels, d_out, d_pcm))
+
+    def blend_report(self, stream: int = 0) -> dict:
+        """fmrx_blend_get as a dict: frames, level_frames (17 counts) and mean = sum(l n_l) / (16 frames),
+        1.0 for full stereo throughout, 0.0 for mono (and with no frames yet)."""
+        out = BlendReport()
+        _check(lib().fmrx_blend_get(self.h, int(stream), C.byref(out)))
+        counts = [int(v) for v in out.level_frames]
+        frames = int(out.frames)
+        mean = sum(l * n for l, n in enumerate(counts)) / (16.0 * frames) if frames else 0.0
+        return {"frames": frames, "level_frames": counts, "mean": mean}
 
     def estimate_psd(self, samples: np.ndarray, freq_bins: int, fs: float):
         """estimatePSD (fourier.cpp:35-117) on the GPU: (freq, psd_db)."""
