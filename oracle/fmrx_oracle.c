@@ -184,6 +184,11 @@ int16_t orc_quant(float x) {
     return (int16_t)(uint16_t)((uint32_t)t & 0xFFFFu);
 }
 
+int orc_quant_n(int16_t* out, const float* x, int n) {
+    for (int i = 0; i < n; i++) out[i] = orc_quant(x[i]);
+    return n;
+}
+
 /* Sequential src/project.cpp (rf_thread :48-84 then audio_thread :132-196 per block; all
  * full blocks, no EOF race) plus the private-history mono product.  With demod_in set, the
  * rf_thread half is skipped and block b's demod is demod_in + b * if_samples. */

@@ -49,6 +49,7 @@ int orc_pll(float* io, int n, float freq, float fs, float ncoScale, float phaseA
 int orc_mixer(float* out, const float* a, const float* b, int n);
 int orc_lr(float* left, float* right, const float* mono, const float* stereo, int n);
 int16_t orc_quant(float x);
+int orc_quant_n(int16_t* out, const float* x, int n); /* orc_quant over n samples */
 long orc_run(int mode, int rf_taps, const uint8_t* iq, size_t nbytes, orc_outputs* o);
 long orc_run_audio(int mode, const float* demod, size_t n_blocks, orc_outputs* o);
 int orc_fm_demod_arctan(double* out, double* prev_phase, const double* i_in, const double* q_in, int n);

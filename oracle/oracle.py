@@ -188,6 +188,39 @@ class _Lib:
             raise ValueError("need at least one segment")
         return freq, psd
 
+    def _elementwise(self, name):
+        """The library's mixer, lr or quant_n entry point."""
+        return getattr(self.lib, self.prefix + name)
+
+    def mixer(self, a, b):
+        """mixer (filter.cpp:176-184): 2 (a b) in float."""
+        a = np.ascontiguousarray(a, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        out = np.zeros(a.size, np.float32)
+        f = self._elementwise("mixer")
+        f.argtypes = [_fp, _fp, _fp, C.c_int]
+        f(_ptr(out, _fp), _ptr(a, _fp), _ptr(b, _fp), a.size)
+        return out
+
+    def lr(self, mono, stereo):
+        """LRExtraction (filter.cpp:186-199): (left, right) = ((m + s) 0.5, (m - s) 0.5)."""
+        m = np.ascontiguousarray(mono, np.float32)
+        st = np.ascontiguousarray(stereo, np.float32)
+        left, right = np.zeros(m.size, np.float32), np.zeros(m.size, np.float32)
+        f = self._elementwise("lr")
+        f.argtypes = [_fp, _fp, _fp, _fp, C.c_int]
+        f(_ptr(left, _fp), _ptr(right, _fp), _ptr(m, _fp), _ptr(st, _fp), m.size)
+        return left, right
+
+    def quant(self, x):
+        """The S16 quantiser (project.cpp:185-191) over an array of floats."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        out = np.zeros(x.size, np.int16)
+        f = self._elementwise("quant_n")
+        f.argtypes = [_i16p, _fp, C.c_int]
+        f(_ptr(out, _i16p), _ptr(x, _fp), x.size)
+        return out
+
     def normalize(self, b):
         b = _as_u8(b)
         out = np.zeros(b.size, np.float32)
@@ -218,32 +251,6 @@ class Oracle(_Lib):
         f(out.ctypes.data_as(_dp), C.byref(pv), i.ctypes.data_as(_dp), q.ctypes.data_as(_dp), i.size)
         return out, pv.value
 
-    def mixer(self, a, b):
-        """mixer (filter.cpp:176-184): 2 (a b) in float."""
-        a = np.ascontiguousarray(a, np.float32)
-        b = np.ascontiguousarray(b, np.float32)
-        out = np.zeros(a.size, np.float32)
-        f = self.lib.orc_mixer
-        f.argtypes = [_fp, _fp, _fp, C.c_int]
-        f(_ptr(out, _fp), _ptr(a, _fp), _ptr(b, _fp), a.size)
-        return out
-
-    def lr(self, mono, stereo):
-        """LRExtraction (filter.cpp:186-199): (left, right) = ((m + s) 0.5, (m - s) 0.5)."""
-        m = np.ascontiguousarray(mono, np.float32)
-        st = np.ascontiguousarray(stereo, np.float32)
-        left, right = np.zeros(m.size, np.float32), np.zeros(m.size, np.float32)
-        f = self.lib.orc_lr
-        f.argtypes = [_fp, _fp, _fp, _fp, C.c_int]
-        f(_ptr(left, _fp), _ptr(right, _fp), _ptr(m, _fp), _ptr(st, _fp), m.size)
-        return left, right
-
-    def quant(self, x):
-        f = self.lib.orc_quant
-        f.restype = C.c_int16
-        f.argtypes = [C.c_float]
-        return np.array([f(float(v)) for v in np.asarray(x, np.float32)], np.int16)
-
 
 class Reference(_Lib):
     """The reference's own filter.cpp / iofunc.cpp behind a sequential project.cpp driver."""
@@ -253,6 +260,22 @@ class Reference(_Lib):
 
     def run(self, mode, rf_taps, iq, fields=None):
         return self._run(self.lib.ref_run, mode, rf_taps, iq, fields)
+
+    @property
+    def own_elementwise(self) -> bool:
+        """Whether this build of libfmref.so wraps the reference's mixer, LRExtraction and quantiser (ref_mixer,
+        ref_lr, ref_quant_n of ref_driver.cpp); one built from an earlier driver does not."""
+        return all(hasattr(self.lib, "ref_" + n) for n in ("mixer", "lr", "quant_n"))
+
+    def _elementwise(self, name):
+        """The three element-wise stages from the reference build where it wraps them; a libfmref.so made from an
+        earlier ref_driver.cpp (it is kept out of git and may outlive a checkout) has only the FIR, design and PLL
+        entry points, and then these three come from the C restatement, which tests/test_oracle.py pins."""
+        if self.own_elementwise:
+            return getattr(self.lib, "ref_" + name)
+        if not hasattr(self, "_orc"):
+            self._orc = C.CDLL(ORACLE_SO)
+        return getattr(self._orc, "orc_" + name)
 
     def run_mono(self, mode, rf_taps, iq):
         """Sequential mono-only receive path (the CPU baseline)."""

@@ -161,6 +161,29 @@ int ref_pll(float* io, int n, float freq, float fs, float ncoScale, float phaseA
     return n;
 }
 
+// mixer (filter.cpp:176-184)
+int ref_mixer(float* out, const float* a, const float* b, int n) {
+    std::vector<float> o, va(a, a + n), vb(b, b + n);
+    mixer(o, va, vb);
+    std::memcpy(out, o.data(), o.size() * sizeof(float));
+    return (int)o.size();
+}
+
+// LRExtraction (filter.cpp:186-199)
+int ref_lr(float* left, float* right, const float* mono, const float* stereo, int n) {
+    std::vector<float> l, r, m(mono, mono + n), s(stereo, stereo + n);
+    LRExtraction(l, r, m, s);
+    std::memcpy(left, l.data(), l.size() * sizeof(float));
+    std::memcpy(right, r.data(), r.size() * sizeof(float));
+    return (int)l.size();
+}
+
+// the quantiser of project.cpp:185-191 over n samples
+int ref_quant_n(int16_t* out, const float* x, int n) {
+    for (int i = 0; i < n; i++) out[i] = quant(x[i]);
+    return n;
+}
+
 // readStdinBlockData (iofunc.cpp:62-69) on a memory buffer.
 int ref_normalize(const uint8_t* bytes, int n, float* out) {
     CinRedirect r(bytes, (size_t)n);

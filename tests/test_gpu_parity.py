@@ -132,16 +132,22 @@ def test_stereo_call_split_and_resume(fmrx, orc, mode, nb):
     iq = np.stack(iqs)
     with fmrx.Receiver(mode, fmrx.STEREO, n_streams=ns) as rx:
         ps = rx.geo.pcm_samples
-        parts, pos = [], 0
-        for n in (1, 3, 2, nb - 6):
-            parts.append(rx.process(iq[:, pos * bb:(pos + n) * bb]))
+        parts, pos, resumed = [], 0, []
+        calls = (1, 3, 2, nb - 6) if nb > 6 else (1, 3, nb - 4)  # whole, non-empty calls that sum to nb
+        assert all(n >= 1 for n in calls) and sum(calls) == nb
+        for n in calls:
+            got = rx.process(iq[:, pos * bb:(pos + n) * bb])
+            assert got.shape == (ns, n * ps)
+            parts.append(got)
             pos += n
             if pos in (1, 4):  # checkpoint / resume through a second context
                 blob = rx.get_state()
                 with fmrx.Receiver(mode, fmrx.STEREO, n_streams=ns) as rx2:
                     rx2.set_state(blob)
                     tail = rx2.process(iq[:, pos * bb:])
-                assert np.array_equal(tail, want[:, pos * ps:]), (mode, pos)
+                assert tail.shape[1] > 0 and np.array_equal(tail, want[:, pos * ps:]), (mode, pos)
+                resumed.append(pos)
+        assert resumed == [1, 4] and pos == nb
         assert np.array_equal(np.concatenate(parts, axis=1), want)
 
 
