@@ -495,6 +495,78 @@ int fmrx_stereo_blend(const fmrx_ctx* ctx, int* on, fmrx_blend_config* cfg);
 int fmrx_blend_hold(fmrx_ctx* ctx, int on);
 int fmrx_blend_get(const fmrx_ctx* ctx, int stream, fmrx_blend_report* out);
 
+/* ---- AFC: measure each stream's carrier offset and retune to it -------------------------------------- */
+/* No counterpart in the reference, which decodes a station at the capture's centre.  A scan reports offsets
+ * on a raster and a real capture is never on it (crystal error, the capture's centre), so the demod row of a
+ * tuned stream carries the tuning error as its mean (csrc/afc.hip).  The sums are stateless
+ * and defined exactly, so the GPU is checked without a tolerance.  Per stream and frame of the demod row
+ * d[n] (the meter's frame: 64 windows of P = bp_fs / 1000 samples, 64 ms), two floats: S, the sum of d[n],
+ * and Q, the sum of fl(d[n] d[n]).  Per window, x = d[window start + n]: sixteen partial sums each,
+ *   a_j = fl(a_j + x[16 i + j]),  b_j = fl(b_j + fl(x[16 i + j] x[16 i + j]))   from 0, i ascending over 0 .. P/16 - 1
+ * (products and sums rounded separately, no FMA), folded by stride halving, a_j = fl(a_j + a_{j+s}) for
+ * j < s, s = 8, 4, 2, 1; the frame's 64 window values a_0 (b_0) are folded by the same tree (s = 32 .. 1).
+ * sums: n_streams x F x 2 floats (S, Q), F the frames of the call.  NaN and Inf in the input follow IEEE
+ * arithmetic, stay in their frame and never fault.  A call takes whole frames, fmrx_meter's granule rule:
+ * else FMRX_EINVAL, nothing launched, nothing written.  The device form's rows are 16-byte aligned
+ * (FMRX_EINVAL otherwise).                                                                                */
+int fmrx_carrier(fmrx_ctx* ctx, const float* demod, size_t n_blocks, float* sums);
+int fmrx_carrier_device(fmrx_ctx* ctx, const float* d_demod, size_t n_blocks,
+                        float* d_sums);            /* async on the context stream */
+/* sum, sumsq: the sequential ascending sums, over the frames in stream order, of S and of Q widened to
+ * double (any split of a stream into calls gives the same bits).                                           */
+typedef struct { double sum, sumsq; uint64_t frames; } fmrx_carrier_report;
+int fmrx_carrier_accumulate(fmrx_carrier_report* io, const float* sums,
+                            size_t frames);        /* host only: frames x 2 floats of one stream */
+/* The decision, host only, no context, everything in double.  With n = 64 P frames samples (P = bp_fs /
+ * 1000), mean = sum / n and mean_square = sumsq / n:
+ *   err_hz = asin(clamp(mean, -1, 1)) bp_fs / (2 pi)         (positive: the carrier is above the tuned offset)
+ *   carrier = mean_square <= cfg.max_mean_square
+ *   correction_hz = step_hz round_half_away(err_hz / step_hz) if carrier and |err_hz| >= deadband_hz, else 0
+ * The discriminator returns the sine of the phase step, so err_hz is exact for an unmodulated carrier;
+ * modulation shrinks the reading by E[cos m] (J0(beta) for a tone: 0.98 for a quiet multiplex, 0.22 at 75 kHz
+ * tone deviation, positive below about 92 kHz), so repeated decisions close in on the carrier and do not
+ * overshoot.  A constant-envelope signal has |d| <= 1, noise alone has heavy tails (mean squares of 3.5 to
+ * 8.5 on synthetic captures): the gate's default of 1.0 is that bound, not a tuned value.
+ * Defaults: step_hz 1000 (the grid on which fmrx_tuner_design accepts every offset in every mode),
+ * deadband_hz 1000, max_pull_hz 50000 (half the scan's default raster), frames 16 (about a second), track 1,
+ * max_mean_square 1.0.  They rest on synthetic stations; no off-air capture has been through them.
+ * FMRX_EINVAL, nothing written: a null argument, step_hz, frames or max_pull_hz <= 0, deadband_hz < 0,
+ * max_mean_square not finite or <= 0, bp_fs no positive multiple of 16000, a report of 0 frames.  cfg NULL:
+ * the defaults.                                                                                            */
+typedef struct { int step_hz, deadband_hz, max_pull_hz, frames, track; float max_mean_square; } fmrx_afc_config;
+typedef struct { double err_hz, mean, mean_square; int carrier; int32_t correction_hz; } fmrx_afc_decision;
+int fmrx_afc_config_default(fmrx_afc_config* cfg);
+int fmrx_afc_decide(const fmrx_carrier_report* report, int bp_fs, const fmrx_afc_config* cfg,
+                    fmrx_afc_decision* out);
+/* on != 0: the calls whose front end writes demod rows (tuned fmrx_process / _device / _device_ex,
+ * fmrx_process_shared / _device, fmrx_process_wide / _device) also run the carrier sums over those rows, on
+ * the context stream behind the meter, the blend levels and RDS, copy the F x 2 floats a stream back and add
+ * them to two reports a stream once the call's work is enqueued (a host synchronisation, as with
+ * fmrx_set_meter): the stream's total and the window since its last decision.  Such a call must be whole
+ * frames (FMRX_EINVAL and nothing runs otherwise).  The PCM of the call is the same bits either way.
+ * With cfg.track != 0, when the call's work is finished every stream whose window holds at least cfg.frames
+ * frames gets fmrx_afc_decide's decision over the whole window, and the window is cleared.  Its new offset
+ * is the current one plus the correction, clamped to origin +- max_pull_hz, origin being the offset the
+ * caller last gave fmrx_tune or fmrx_tune_wide for the stream (on a context with a capture stage, once
+ * fmrx_tune_wide was accepted, the offsets are the ones against the capture's rate).  If any stream moved,
+ * the context retunes all streams at its current position, as fmrx_tune (fmrx_tune_wide) with
+ * fmrx_tuner_info's (fmrx_wide_info's) position would; the next call starts on the new tables.  A new
+ * offset the design refuses leaves that stream where it was and is counted in `refused`.  Retunes happen
+ * at call boundaries only, so WITH TRACKING THE PCM DEPENDS ON HOW A STREAM IS SPLIT INTO CALLS; with
+ * track == 0 (measure only) nothing depends on the split.  A caller's own fmrx_tune / fmrx_tune_wide sets
+ * new origins and clears the windows; fmrx_reset puts the offsets back to the origins, clears the reports,
+ * the decisions and the counts and keeps the switch and the config; none of it is in the fmrx_get_state
+ * blob, as with tuning.  fmrx_set_afc with on != 0 clears the reports, the decisions and the counts (on == 0
+ * leaves them readable); either leaves the offsets and the origins where they are.  cfg NULL: the defaults; a bad
+ * cfg: FMRX_EINVAL, nothing changed.  Off (the default): no call launches, allocates or copies anything more,
+ * every output bit is what it was.  The untuned fused u8 path and fmrx_audio_block write no demod rows and
+ * are never measured.                                                                                       */
+typedef struct { fmrx_carrier_report total; int32_t origin_hz, offset_hz; uint32_t retunes, refused;
+                 uint32_t decisions; fmrx_afc_decision last; /* zeros before the first decision */
+               } fmrx_afc_status;
+int fmrx_set_afc(fmrx_ctx* ctx, const fmrx_afc_config* cfg /* NULL: defaults */, int on);
+int fmrx_afc_get(const fmrx_ctx* ctx, int stream, fmrx_afc_status* out);
+
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */

@@ -1,6 +1,6 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
 // [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]
-// [--capture-rate HZ] [--rds] [--deemph 50|75] [--meter] [--blend]`:
+// [--capture-rate HZ] [--rds] [--deemph 50|75] [--meter] [--blend] [--afc]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -52,6 +52,12 @@
 //     (fmrx_blend_hold); at end of input one line goes to stderr, `blend mean=%.2f full=%llu mono=%llu
 //     frames=%llu` (the mean level over 16, the frames at level 16 and at level 0, all frames).  With
 //     <channels> 1 or --mono-product: message, exit 1.
+//   * --afc (an fmrx extension) measures the station's carrier against --offset-hz and retunes to it between
+//     batches (fmrx_set_afc, the default configuration, tracking on): batches of whole frames and the tuned
+//     front end as with --meter; blocks past the last whole frame are decoded where the tuner then stands,
+//     unmeasured; at end of input one line goes to stderr, `afc offset=%+d err=%+.0f carrier=%d retunes=%u
+//     frames=%llu` (where the stream ended, its last decision's error and gate, the retunes, all frames).
+//     The PCM depends on the batch size, as every retune happens between two batches.
 //
 // Streaming runtime.  The reference splits the work into a producer thread
 // (read + RF front end, project.cpp:48-84) and a consumer thread (audio back end, :132-196)
@@ -123,6 +129,7 @@ void usage(const char* argv0) {
                  "options (fmrx): [--batch N] [--device D] [--rf-taps T] [--mono-product] [--offset-hz F]\n"
                  "                [--deemph 50|75]  de-emphasise the audio (time constant in us; default: none)\n"
                  "                [--meter]  measure the pilot and the RDS subcarrier; at end of input print their levels to stderr\n"
+                 "                [--afc]  measure the carrier's offset and retune to it between batches; print where it ended to stderr\n"
                  "                [--blend]  with <channels> 2: blend toward mono by the pilot's signal-to-noise ratio; print the levels' summary to stderr\n"
                  "                [--rds-sync]  with --rds: per-block sync with burst correction; print the extended line too\n"
                  "                [--rds]  decode the station's RDS too; at end of input print its PI, PTY and name to stderr\n"
@@ -181,7 +188,7 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
 
 int main(int argc, char** argv) {
     int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false, tuned = false, scan = false, rds = false, rds_sync = false, meter = false, blend = false;
+    bool mono_product = false, tuned = false, scan = false, rds = false, rds_sync = false, meter = false, blend = false, afc = false;
     long offset_hz = 0;
     int iq_format = FMRX_IQ_U8, capture_decim = 1, deemph_us = 0;
     long capture_rate = 0;
@@ -199,6 +206,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--rds-sync")) rds_sync = true;
         else if (!std::strcmp(argv[i], "--meter")) meter = true;
         else if (!std::strcmp(argv[i], "--blend")) blend = true;
+        else if (!std::strcmp(argv[i], "--afc")) afc = true;
         else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
         else if (!std::strcmp(argv[i], "--iq-format") && i + 1 < argc) {
             const char* f = argv[++i];
@@ -325,17 +333,18 @@ int main(int argc, char** argv) {
     }
     // --rds, --meter: whole RDS granules (the meter's frames) a batch (rounded up), decoded by the tuned front end
     size_t rds_unit = unit_blocks;
-    if (rds || meter || blend) {
+    if (rds || meter || blend || afc) {
         if (fmrx_rds_granule(ctx, &rds_unit) != FMRX_OK || (rds && fmrx_set_rds(ctx, 1) != FMRX_OK) ||
             (rds_sync && fmrx_set_rds_sync(ctx, 1) != FMRX_OK) ||
-            (meter && fmrx_set_meter(ctx, 1) != FMRX_OK) || (blend && fmrx_set_stereo_blend(ctx, 1, nullptr) != FMRX_OK)) {
-            std::fprintf(stderr, "fmrx: %s: %s\n", rds ? "--rds" : meter ? "--meter" : "--blend", fmrx_last_error());
+            (meter && fmrx_set_meter(ctx, 1) != FMRX_OK) || (blend && fmrx_set_stereo_blend(ctx, 1, nullptr) != FMRX_OK) ||
+            (afc && fmrx_set_afc(ctx, nullptr, 1) != FMRX_OK)) {
+            std::fprintf(stderr, "fmrx: %s: %s\n", rds ? "--rds" : meter ? "--meter" : blend ? "--blend" : "--afc", fmrx_last_error());
             fmrx_destroy(ctx);
             return 1;
         }
         batch = (int)(((size_t)batch + rds_unit - 1) / rds_unit * rds_unit);
     }
-    if (tuned || wide || rds || meter || blend) {  // out of range (or no 32-bit value) -> message, exit 1
+    if (tuned || wide || rds || meter || blend || afc) {  // out of range (or no 32-bit value) -> message, exit 1
         const int32_t f = (int32_t)offset_hz;
         if ((long)f != offset_hz || (wide ? fmrx_tune_wide : fmrx_tune)(ctx, &f, 0) != FMRX_OK) {
             std::fprintf(stderr, "fmrx: --offset-hz %ld: %s\n", offset_hz,
@@ -408,6 +417,7 @@ int main(int argc, char** argv) {
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
             if ((head > 0 && process(ctx, s.d_in, head, s.d_out) != FMRX_OK) ||
                 (head < s.blocks && (fmrx_set_rds(ctx, 0) != FMRX_OK || fmrx_set_meter(ctx, 0) != FMRX_OK ||
+                                     (afc && fmrx_set_afc(ctx, nullptr, 0) != FMRX_OK) ||
                                      (blend && fmrx_blend_hold(ctx, 1) != FMRX_OK) ||
                                      process(ctx, s.d_in + head / unit_blocks * block_bytes, s.blocks - head,
                                              s.d_out + head * geo.pcm_samples) != FMRX_OK))) {
@@ -465,6 +475,12 @@ int main(int argc, char** argv) {
         if (fmrx_meter_get(ctx, 0, &rep) == FMRX_OK && (rep.frames == 0 || fmrx_meter_detect(&rep, nullptr, &sc) == FMRX_OK))
             std::fprintf(stderr, "meter pilot_snr=%.1f stereo=%d rds_snr=%.1f rds=%d frames=%llu\n", (double)sc.pilot_snr_db,
                          sc.stereo, (double)sc.rds_snr_db, sc.rds, (unsigned long long)rep.frames);
+    }
+    if (afc) {
+        fmrx_afc_status st;
+        if (fmrx_afc_get(ctx, 0, &st) == FMRX_OK)
+            std::fprintf(stderr, "afc offset=%+d err=%+.0f carrier=%d retunes=%u frames=%llu\n", (int)st.offset_hz, st.last.err_hz,
+                         st.last.carrier, st.retunes, (unsigned long long)st.total.frames);
     }
     if (blend) {
         fmrx_blend_report rep;

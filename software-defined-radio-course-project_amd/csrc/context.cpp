@@ -61,6 +61,7 @@ int reset_state(fmrx_ctx* c) {
         (rc = reset_rds_bits(c)) || (rc = reset_deemph(c)) || (rc = reset_blend(c)))
         return rc;
     reset_meter(c);
+    if ((rc = reset_afc(c))) return rc;  // behind reset_front: a pulled stream goes back to its origin at position 0
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }

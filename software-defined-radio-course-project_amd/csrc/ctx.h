@@ -1,6 +1,6 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, blend_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, blend_api.cpp, afc_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -248,6 +248,23 @@ struct Ctx {
         size_t pending = 0;                   // frames a stream of a call enqueued and not yet added
         std::vector<fmrx_meter_report> rep;   // n_streams
     } meter;
+    // AFC (fmrx_set_afc, afc.hip): the carrier sums of the demod rows, the decisions and the retunes; no
+    // signal state, not in the blob; nothing on the device is allocated until the switch is first turned on
+    // (or fmrx_carrier first runs).  The offsets it moves are tune.offsets, or wide.offsets once
+    // fmrx_tune_wide was accepted (`wide` says which the origins are)
+    struct Afc {
+        bool on = false;                      // fmrx_set_afc
+        fmrx_afc_config cfg{1000, 1000, 50000, 16, 1, 1.0f};
+        DevBuf<float> sums;                   // a call's sums: n_streams x frames x 2
+        std::vector<float> host;              // their host copy
+        size_t pending = 0;                   // frames a stream of a call enqueued and not yet added
+        std::vector<fmrx_carrier_report> total, window;  // n_streams: since the reset, since the last decision
+        std::vector<int32_t> origin;          // n_streams: what the caller last tuned to
+        bool wide = false;                    // the origins are fmrx_tune_wide's
+        bool moved = false;                   // some offset is not its origin
+        std::vector<uint32_t> retunes, refused, decisions;  // n_streams
+        std::vector<fmrx_afc_decision> last;  // n_streams
+    } afc;
     // FM de-emphasis (fmrx_set_deemphasis, deemph.hip): configuration and a carry of its own, not in the
     // blob; nothing here is allocated until it is first turned on (or fmrx_deemph first runs)
     struct Deemph {
@@ -474,6 +491,15 @@ void reset_meter(fmrx_ctx* c);                               // the reports back
 int meter_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
 int meter_finish(fmrx_ctx* c);
 
+// ---- afc_api.cpp
+void reset_afc_reports(fmrx_ctx* c);                         // reports, decisions and counts back to zero (sized here)
+int reset_afc(fmrx_ctx* c);                                  // that, and the offsets back to the origins
+void afc_caller_tuned(fmrx_ctx* c);                          // fmrx_tune / fmrx_tune_wide accepted: new origins, windows cleared
+// the carrier sums over the rows at d_demod (whole frames), enqueued; afc_finish copies them back, waits for
+// the stream, adds them to the reports and, with tracking on, decides and retunes
+int afc_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
+int afc_finish(fmrx_ctx* c);
+
 // ---- blend_api.cpp
 void init_blend(fmrx_ctx* c);                                // the mode's A, Gm and c; nothing allocated
 int check_blend_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole granules: the RDS granule's blocks
@@ -501,5 +527,8 @@ int check_capture_decim(int decim, bool or_one);
 int check_wide_rf_fs(int rf_fs);
 // n_blocks of a wide call: whole granules (FMRX_EINVAL otherwise)
 int check_wide_blocks(const fmrx_ctx* c, size_t n_blocks);
+// what fmrx_tune (offsets non-null) and fmrx_tune_wide do once their arguments are checked; AFC's retunes run them too
+int tune_narrow(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair);
+int tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair);
 
 }  // namespace fmrx

@@ -354,6 +354,16 @@ struct MeterLaunch {
 };
 int launch_meter(const MeterLaunch& L, int n_streams, hipStream_t s);
 
+// ---- carrier sums (afc.hip) --------------------------------------------------
+struct CarrierLaunch {
+    const float* demod;     // n_streams rows (stride demod_stride) of frames x 64 P samples, 16-byte aligned
+    size_t demod_stride;    // a multiple of 4 floats
+    int P;                  // 240, 256 or 288
+    int frames;             // frames a stream
+    float* sums;            // n_streams x frames x 2: S, Q (8-byte aligned)
+};
+int launch_carrier(const CarrierLaunch& L, int n_streams, hipStream_t s);
+
 // ---- soft stereo (blend.hip) -------------------------------------------------
 constexpr int kBlendSteps = 16;      // thresholds; a level is 0 .. 16
 constexpr int kBlendCarry = 8;       // floats a stream: a of the last three frames, g of them, the last level, 0

@@ -89,27 +89,31 @@ int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n
                         demod_stride, demod_hist, pre_tail);
 }
 
-// The taps on the demod rows, the meter (fmrx_set_meter), soft stereo's levels (fmrx_set_stereo_blend) and
-// the RDS decode (fmrx_set_rds), in that order everywhere; a further tap is one line in each of the three.
+// The taps on the demod rows, the meter (fmrx_set_meter), soft stereo's levels (fmrx_set_stereo_blend),
+// the RDS decode (fmrx_set_rds) and the carrier sums (fmrx_set_afc), in that order everywhere; a further tap
+// is one line in each of the three.
 // check_taps: the call is whole granules of every tap that is on (the RDS decode's refusal first).  The
 // levels read the meter's powers: one meter launch serves both, and only fmrx_set_meter has them copied
-// back and added to its reports.
+// back and added to its reports.  The carrier sums' finish comes last: with tracking it may retune.
 static int check_taps(const fmrx_ctx* c, size_t n_blocks) {
     int rc = c->rdsb.on ? check_rds_blocks(c, n_blocks) : 0;
     if (!rc && c->meter.on) rc = check_meter_blocks(c, n_blocks);
+    if (!rc && c->afc.on) rc = check_meter_blocks(c, n_blocks);
     return rc || !blend_metered(c) ? rc : check_blend_blocks(c, n_blocks);
 }
 static int taps_enqueue(fmrx_ctx* c, size_t n_blocks) {
     const float* rows = c->stereo.demod.p + kDemodHist;
     int rc = c->meter.on || blend_metered(c) ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
     if (!rc && c->blend.on) rc = blend_enqueue(c, n_blocks);
-    return rc || !c->rdsb.on ? rc : rds_decode_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
+    if (!rc && c->rdsb.on) rc = rds_decode_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
+    return rc || !c->afc.on ? rc : afc_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
 }
 static int taps_finish(fmrx_ctx* c) {
     int rc = c->meter.on ? meter_finish(c) : 0;
     if (!c->meter.on) c->meter.pending = 0;  // powers soft stereo alone asked for: nothing to report
     if (!rc && c->blend.on) rc = blend_finish(c);
-    return rc || !c->rdsb.on ? rc : rds_decode_finish(c);
+    if (!rc && c->rdsb.on) rc = rds_decode_finish(c);
+    return rc || !c->afc.on ? rc : afc_finish(c);
 }
 
 // The audio stage of a call whose front end filled the context's demod rows (mono: the polyphase
@@ -327,6 +331,49 @@ int set_capture_stage(fmrx_ctx* c, int up, int down, size_t blocks) {
 
 }  // namespace
 
+namespace fmrx {
+
+// The streams' rotators for offsets_hz in place of the current ones, the position set, tuning on
+int tune_narrow(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    const int rc = tuner_upload(c, offsets_hz);
+    if (rc) return rc;
+    c->tune.offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
+    c->tune.pos = first_pair;
+    c->tune.on = true;
+    c->wide.tuned = false;  // the tables are no longer the fine offsets of fmrx_tune_wide
+    return FMRX_OK;
+}
+
+// The same on a context with a capture stage: every offset split into its coarse and fine part (first_pair
+// a multiple of the ratio's down, in wide pairs)
+int tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
+    const CaptureRatio& r = c->wide.ratio;
+    const size_t ns = c->cfg.n_streams;
+    std::vector<int32_t> fine(ns);
+    std::vector<WideStream> ws(ns);
+    std::vector<float> tab(2 * (size_t)kRateMaxN * ns, 0.0f);
+    int rc;
+    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
+        int fr = 0, n = 0, k = 0;
+        if ((rc = fmrx_rate_design(c->geo.rf_fs, r.cap_fs(c->geo.rf_fs), offsets_hz[s], nullptr, nullptr, nullptr, &fr, &n, &k,
+                                   tab.data() + 2 * kRateMaxN * s, nullptr, nullptr)))
+            return rc;
+        fine[s] = fr;
+        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
+    }
+    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
+    HIPCHK(hipMemcpy(c->wide.tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->wide.streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
+    c->tune.offsets = fine;  // the existing tuner state: the fine parts at rf_fs
+    c->tune.pos = first_pair / (uint64_t)r.down * (uint64_t)r.up;
+    c->tune.on = true;
+    c->wide.offsets.assign(offsets_hz, offsets_hz + ns);
+    c->wide.tuned = true;
+    return FMRX_OK;
+}
+
+}  // namespace fmrx
+
 extern "C" {
 
 // ---- off-centre tuning ----------------------------------------------------------------------
@@ -350,15 +397,12 @@ int fmrx_tune(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) {
         c->tune.on = false;
         c->wide.tuned = false;
         c->tune.pos = first_pair;
+        afc_caller_tuned(c);
         return FMRX_OK;
     }
-    const int rc = tuner_upload(c, offsets_hz);
-    if (rc) return rc;
-    c->tune.offsets.assign(offsets_hz, offsets_hz + c->cfg.n_streams);
-    c->tune.pos = first_pair;
-    c->tune.on = true;
-    c->wide.tuned = false;  // the tables are no longer the fine offsets of fmrx_tune_wide
-    return FMRX_OK;
+    const int rc = tune_narrow(c, offsets_hz, first_pair);
+    if (!rc) afc_caller_tuned(c);
+    return rc;
 }
 
 // ---- raw I/Q formats ----------------------------------------------------------------------------
@@ -502,28 +546,9 @@ int fmrx_tune_wide(fmrx_ctx* c, const int32_t* offsets_hz, uint64_t first_pair) 
         return fail(FMRX_EINVAL, "fmrx_tune_wide: first_pair %llu is no multiple of the decimation %d",
                     (unsigned long long)first_pair, r.down);
     }
-    const size_t ns = c->cfg.n_streams;
-    std::vector<int32_t> fine(ns);
-    std::vector<WideStream> ws(ns);
-    std::vector<float> tab(2 * (size_t)kRateMaxN * ns, 0.0f);
-    int rc;
-    for (size_t s = 0; s < ns; s++) {  // every offset checked before anything changes
-        int fr = 0, n = 0, k = 0;
-        if ((rc = fmrx_rate_design(c->geo.rf_fs, r.cap_fs(c->geo.rf_fs), offsets_hz[s], nullptr, nullptr, nullptr, &fr, &n, &k,
-                                   tab.data() + 2 * kRateMaxN * s, nullptr, nullptr)))
-            return rc;
-        fine[s] = fr;
-        ws[s] = WideStream{(uint32_t)n, (uint32_t)k};
-    }
-    if ((rc = tuner_upload(c, fine.data()))) return rc;  // drains the stream before the tables change
-    HIPCHK(hipMemcpy(c->wide.tab.p, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->wide.streams.p, ws.data(), sizeof(WideStream) * ns, hipMemcpyHostToDevice));
-    c->tune.offsets = fine;  // the existing tuner state: the fine parts at rf_fs
-    c->tune.pos = first_pair / (uint64_t)r.down * (uint64_t)r.up;
-    c->tune.on = true;
-    c->wide.offsets.assign(offsets_hz, offsets_hz + ns);
-    c->wide.tuned = true;
-    return FMRX_OK;
+    const int rc = tune_wide(c, offsets_hz, first_pair);
+    if (!rc) afc_caller_tuned(c);
+    return rc;
 }
 
 int fmrx_wide_info(fmrx_ctx* c, int32_t* offsets_hz, uint64_t* next_pair, int* enabled) {

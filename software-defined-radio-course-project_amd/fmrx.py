@@ -195,6 +195,35 @@ class BlendReport(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("level_frames", C.c_uint64 * (BLEND_STEPS + 1))]
 
 
+class CarrierReport(C.Structure):
+    """fmrx_carrier_report: a stream's summed demod samples and squares and the frames they cover."""
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double), ("frames", C.c_uint64)]
+
+
+class AfcConfig(C.Structure):
+    """fmrx_afc_config: the decision's grid, deadband, reach, window, the tracking switch and the carrier gate."""
+    _fields_ = [("step_hz", C.c_int), ("deadband_hz", C.c_int), ("max_pull_hz", C.c_int), ("frames", C.c_int),
+                ("track", C.c_int), ("max_mean_square", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AfcDecision(C.Structure):
+    """fmrx_afc_decision: what fmrx_afc_decide says of a report."""
+    _fields_ = [("err_hz", C.c_double), ("mean", C.c_double), ("mean_square", C.c_double), ("carrier", C.c_int),
+                ("correction_hz", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AfcStatus(C.Structure):
+    """fmrx_afc_status: a stream's total report, where it was tuned and where it is, its counts and last decision."""
+    _fields_ = [("total", CarrierReport), ("origin_hz", C.c_int32), ("offset_hz", C.c_int32), ("retunes", C.c_uint32),
+                ("refused", C.c_uint32), ("decisions", C.c_uint32), ("last", AfcDecision)]
+
+
 _vp, _sz, _fp, _i16p, _u8p =C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int16), C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every function declared in include/fmrx.h
@@ -291,6 +320,13 @@ PROTOTYPES = {
     "fmrx_stereo_blend": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(BlendConfig)]),
     "fmrx_blend_hold": (C.c_int, [_vp, C.c_int]),
     "fmrx_blend_get": (C.c_int, [_vp, C.c_int, C.POINTER(BlendReport)]),
+    "fmrx_carrier": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_carrier_device": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "fmrx_carrier_accumulate": (C.c_int, [C.POINTER(CarrierReport), _vp, _sz]),
+    "fmrx_afc_config_default": (C.c_int, [C.POINTER(AfcConfig)]),
+    "fmrx_afc_decide": (C.c_int, [C.POINTER(CarrierReport), C.c_int, C.POINTER(AfcConfig), C.POINTER(AfcDecision)]),
+    "fmrx_set_afc": (C.c_int, [_vp, C.POINTER(AfcConfig), C.c_int]),
+    "fmrx_afc_get": (C.c_int, [_vp, C.c_int, C.POINTER(AfcStatus)]),
     "fmrx_synchronize": (C.c_int, [_vp]),
     "fmrx_stream": (_vp, [_vp]),
     "fmrx_kernel_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]),
@@ -474,6 +510,34 @@ def meter_detect(report: MeterReport, pilot_min_snr_db: float | None = None, rds
     return out.as_dict()
 
 
+def carrier_accumulate(sums, report: CarrierReport | None = None) -> CarrierReport:
+    """fmrx_carrier_accumulate (host only): add one stream's frames x 2 sums to report (a new one when None)."""
+    report = CarrierReport() if report is None else report
+    p = np.ascontiguousarray(sums, np.float32).reshape(-1, 2)
+    _check(lib().fmrx_carrier_accumulate(C.byref(report), _np_ptr(p), p.shape[0]))
+    return report
+
+
+def afc_config_default(**kw) -> AfcConfig:
+    """fmrx_afc_config_default, with the fields given (step_hz, deadband_hz, max_pull_hz, frames, track,
+    max_mean_square) set."""
+    cfg = AfcConfig()
+    _check(lib().fmrx_afc_config_default(C.byref(cfg)))
+    for k, v in kw.items():
+        if k not in dict(AfcConfig._fields_):
+            raise TypeError(f"no AFC setting {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def afc_decide(report: CarrierReport, bp_fs: int, **kw) -> dict:
+    """fmrx_afc_decide (host only): err_hz, mean, mean_square, carrier and correction_hz of a report as a
+    dict; the settings given replace afc_config_default's."""
+    out = AfcDecision()
+    _check(lib().fmrx_afc_decide(C.byref(report), int(bp_fs), C.byref(afc_config_default(**kw)) if kw else None, C.byref(out)))
+    return out.as_dict()
+
+
 def blend_config(lo_db: float | None = None, hi_db: float | None = None) -> BlendConfig:
     """fmrx_blend_config_default (10 and 22 dB) with the bounds given replaced."""
     cfg = BlendConfig()
@@ -607,11 +671,12 @@ def rds_parse_blocks(blocks, n_bits: int = 0, ext: RdsExt | None = None, flush: 
 
 
 PROBE_FRAMES = 16  # frames (64 ms each) decode_stations(probe=True) meters before it decides
+AFC_PASSES = 3     # passes over those frames decode_stations(afc=True) makes at most before it decodes
 
 
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
                     capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, probe: bool = False,
-                    rds_sync: bool = False, blend: bool = False, **cfg):
+                    rds_sync: bool = False, blend: bool = False, afc: bool = False, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
@@ -631,7 +696,14 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     blend=True (with channels=STEREO; a ValueError without): soft stereo (set_stereo_blend, the default
     thresholds) blends every station decoded in stereo toward mono by its pilot; the capture is trimmed to whole
     RDS granules and the result gains a last list, blends: Receiver.blend_report's dict a station (None for a
-    station that probe=True routed to mono, which stays mono)."""
+    station that probe=True routed to mono, which stays mono).
+    afc=True: after the scan, up to AFC_PASSES mono passes over the same leading frames with the measure-only
+    AFC switch (set_afc(track=0)) move every station by afc_decide's correction (the default configuration;
+    within max_pull_hz of the scan's offset, and only to offsets the tuner's design accepts) and stop early when
+    none moves; with probe=True the last of them is the probe's pass too.  The stations returned carry the
+    corrected offset_hz, everything is decoded there, and the result gains a last list after the probe's and
+    the blend's: a dict a station (err_hz, mean_square and carrier of its last measurement, pulled_hz against
+    the scan's offset), None where the capture holds no whole frame (decoded as without afc)."""
     if rds_sync and not rds:
         raise ValueError("rds_sync needs rds")
     if blend and channels != STEREO:
@@ -651,30 +723,34 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
         elif wide:
             rx.set_capture_decim(capture_decim)
 
-    def run(sel, ch, want_rds, meter=False):
-        """The stations sel in one context of ch channels: (pcm rows, infos or None, levels or None, blends or None)."""
+    def run(sel, ch, want_rds, meter=False, measure=False):
+        """The stations sel in one context of ch channels: (pcm rows, infos or None, levels or None, blends or None,
+        AFC decisions or None).  meter, measure: over the leading frames alone, with the meter, the measure-only AFC."""
+        lead = meter or measure
         data = iq
         with Receiver(mode, ch, rf_taps=rf_taps, n_streams=len(sel)) as rx:
             configure(rx)
             getattr(rx, tune)([stations[k].offset_hz for k in sel])
-            if deemphasis_us and not meter:
+            if deemphasis_us and not lead:
                 rx.set_deemphasis(deemphasis_us)
-            if rds or meter or blend:
+            if rds or lead or blend:
                 blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
                 per = rx.rds_granule // blocks * pairs * 2  # elements of the capture an RDS granule (whole frames) takes
                 n = data.size // per
-                if meter:  # the leading frames alone
+                if lead:  # the leading frames alone
                     frames = rx.rds_granule * rx.geo.if_samples // (METER_WINDOWS * (rx.geo.bp_fs // 1000))
                     n = min(n, max(1, PROBE_FRAMES // frames))
                     if n == 0:
-                        return None, None, None, None
+                        return None, None, None, None, None
                 data = data[: n * per]
             if want_rds:
                 rx.set_rds(True)
                 rx.set_rds_sync(rds_sync)
             if meter:
                 rx.set_meter(True)
-            blended = blend and ch == STEREO and not meter
+            if measure:
+                rx.set_afc(True, track=0)
+            blended = blend and ch == STEREO and not lead
             if blended:
                 rx.set_stereo_blend(True)
             pcm = getattr(rx, process)(data).reshape(len(sel), -1)
@@ -685,19 +761,48 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
                 infos = [rx.rds_info(k).as_dict() for k in range(len(sel))] if want_rds else None
             levels = [meter_detect(rx.meter_report(k)) for k in range(len(sel))] if meter else None
             blends = [rx.blend_report(k) for k in range(len(sel))] if blended else None
-        return pcm, infos, levels, blends
+            decided = [afc_decide(rx.afc_status(k).total, rx.geo.bp_fs) for k in range(len(sel))] if measure else None
+        return pcm, infos, levels, blends, decided
+
+    def accepts(hz):
+        try:
+            if wide:
+                rate_design(geo.rf_fs, cap_fs, hz)
+            else:
+                tuner_design(geo.rf_fs, hz)
+            return True
+        except FmrxError:
+            return False
 
     with Receiver(mode, channels, rf_taps=rf_taps) as rx:
         configure(rx)
         stations = getattr(rx, scan)(iq, **cfg)
-    tail = (([],) if probe else ()) + (([],) if blend else ())
+        geo, cap_fs = rx.geo, rx.capture_rate[0] if wide else None
+    tail = (([],) if probe else ()) + (([],) if blend else ()) + (([],) if afc else ())
     if not stations:
         return (([], np.zeros((0, 0), np.int16), []) if rds else ([], np.zeros((0, 0), np.int16))) + tail
     everyone = list(range(len(stations)))
+    levels, pulls = None, ()
+    if afc:
+        found, reach = [s.offset_hz for s in stations], afc_config_default().max_pull_hz
+        decided = None
+        for _ in range(AFC_PASSES):
+            levels, decided = run(everyone, MONO, False, meter=probe, measure=True)[2::2]
+            moved = False
+            for k, d in enumerate(decided or ()):
+                to = min(found[k] + reach, max(found[k] - reach, stations[k].offset_hz + d["correction_hz"]))
+                if to != stations[k].offset_hz and accepts(to):
+                    stations[k].offset_hz, moved = to, True
+            if not moved:
+                break
+        pulls = ([None if decided is None else {"err_hz": d["err_hz"], "mean_square": d["mean_square"], "carrier": d["carrier"],
+                                                "pulled_hz": stations[k].offset_hz - found[k]}
+                  for k, d in enumerate(decided or [None] * len(stations))],)
     if not probe:
-        pcm, infos, _, blends = run(everyone, channels, rds)
-        return ((stations, pcm, infos) if rds else (stations, pcm)) + ((blends,) if blend else ())
-    levels = run(everyone, MONO, False, meter=True)[2]
+        pcm, infos, _, blends, _ = run(everyone, channels, rds)
+        return ((stations, pcm, infos) if rds else (stations, pcm)) + ((blends,) if blend else ()) + pulls
+    if not afc:
+        levels = run(everyone, MONO, False, meter=True)[2]
     groups: dict = {}
     for k in everyone:
         key = (channels == STEREO, rds) if levels is None else (bool(levels[k]["stereo"]) and channels == STEREO,
@@ -708,7 +813,7 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     # calls release the GIL), so that their serial PLL chains overlap as they do inside one context
     with ThreadPoolExecutor(max_workers=len(groups)) as pool:
         done = list(pool.map(lambda kv: run(kv[1], STEREO if kv[0][0] else MONO, kv[0][1]), groups.items()))
-    for ((stereo, with_rds), sel), (pcm, inf, _, bl) in zip(groups.items(), done):
+    for ((stereo, with_rds), sel), (pcm, inf, _, bl, _) in zip(groups.items(), done):
         if channels == STEREO and not stereo:
             pcm = np.repeat(pcm, 2, axis=1)  # mono into R and L
         for i, k in enumerate(sel):
@@ -717,7 +822,7 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
             blends[k] = bl[i] if bl else None
     pcm = np.stack(rows)
     levels = [None] * len(stations) if levels is None else levels
-    return ((stations, pcm, infos, levels) if rds else (stations, pcm, levels)) + ((blends,) if blend else ())
+    return ((stations, pcm, infos, levels) if rds else (stations, pcm, levels)) + ((blends,) if blend else ()) + pulls
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:
@@ -990,6 +1095,33 @@ class Receiver:
         rep = MeterReport()
         _check(lib().fmrx_meter_get(self.h, int(stream), C.byref(rep)))
         return rep
+
+    # ---- AFC
+    def carrier(self, demod: np.ndarray) -> np.ndarray:
+        """fmrx_carrier: demod rows (whole frames: multiples of rds_granule blocks) -> the carrier sums (S, Q),
+        float32 of shape (n_streams, frames, 2), or (frames, 2) for one stream."""
+        d = np.ascontiguousarray(demod, np.float32).reshape(self.n_streams, -1)
+        nb = d.shape[1] // self.geo.if_samples
+        if nb * self.geo.if_samples != d.shape[1]:
+            raise FmrxError(FMRX_EINVAL, "carrier takes whole blocks")
+        frames = d.shape[1] // (METER_WINDOWS * (self.geo.bp_fs // 1000))
+        out = np.zeros((self.n_streams, frames, 2), np.float32)
+        _check(lib().fmrx_carrier(self.h, _np_ptr(d), nb, _np_ptr(out)))
+        return out if self.n_streams > 1 else out[0]
+
+    def carrier_device(self, d_demod: int, n_blocks: int, d_sums: int) -> None:
+        _check(lib().fmrx_carrier_device(self.h, d_demod, n_blocks, d_sums))
+
+    def set_afc(self, on: bool, **kw) -> None:
+        """fmrx_set_afc: the tuned, shared and wide process calls also sum their demod rows (whole frames) and,
+        with track (the default), retune every stream to its carrier between calls; the settings given
+        (afc_config_default's fields) replace the defaults."""
+        _check(lib().fmrx_set_afc(self.h, C.byref(afc_config_default(**kw)), int(bool(on))))
+
+    def afc_status(self, stream: int = 0) -> AfcStatus:
+        st = AfcStatus()
+        _check(lib().fmrx_afc_get(self.h, int(stream), C.byref(st)))
+        return st
 
     # ---- soft stereo (DESIGN §5.14)
     def set_stereo_blend(self, on: bool, lo_db: float | None = None, hi_db: float | None = None) -> None:
