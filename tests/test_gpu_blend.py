@@ -14,11 +14,11 @@ import numpy as np
 import pytest
 
 import blend_ref as B
-import deemph_ref as dr
 import iqgen
 import meter_ref as M
 import oracle
 from conftest import case_input, load_case
+from taps_ref import dev_of, reference, station
 from test_meter_host import _powers, _u8
 
 pytestmark = pytest.mark.gpu
@@ -182,53 +182,6 @@ def test_apply_primitive_refusals(fmrx):
 
 
 # ---- the switch --------------------------------------------------------------------------------------
-
-_cache: dict = {}
-
-
-def dev_of(mode):
-    """test_meter_host's DEV at the mode's demod rate: the broadcast's peak deviation in radians a sample."""
-    return 2.0 * np.pi * 75000.0 / oracle.MODES[mode][5]
-
-
-def station(mode, frames, sigmas, pilot=0.05, seed=7):
-    """A stereo station with RDS as u8 at amplitude 100 (read-only): frames meter frames, Gaussian noise of
-    sigmas[i] LSB over the i-th run of four frames (the last one to the end)."""
-    key = ("iq", mode, frames, tuple(sigmas), pilot, seed)
-    if key not in _cache:
-        bb, nif = oracle.MODES[mode][0], oracle.MODES[mode][1]
-        blocks = frames * M.frame_samples(mode) // nif
-        assert blocks * nif == frames * M.frame_samples(mode)
-        n, dev = blocks * bb // 2, dev_of(mode)
-        z = M.fm_signal(mode, n, pilot=pilot * dev, lr=0.2 * dev, rds=0.04 * dev, audio=0.3 * dev,
-                        bits=M.station_bits(0x1234, "TEST  FM", frames * 0.064 + 0.1))
-        per = 4 * (n // frames)
-        parts = []
-        for i, sg in enumerate(sigmas):
-            lo, hi = i * per, n if i == len(sigmas) - 1 else (i + 1) * per
-            parts.append(_u8(z[lo:hi], sg, seed + i))
-        iq = np.concatenate(parts)
-        iq.setflags(write=False)
-        _cache[key] = iq
-    return _cache[key]
-
-
-def reference(orc, fm, mode, iq, key, tau=0):
-    """(pcm, level row with entry 0, blended floats, powers) of one stream over the whole of iq from the reset."""
-    if (key, tau) not in _cache:
-        o = orc.run(mode, 51, iq, ["left", "right", "demod"])
-        pw = M.power(o["demod"], fm.meter_design(oracle.MODES[mode][5])[1])
-        row, _ = B.levels(pw, fm.blend_design())
-        y = B.apply(mode, np.stack([o["right"], o["left"]], axis=1), row)
-        if tau:
-            pcm = dr.pcm_stereo(orc, y[:, 1], y[:, 0], fm.deemph_design(48000 if mode < 2 else 44100, tau))
-        else:
-            pcm = B.quant(orc, y)
-        for a in (pcm, row, y, pw):
-            a.setflags(write=False)
-        _cache[key, tau] = (pcm, row, y, pw, orc.quant(np.stack([o["right"], o["left"]], axis=1).reshape(-1)))
-    return _cache[key, tau]
-
 
 def in_calls(fn, iq, bb, calls):
     out, b = [], 0

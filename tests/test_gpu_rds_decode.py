@@ -233,3 +233,99 @@ def test_cli_prints_the_station(fmrx, orc):
     assert line in r.stderr.decode().splitlines(), r.stderr.decode()
     assert r.stdout == plain.stdout and len(r.stdout) == (IQ_GRANULES * 24 + 5) * 128 * 2 * 2
     assert b"rds pi=" not in plain.stderr
+
+
+# ---- edge inputs: the decisions a real signal never reaches ---------------------------------------------------
+
+EDGE_GRANULES = 2  # of mode 0: two windows, so the carried sign, chip and tail see the edges too
+
+
+def edge_rows(orc, which):
+    """Three streams of constructed mixer rows of mode 0, one edge a stream.  "flat": all zeros (the phase
+    histogram ties at bin 0, p = 8; the pairing vote ties, q = 0), all -0.0, a constant negative row.  "mixed":
+    denormals of both signs; the transmitter's row with one NaN inside the second window; impulses of both
+    signs so far apart that y is exactly 0.0f between them."""
+    n = EDGE_GRANULES * R.granule_samples(0)
+    if which == "flat":
+        return np.stack([np.zeros(n, np.float32), np.full(n, -0.0, np.float32), np.full(n, -0.25, np.float32)])
+    tiny = np.float32(1e-41) * np.where((np.arange(n) // 37) % 2 == 0, 1, -1).astype(np.float32)
+    nan = mix_of(orc, 0, EDGE_GRANULES * R.GRANULES[0])[0].copy()
+    nan[R.granule_samples(0) + 5000] = np.nan
+    sparse = np.zeros(n, np.float32)
+    sparse[200::400] = np.where(np.arange(sparse[200::400].size) % 2 == 0, 1.0, -1.0).astype(np.float32)
+    return np.stack([tiny, nan, sparse])
+
+
+def same_edges(got, want, s, y=True):
+    """Stream s of a result against its reference: bits, codes and windows equal; y on the bits wherever the
+    reference is a number, and a NaN wherever it is not (NaN >= 0 is false on both sides)."""
+    same({k: got[k][s] for k in ("bits", "codes", "win")}, want)
+    if y:
+        keep = ~np.isnan(want["y"])
+        assert np.array_equal(np.isnan(got["y"][s]), ~keep), s
+        assert np.array_equal(got["y"][s][keep].view(np.uint32), want["y"][keep].view(np.uint32)), s
+
+
+@pytest.mark.parametrize("which", ["flat", "mixed"])
+def test_rds_bits_edge_rows(fmrx, orc, which):
+    rows = edge_rows(orc, which)
+    want = [R.back_half(orc, 0, r) for r in rows]
+    if which == "flat":
+        assert want[0]["win"].tolist() == want[1]["win"].tolist() == [[8, 0], [8, 0]]  # both ties, both windows
+        assert int(want[0]["bits"].sum()) == 1 and not want[0]["codes"].any() and np.all(want[2]["y"][R.WIN:] < 0)
+        assert np.all(want[1]["y"] == 0)
+    else:
+        y0, y1, y2 = (w["y"] for w in want)
+        tiny = np.finfo(np.float32).tiny
+        assert np.any((y0 > 0) & (y0 < tiny)) and np.any((y0 < 0) & (y0 > -tiny)) and np.all(np.abs(y0) < tiny)
+        bad = np.flatnonzero(np.isnan(y1))
+        assert bad.size and bad.min() >= R.WIN and np.isfinite(y1[: R.WIN]).all()  # inside the second window
+        assert np.any(y2 == 0) and np.any(y2 > 0) and np.any(y2 < 0) and np.isfinite(y2).all()
+        sign = np.sign(y2[y2 != 0])
+        assert np.any((y2[1:-1] == 0) & (y2[:-2] != 0)) and np.any(sign[1:] != sign[:-1])  # exact zeros between signed samples
+    g = R.granule_samples(0)
+    with fmrx.Receiver(0, fmrx.MONO, n_streams=3) as rx:
+        got = rx.rds_bits(rows, want_y=True)
+        for s in range(3):
+            same_edges(got, want[s], s)
+        rx.reset()  # the same rows a granule at a time: the carried bytes and the tail see the edges
+        parts = [rx.rds_bits(rows[:, k: k + g], want_y=True) for k in range(0, rows.shape[1], g)]
+        cat = {k: np.concatenate([p[k] for p in parts], axis=1) for k in ("y", "bits", "codes", "win")}
+        for s in range(3):
+            same_edges(cat, want[s], s)
+
+
+def front_edge_rows(n_blocks):
+    """test_gpu_stereo_variants' special values in the demod of mode 0 (stereo_ref.special_demod: denormals of both
+    signs, a run of -0.0, the smallest normals, +-1e30), the same with the other sign, and the same with +-1e18
+    in place of +-1e30."""
+    from stereo_ref import special_demod
+    a = special_demod(0, n_blocks)
+    c = a.copy()
+    c[np.abs(c) == np.float32(1e30)] *= np.float32(1e-12)
+    return np.stack([a, -a, c])
+
+
+def test_rds_block_edge_rows(fmrx, orc):
+    """The front half on denormals, signed zeros and huge samples.  The channel is compared over the whole row.
+    +-1e30 squares to Inf in front of the 114 kHz PLL, whose outputs are NaN from there on: NaN and Inf through
+    that PLL are test_pll_demoted_special_values' subject, so nco and rds of those two streams are compared up
+    to the first sample the reference does not give as a number (behind every other special value), and over
+    the whole row on the stream whose largest samples, +-1e18, stay finite when squared."""
+    nb = R.GRANULES[0]
+    rows = front_edge_rows(nb)
+    want = [orc.rds(0, r) for r in rows]
+    with fmrx.Receiver(0, fmrx.MONO, n_streams=3) as rx:
+        got = rx.rds_block(rows, want_nco=True, want_channel=True)
+    nif = oracle.MODES[0][1]
+    for s in range(3):
+        assert np.isfinite(want[s]["channel"]).all()
+        assert np.array_equal(got["channel"][s].view(np.uint32), want[s]["channel"].view(np.uint32)), s
+        ok = np.isfinite(want[s]["nco"]) & np.isfinite(want[s]["rds"])
+        end = ok.size if ok.all() else int(np.flatnonzero(~ok)[0])
+        if s == 2:
+            assert end == ok.size
+        else:  # every other special value lies in front of the first sample that is no number
+            assert nif + 200 + 32 + 120 + 32 + 20 <= end < ok.size, (s, end)
+        for k in ("nco", "rds"):
+            assert np.array_equal(got[k][s][:end].view(np.uint32), want[s][k][:end].view(np.uint32)), (s, k)
