@@ -77,6 +77,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -122,7 +123,8 @@ struct Slot {
     bool last = false;
 };
 
-void usage(const char* argv0) {
+// the usage text to stderr; false, as refuse() below
+bool usage(const char* argv0) {
     std::fprintf(stderr,
                  "Usage: %s\nor \nUsage %s <mode> <channels>\n"
                  "\t\t<mode> is a value from 0 to 3\n\t\t   <channels> is either 1 or 2\n"
@@ -141,6 +143,16 @@ void usage(const char* argv0) {
                  "                [--scan [--scan-bytes B]]  list the stations of the first B bytes (default 16777216)\n"
                  "                                           as `offset_hz power_db snr_db` lines; no PCM\n",
                  argv0, argv0);
+    return false;
+}
+
+// a message to stderr; false, which every step of main answers for "exit 1"
+bool refuse(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    return false;
 }
 
 [[noreturn]] void die_hip(hipError_t e, const char* what) {
@@ -149,8 +161,192 @@ void usage(const char* argv0) {
     std::_Exit(1);
 }
 
-// --scan: the stations in the first max_bytes of stdin, one line each
-int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
+#define CLI_HIP(x)                              \
+    do {                                        \
+        const hipError_t e_ = (x);              \
+        if (e_ != hipSuccess) die_hip(e_, #x);  \
+    } while (0)
+
+// ---- the demod-row switches: one row each, in the order of their end-of-input lines -------------------
+// Every one of them taps the tuned front end's demod rows over whole RDS granules (the meter's frames), so
+// with any of them on the batch is whole granules and the tuner runs; what differs is in its row.
+
+void report_rds(fmrx_ctx* ctx) {
+    fmrx_rds_info info;
+    if (fmrx_rds_info_get(ctx, 0, &info) == FMRX_OK)
+        std::fprintf(stderr, "rds pi=%04X pty=%d ps=\"%s\" groups=%d\n", (unsigned)info.pi, (int)info.pty, info.ps,
+                     (int)info.groups);
+}
+
+void report_rds_sync(fmrx_ctx* ctx) {
+    fmrx_rds_ext x;
+    if (fmrx_rds_blocks_flush(ctx, nullptr, 0, nullptr) != FMRX_OK || fmrx_rds_ext_get(ctx, 0, &x) != FMRX_OK) return;
+    char ct[32] = "-";
+    if (x.ct_set) {
+        const int half = x.ct_offset < 0 ? -x.ct_offset : x.ct_offset;
+        std::snprintf(ct, sizeof ct, "%04d-%02d-%02dT%02d:%02d%c%02d:%02d", (int)x.ct_year, (int)x.ct_month, (int)x.ct_day,
+                      (int)x.ct_hour, (int)x.ct_minute, x.ct_offset < 0 ? '-' : '+', half / 2, half % 2 * 30);
+    }
+    std::fprintf(stderr, "rdsx pi=%04X pty=%d ps=\"%s\" ct=%s af=%d blocks=%llu+%llu groups=%llu+%llu\n", (unsigned)x.pi,
+                 (int)x.pty, x.ps, ct, (int)x.af_n, (unsigned long long)x.exact_blocks,
+                 (unsigned long long)x.corrected_blocks, (unsigned long long)x.groups,
+                 (unsigned long long)x.partial_groups);
+}
+
+void report_meter(fmrx_ctx* ctx) {
+    fmrx_meter_report rep;
+    fmrx_subcarriers sc{};
+    if (fmrx_meter_get(ctx, 0, &rep) == FMRX_OK && (rep.frames == 0 || fmrx_meter_detect(&rep, nullptr, &sc) == FMRX_OK))
+        std::fprintf(stderr, "meter pilot_snr=%.1f stereo=%d rds_snr=%.1f rds=%d frames=%llu\n", (double)sc.pilot_snr_db,
+                     sc.stereo, (double)sc.rds_snr_db, sc.rds, (unsigned long long)rep.frames);
+}
+
+void report_afc(fmrx_ctx* ctx) {
+    fmrx_afc_status st;
+    if (fmrx_afc_get(ctx, 0, &st) == FMRX_OK)
+        std::fprintf(stderr, "afc offset=%+d err=%+.0f carrier=%d retunes=%u frames=%llu\n", (int)st.offset_hz, st.last.err_hz,
+                     st.last.carrier, st.retunes, (unsigned long long)st.total.frames);
+}
+
+void report_blend(fmrx_ctx* ctx) {
+    fmrx_blend_report rep;
+    if (fmrx_blend_get(ctx, 0, &rep) != FMRX_OK) return;
+    double sum = 0.0;
+    for (int l = 0; l <= 16; l++) sum += (double)l * (double)rep.level_frames[l];
+    std::fprintf(stderr, "blend mean=%.2f full=%llu mono=%llu frames=%llu\n", rep.frames ? sum / (16.0 * (double)rep.frames) : 0.0,
+                 (unsigned long long)rep.level_frames[16], (unsigned long long)rep.level_frames[0],
+                 (unsigned long long)rep.frames);
+}
+
+enum { kRds, kRdsSync, kMeter, kAfc, kBlend, kSwitchCount };
+
+struct Switch {
+    const char* flag;
+    int (*turn_on)(fmrx_ctx*);
+    int (*before_tail)(fmrx_ctx*);  // ahead of the blocks past the last whole granule (null: it stays as it is)
+    void (*report)(fmrx_ctx*);      // its line at end of input
+};
+
+const Switch kSwitches[kSwitchCount] = {
+    {"--rds", [](fmrx_ctx* c) { return fmrx_set_rds(c, 1); }, [](fmrx_ctx* c) { return fmrx_set_rds(c, 0); }, report_rds},
+    {"--rds-sync", [](fmrx_ctx* c) { return fmrx_set_rds_sync(c, 1); }, nullptr, report_rds_sync},
+    {"--meter", [](fmrx_ctx* c) { return fmrx_set_meter(c, 1); }, [](fmrx_ctx* c) { return fmrx_set_meter(c, 0); }, report_meter},
+    {"--afc", [](fmrx_ctx* c) { return fmrx_set_afc(c, nullptr, 1); }, [](fmrx_ctx* c) { return fmrx_set_afc(c, nullptr, 0); }, report_afc},
+    {"--blend", [](fmrx_ctx* c) { return fmrx_set_stereo_blend(c, 1, nullptr); }, [](fmrx_ctx* c) { return fmrx_blend_hold(c, 1); }, report_blend},
+};
+
+struct Options {
+    int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
+    bool mono_product = false, tuned = false, scan = false, have_rate = false, have_deemph = false;
+    bool on[kSwitchCount] = {};  // the demod-row switches, by row of kSwitches
+    long offset_hz = 0, capture_rate = 0;
+    int iq_format = FMRX_IQ_U8, capture_decim = 1, deemph_us = 0;
+    long long scan_bytes = 1ll << 24;
+    bool any_switch() const { return std::find(on, on + kSwitchCount, true) != on + kSwitchCount; }
+};
+
+// The arguments into o, and every refusal that needs no context.
+bool parse(int argc, char** argv, Options* o) {
+    bool have_decim = false;
+    const char* bad_format = nullptr;
+    std::vector<const char*> pos;
+    for (int i = 1; i < argc; i++) {
+        const auto is = [&](const char* flag) { return !std::strcmp(argv[i], flag); };
+        const bool value = i + 1 < argc;  // a value follows
+        if (is("--batch") && value) o->batch = std::atoi(argv[++i]);
+        else if (is("--device") && value) o->device = std::atoi(argv[++i]);
+        else if (is("--rf-taps") && value) o->rf_taps = std::atoi(argv[++i]);
+        else if (is("--mono-product")) o->mono_product = true;
+        else if (is("--scan")) o->scan = true;
+        else if (is("--rds")) o->on[kRds] = true;
+        else if (is("--rds-sync")) o->on[kRdsSync] = true;
+        else if (is("--meter")) o->on[kMeter] = true;
+        else if (is("--blend")) o->on[kBlend] = true;
+        else if (is("--afc")) o->on[kAfc] = true;
+        else if (is("--scan-bytes") && value) o->scan_bytes = std::atoll(argv[++i]);
+        else if (is("--iq-format") && value) {
+            static const char* const names[] = {"u8", "s8", "s16", "f32"};  // FMRX_IQ_U8 .. FMRX_IQ_F32
+            const char* f = argv[++i];
+            const auto at = std::find_if(names, names + 4, [&](const char* n) { return !std::strcmp(f, n); });
+            if (at == names + 4) bad_format = f;
+            else o->iq_format = (int)(at - names);
+        }
+        else if (is("--deemph") && value) o->deemph_us = std::atoi(argv[++i]), o->have_deemph = true;
+        else if (is("--capture-decim") && value) o->capture_decim = std::atoi(argv[++i]), have_decim = true;
+        else if (is("--capture-rate") && value) o->capture_rate = std::atol(argv[++i]), o->have_rate = true;
+        else if (is("--offset-hz") && value) o->offset_hz = std::atol(argv[++i]), o->tuned = true;
+        else if (argv[i][0] == '-' && argv[i][1] != '\0' && !(argv[i][1] >= '0' && argv[i][1] <= '9')) return usage(argv[0]);
+        else pos.push_back(argv[i]);  // "-1" is a (negative, invalid) mode as in project
+    }
+    if (pos.size() > 2) return usage(argv[0]);  // project.cpp:292-298
+    if (pos.size() < 2) {  // :278-279 (argc < 3): argv[1] alone is not parsed
+        std::fprintf(stderr, "Operating in default mode 0, mono\n");
+    } else {  // :280-291
+        o->mode = std::atoi(pos[0]);
+        o->channels = std::atoi(pos[1]);
+        if (o->mode < 0 || o->mode > 3) return refuse("Invalid mode: %d!\n", o->mode);
+        if (o->channels < 1 || o->channels > 2) return refuse("Invaild channel: %d!\n", o->channels);  // project.cpp:289, verbatim
+    }
+    if (o->on[kRdsSync] && !o->on[kRds]) return refuse("fmrx: --rds-sync needs --rds\n");
+    if (o->on[kBlend] && (o->channels != 2 || o->mono_product))
+        return refuse("fmrx: --blend needs <channels> 2 (soft stereo blends a stereo decode)\n");
+    if (bad_format) return refuse("fmrx: --iq-format %s: expected u8, s8, s16 or f32\n", bad_format);
+    if (o->capture_decim < 1 || o->capture_decim > 10)
+        return refuse("fmrx: --capture-decim %d: expected 1 to 10\n", o->capture_decim);
+    if (o->have_rate && have_decim) return refuse("fmrx: --capture-rate and --capture-decim exclude each other\n");
+    if (o->have_rate && (o->capture_rate < 1 || o->capture_rate > 2147483647l))
+        return refuse("fmrx: --capture-rate %ld: expected a rate in Hz\n", o->capture_rate);
+    if (o->have_deemph && o->deemph_us != 50 && o->deemph_us != 75)
+        return refuse("fmrx: --deemph %d: expected 50 or 75 (microseconds)\n", o->deemph_us);
+    if (o->batch < 1) o->batch = 1;
+    std::fprintf(stderr, "Operating in mode %d, %s\n", o->mode, o->channels == 1 ? "mono" : "stereo");
+    return true;
+}
+
+// The context and what its input looks like.
+struct Session {
+    fmrx_ctx* ctx = nullptr;
+    fmrx_geometry_t geo;
+    bool wide = false;
+    size_t unit_blocks = 1, unit_pairs = 0;  // a read unit: a block, or with --capture-rate a granule of unit_blocks blocks
+    size_t pair_bytes = 0, block_bytes = 0;  // bytes an I/Q pair and a read unit take (geo.block_bytes for u8 at the mode's rate)
+    size_t batch = 0, rds_unit = 1;          // blocks a batch (whole units); blocks the switches' calls are whole multiples of
+};
+
+// The context, set to stdin's format and rate.
+bool open_context(const Options& o, Session* s) {
+    // project.cpp always writes the stereo R,L stream whatever `channels` says (:179-195).
+    fmrx_config cfg;
+    if (fmrx_config_default(&cfg, o.mode, o.mono_product ? FMRX_MONO : FMRX_STEREO) != FMRX_OK)
+        return refuse("fmrx: %s\n", fmrx_last_error());
+    cfg.device = o.device;
+    cfg.rf_taps = o.rf_taps;
+    if (fmrx_geometry(&cfg, &s->geo) != FMRX_OK || fmrx_create(&cfg, &s->ctx) != FMRX_OK)
+        return refuse("fmrx: %s\n", fmrx_last_error());
+    if (o.iq_format != FMRX_IQ_U8 && fmrx_set_input_format(s->ctx, o.iq_format) != FMRX_OK)
+        return refuse("fmrx: --iq-format: %s\n", fmrx_last_error());
+    s->wide = o.capture_decim > 1;
+    if (s->wide && fmrx_set_capture_decim(s->ctx, o.capture_decim) != FMRX_OK)
+        return refuse("fmrx: --capture-decim: %s\n", fmrx_last_error());
+    s->unit_pairs = s->geo.iq_pairs * (size_t)o.capture_decim;
+    if (o.have_rate) {
+        int d = 1;
+        if (fmrx_set_capture_rate(s->ctx, (int)o.capture_rate) != FMRX_OK || fmrx_capture_decim(s->ctx, &d) != FMRX_OK ||
+            fmrx_wide_granule(s->ctx, &s->unit_blocks, &s->unit_pairs) != FMRX_OK)
+            return refuse("fmrx: --capture-rate: %s\n", fmrx_last_error());
+        s->wide = d != 1;  // fmrx_capture_decim reads 1 at the mode's own rate alone (D, or 0 at a rational ratio): no wide capture
+    }
+    s->pair_bytes = (size_t)fmrx_iq_pair_bytes(o.iq_format);
+    s->block_bytes = s->unit_pairs * s->pair_bytes;
+    s->batch = std::max<size_t>(1, (size_t)o.batch / s->unit_blocks) * s->unit_blocks;
+    s->rds_unit = s->unit_blocks;
+    return true;
+}
+
+// --scan: the stations in the first --scan-bytes of stdin, one line each
+bool scan_stdin(const Options& o, const Session& s) {
+    if (o.scan_bytes <= 0) return refuse("fmrx: --scan-bytes must be positive\n");
+    const size_t max_bytes = (size_t)o.scan_bytes;
     fmrx_scan_config sc;
     (void)fmrx_scan_config_default(&sc);
     std::vector<uint8_t> iq(max_bytes);
@@ -160,204 +356,44 @@ int scan_stdin(fmrx_ctx* ctx, size_t max_bytes, size_t pair_bytes, bool wide) {
         if (r == 0) break;
         got += r;
     }
-    if (got < pair_bytes * (size_t)sc.fft_bins) {
-        std::fprintf(stderr, "fmrx: --scan needs at least %zu bytes of I/Q on stdin, got %zu\n",
-                     pair_bytes * (size_t)sc.fft_bins, got);
-        return 1;
-    }
+    if (got < s.pair_bytes * (size_t)sc.fft_bins)
+        return refuse("fmrx: --scan needs at least %zu bytes of I/Q on stdin, got %zu\n", s.pair_bytes * (size_t)sc.fft_bins, got);
     constexpr int kMaxStations = 256;
     fmrx_station st[kMaxStations];
     int n = 0;
-    if ((wide ? fmrx_scan_wide : fmrx_scan)(ctx, iq.data(), got / pair_bytes, &sc, st, kMaxStations, &n) != FMRX_OK) {
-        std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
-        return 1;
-    }
+    if ((s.wide ? fmrx_scan_wide : fmrx_scan)(s.ctx, iq.data(), got / s.pair_bytes, &sc, st, kMaxStations, &n) != FMRX_OK)
+        return refuse("fmrx: %s\n", fmrx_last_error());
     for (int i = 0; i < n && i < kMaxStations; i++)
         std::printf("%d %.2f %.2f\n", (int)st[i].offset_hz, (double)st[i].power_db, (double)st[i].snr_db);
     std::fflush(stdout);
-    return 0;
+    return true;
 }
 
-#define CLI_HIP(x)                              \
-    do {                                        \
-        const hipError_t e_ = (x);              \
-        if (e_ != hipSuccess) die_hip(e_, #x);  \
-    } while (0)
+// What a decode sets before its first batch: de-emphasis, the switches, the tuner.
+bool prepare(const Options& o, Session* s) {
+    if (o.have_deemph && fmrx_set_deemphasis(s->ctx, o.deemph_us) != FMRX_OK) return refuse("fmrx: --deemph: %s\n", fmrx_last_error());
+    // any switch: whole RDS granules (the meter's frames) a batch (rounded up), decoded by the tuned front end
+    const bool granule = !o.any_switch() || fmrx_rds_granule(s->ctx, &s->rds_unit) == FMRX_OK;
+    for (int r = 0; r < kSwitchCount; r++)
+        if (o.on[r] && (!granule || kSwitches[r].turn_on(s->ctx) != FMRX_OK))
+            return refuse("fmrx: %s: %s\n", kSwitches[r].flag, fmrx_last_error());
+    s->batch = (s->batch + s->rds_unit - 1) / s->rds_unit * s->rds_unit;
+    if (o.tuned || s->wide || o.any_switch()) {  // out of range (or no 32-bit value) -> message, exit 1
+        const int32_t f = (int32_t)o.offset_hz;
+        if ((long)f != o.offset_hz || (s->wide ? fmrx_tune_wide : fmrx_tune)(s->ctx, &f, 0) != FMRX_OK)
+            return refuse("fmrx: --offset-hz %ld: %s\n", o.offset_hz, (long)f != o.offset_hz ? "out of range" : fmrx_last_error());
+    }
+    return true;
+}
 
-}  // namespace
+// stdin to stdout through the ring of three slots, until end of input
+void pump(const Options& o, const Session& ss) {
+    const size_t unit_blocks = ss.unit_blocks, block_bytes = ss.block_bytes, pcm_samples = ss.geo.pcm_samples;
+    const size_t in_cap = block_bytes * (ss.batch / unit_blocks);
+    const size_t out_cap = pcm_samples * ss.batch;
 
-int main(int argc, char** argv) {
-    int mode = 0, channels = 1, batch = 16, device = 0, rf_taps = 51;
-    bool mono_product = false, tuned = false, scan = false, rds = false, rds_sync = false, meter = false, blend = false, afc = false;
-    long offset_hz = 0;
-    int iq_format = FMRX_IQ_U8, capture_decim = 1, deemph_us = 0;
-    long capture_rate = 0;
-    bool have_decim = false, have_rate = false, have_deemph = false;
-    const char* bad_format = nullptr;
-    long long scan_bytes = 1ll << 24;
-    std::vector<const char*> pos;
-    for (int i = 1; i < argc; i++) {
-        if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device = std::atoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--rf-taps") && i + 1 < argc) rf_taps = std::atoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--mono-product")) mono_product = true;
-        else if (!std::strcmp(argv[i], "--scan")) scan = true;
-        else if (!std::strcmp(argv[i], "--rds")) rds = true;
-        else if (!std::strcmp(argv[i], "--rds-sync")) rds_sync = true;
-        else if (!std::strcmp(argv[i], "--meter")) meter = true;
-        else if (!std::strcmp(argv[i], "--blend")) blend = true;
-        else if (!std::strcmp(argv[i], "--afc")) afc = true;
-        else if (!std::strcmp(argv[i], "--scan-bytes") && i + 1 < argc) scan_bytes = std::atoll(argv[++i]);
-        else if (!std::strcmp(argv[i], "--iq-format") && i + 1 < argc) {
-            const char* f = argv[++i];
-            if (!std::strcmp(f, "u8")) iq_format = FMRX_IQ_U8;
-            else if (!std::strcmp(f, "s8")) iq_format = FMRX_IQ_S8;
-            else if (!std::strcmp(f, "s16")) iq_format = FMRX_IQ_S16;
-            else if (!std::strcmp(f, "f32")) iq_format = FMRX_IQ_F32;
-            else bad_format = f;
-        }
-        else if (!std::strcmp(argv[i], "--deemph") && i + 1 < argc) {
-            deemph_us = std::atoi(argv[++i]);
-            have_deemph = true;
-        }
-        else if (!std::strcmp(argv[i], "--capture-decim") && i + 1 < argc) {
-            capture_decim = std::atoi(argv[++i]);
-            have_decim = true;
-        }
-        else if (!std::strcmp(argv[i], "--capture-rate") && i + 1 < argc) {
-            capture_rate = std::atol(argv[++i]);
-            have_rate = true;
-        }
-        else if (!std::strcmp(argv[i], "--offset-hz") && i + 1 < argc) {
-            offset_hz = std::atol(argv[++i]);
-            tuned = true;
-        }
-        else if (argv[i][0] == '-' && argv[i][1] != '\0' && !(argv[i][1] >= '0' && argv[i][1] <= '9')) {
-            usage(argv[0]);
-            return 1;
-        } else pos.push_back(argv[i]);  // "-1" is a (negative, invalid) mode as in project
-    }
-    if (pos.size() < 2) {  // project.cpp:278-279 (argc < 3): argv[1] alone is not parsed
-        std::fprintf(stderr, "Operating in default mode 0, mono\n");
-    } else if (pos.size() == 2) {  // :280-291
-        mode = std::atoi(pos[0]);
-        channels = std::atoi(pos[1]);
-        if (mode < 0 || mode > 3) { std::fprintf(stderr, "Invalid mode: %d!\n", mode); return 1; }
-        if (channels < 1 || channels > 2) { std::fprintf(stderr, "Invaild channel: %d!\n", channels); return 1; }  // project.cpp:289, verbatim
-    } else {  // :292-298
-        usage(argv[0]);
-        return 1;
-    }
-    if (rds_sync && !rds) {
-        std::fprintf(stderr, "fmrx: --rds-sync needs --rds\n");
-        return 1;
-    }
-    if (blend && (channels != 2 || mono_product)) {
-        std::fprintf(stderr, "fmrx: --blend needs <channels> 2 (soft stereo blends a stereo decode)\n");
-        return 1;
-    }
-    if (bad_format) {
-        std::fprintf(stderr, "fmrx: --iq-format %s: expected u8, s8, s16 or f32\n", bad_format);
-        return 1;
-    }
-    if (capture_decim < 1 || capture_decim > 10) {
-        std::fprintf(stderr, "fmrx: --capture-decim %d: expected 1 to 10\n", capture_decim);
-        return 1;
-    }
-    if (have_rate && have_decim) {
-        std::fprintf(stderr, "fmrx: --capture-rate and --capture-decim exclude each other\n");
-        return 1;
-    }
-    if (have_rate && (capture_rate < 1 || capture_rate > 2147483647l)) {
-        std::fprintf(stderr, "fmrx: --capture-rate %ld: expected a rate in Hz\n", capture_rate);
-        return 1;
-    }
-    if (have_deemph && deemph_us != 50 && deemph_us != 75) {
-        std::fprintf(stderr, "fmrx: --deemph %d: expected 50 or 75 (microseconds)\n", deemph_us);
-        return 1;
-    }
-    bool wide = capture_decim > 1;
-    if (batch < 1) batch = 1;
-    std::fprintf(stderr, "Operating in mode %d, %s\n", mode, channels == 1 ? "mono" : "stereo");
-
-    // project.cpp always writes the stereo R,L stream whatever `channels` says (:179-195).
-    const int out_channels = mono_product ? FMRX_MONO : FMRX_STEREO;
-    fmrx_config cfg;
-    if (fmrx_config_default(&cfg, mode, out_channels) != FMRX_OK) {
-        std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
-        return 1;
-    }
-    cfg.device = device;
-    cfg.rf_taps = rf_taps;
-    fmrx_geometry_t geo;
-    fmrx_ctx* ctx = nullptr;
-    if (fmrx_geometry(&cfg, &geo) != FMRX_OK || fmrx_create(&cfg, &ctx) != FMRX_OK) {
-        std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
-        return 1;
-    }
-    if (iq_format != FMRX_IQ_U8 && fmrx_set_input_format(ctx, iq_format) != FMRX_OK) {
-        std::fprintf(stderr, "fmrx: --iq-format: %s\n", fmrx_last_error());
-        fmrx_destroy(ctx);
-        return 1;
-    }
-    if (wide && fmrx_set_capture_decim(ctx, capture_decim) != FMRX_OK) {
-        std::fprintf(stderr, "fmrx: --capture-decim: %s\n", fmrx_last_error());
-        fmrx_destroy(ctx);
-        return 1;
-    }
-    // what one read unit is: a block, or with --capture-rate a granule of unit_blocks blocks
-    size_t unit_blocks = 1, unit_pairs = geo.iq_pairs * (size_t)capture_decim;
-    if (have_rate) {
-        int d = 1;
-        if (fmrx_set_capture_rate(ctx, (int)capture_rate) != FMRX_OK || fmrx_capture_decim(ctx, &d) != FMRX_OK ||
-            fmrx_wide_granule(ctx, &unit_blocks, &unit_pairs) != FMRX_OK) {
-            std::fprintf(stderr, "fmrx: --capture-rate: %s\n", fmrx_last_error());
-            fmrx_destroy(ctx);
-            return 1;
-        }
-        wide = d != 1;  // fmrx_capture_decim reads 1 at the mode's own rate alone (D, or 0 at a rational ratio): no wide capture
-    }
-    const size_t pair_bytes = (size_t)fmrx_iq_pair_bytes(iq_format);
-    const size_t block_bytes = unit_pairs * pair_bytes;  // bytes a read unit; geo.block_bytes for u8 at the mode's rate
-    batch = (int)(std::max<size_t>(1, (size_t)batch / unit_blocks) * unit_blocks);  // whole units
-    if (scan) {
-        const int rc = scan_bytes > 0 ? scan_stdin(ctx, (size_t)scan_bytes, pair_bytes, wide) : 1;
-        if (scan_bytes <= 0) std::fprintf(stderr, "fmrx: --scan-bytes must be positive\n");
-        fmrx_destroy(ctx);
-        return rc;
-    }
-    if (have_deemph && fmrx_set_deemphasis(ctx, deemph_us) != FMRX_OK) {
-        std::fprintf(stderr, "fmrx: --deemph: %s\n", fmrx_last_error());
-        fmrx_destroy(ctx);
-        return 1;
-    }
-    // --rds, --meter: whole RDS granules (the meter's frames) a batch (rounded up), decoded by the tuned front end
-    size_t rds_unit = unit_blocks;
-    if (rds || meter || blend || afc) {
-        if (fmrx_rds_granule(ctx, &rds_unit) != FMRX_OK || (rds && fmrx_set_rds(ctx, 1) != FMRX_OK) ||
-            (rds_sync && fmrx_set_rds_sync(ctx, 1) != FMRX_OK) ||
-            (meter && fmrx_set_meter(ctx, 1) != FMRX_OK) || (blend && fmrx_set_stereo_blend(ctx, 1, nullptr) != FMRX_OK) ||
-            (afc && fmrx_set_afc(ctx, nullptr, 1) != FMRX_OK)) {
-            std::fprintf(stderr, "fmrx: %s: %s\n", rds ? "--rds" : meter ? "--meter" : blend ? "--blend" : "--afc", fmrx_last_error());
-            fmrx_destroy(ctx);
-            return 1;
-        }
-        batch = (int)(((size_t)batch + rds_unit - 1) / rds_unit * rds_unit);
-    }
-    if (tuned || wide || rds || meter || blend || afc) {  // out of range (or no 32-bit value) -> message, exit 1
-        const int32_t f = (int32_t)offset_hz;
-        if ((long)f != offset_hz || (wide ? fmrx_tune_wide : fmrx_tune)(ctx, &f, 0) != FMRX_OK) {
-            std::fprintf(stderr, "fmrx: --offset-hz %ld: %s\n", offset_hz,
-                         (long)f != offset_hz ? "out of range" : fmrx_last_error());
-            fmrx_destroy(ctx);
-            return 1;
-        }
-    }
-    const size_t in_cap = block_bytes * ((size_t)batch / unit_blocks);
-    const size_t out_cap = geo.pcm_samples * (size_t)batch;
-
-    CLI_HIP(hipSetDevice(device));
-    hipStream_t compute = static_cast<hipStream_t>(fmrx_stream(ctx));
+    CLI_HIP(hipSetDevice(o.device));
+    hipStream_t compute = static_cast<hipStream_t>(fmrx_stream(ss.ctx));
     hipStream_t up, down;
     CLI_HIP(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
     CLI_HIP(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
@@ -397,38 +433,39 @@ int main(int argc, char** argv) {
             Slot& s = slots[i];
             if (s.blocks > 0) {
                 CLI_HIP(hipEventSynchronize(s.downloaded));
-                std::fwrite(s.h_out, sizeof(int16_t), s.blocks * geo.pcm_samples, stdout);
+                std::fwrite(s.h_out, sizeof(int16_t), s.blocks * pcm_samples, stdout);
             }
             if (s.last) return;
             free_q.push(i);
         }
     });
 
-    auto process = wide ? fmrx_process_wide_device : fmrx_process_device;
+    auto process = ss.wide ? fmrx_process_wide_device : fmrx_process_device;
     for (;;) {
         const int i = filled_q.pop();
         Slot& s = slots[i];
         if (s.blocks > 0) {
-            // with --rds, --meter or --blend: the whole granules, then (end of input only) the blocks left over without
-            // RDS and meter, blended at the last level
-            const size_t head = s.blocks / rds_unit * rds_unit;
+            // with a switch on: the whole granules, then (end of input only) the blocks left over, every switch as
+            // its row says before the tail
+            const size_t head = s.blocks / ss.rds_unit * ss.rds_unit;
             CLI_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.blocks / unit_blocks * block_bytes, hipMemcpyHostToDevice, up));
             CLI_HIP(hipEventRecord(s.uploaded, up));
             CLI_HIP(hipStreamWaitEvent(compute, s.uploaded, 0));
-            if ((head > 0 && process(ctx, s.d_in, head, s.d_out) != FMRX_OK) ||
-                (head < s.blocks && (fmrx_set_rds(ctx, 0) != FMRX_OK || fmrx_set_meter(ctx, 0) != FMRX_OK ||
-                                     (afc && fmrx_set_afc(ctx, nullptr, 0) != FMRX_OK) ||
-                                     (blend && fmrx_blend_hold(ctx, 1) != FMRX_OK) ||
-                                     process(ctx, s.d_in + head / unit_blocks * block_bytes, s.blocks - head,
-                                             s.d_out + head * geo.pcm_samples) != FMRX_OK))) {
+            bool ok = head == 0 || process(ss.ctx, s.d_in, head, s.d_out) == FMRX_OK;
+            if (ok && head < s.blocks) {
+                for (int r = 0; ok && r < kSwitchCount; r++)
+                    if (o.on[r] && kSwitches[r].before_tail) ok = kSwitches[r].before_tail(ss.ctx) == FMRX_OK;
+                ok = ok && process(ss.ctx, s.d_in + head / unit_blocks * block_bytes, s.blocks - head,
+                                   s.d_out + head * pcm_samples) == FMRX_OK;
+            }
+            if (!ok) {
                 std::fprintf(stderr, "fmrx: %s\n", fmrx_last_error());
                 std::fflush(stdout);
                 std::_Exit(1);
             }
             CLI_HIP(hipEventRecord(s.computed, compute));
             CLI_HIP(hipStreamWaitEvent(down, s.computed, 0));
-            CLI_HIP(hipMemcpyAsync(s.h_out, s.d_out, s.blocks * geo.pcm_samples * sizeof(int16_t),
-                                   hipMemcpyDeviceToHost, down));
+            CLI_HIP(hipMemcpyAsync(s.h_out, s.d_out, s.blocks * pcm_samples * sizeof(int16_t), hipMemcpyDeviceToHost, down));
             CLI_HIP(hipEventRecord(s.downloaded, down));
         }
         done_q.push(i);
@@ -448,51 +485,23 @@ int main(int argc, char** argv) {
     }
     (void)hipStreamDestroy(up);
     (void)hipStreamDestroy(down);
-    if (rds) {
-        fmrx_rds_info info;
-        if (fmrx_rds_info_get(ctx, 0, &info) == FMRX_OK)
-            std::fprintf(stderr, "rds pi=%04X pty=%d ps=\"%s\" groups=%d\n", (unsigned)info.pi, (int)info.pty, info.ps,
-                         (int)info.groups);
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    Options o;
+    Session s;
+    if (!parse(argc, argv, &o)) return 1;
+    bool ok = open_context(o, &s);
+    if (ok && o.scan) {
+        ok = scan_stdin(o, s);
+    } else if (ok && (ok = prepare(o, &s))) {
+        pump(o, s);
+        for (int r = 0; r < kSwitchCount; r++)
+            if (o.on[r]) kSwitches[r].report(s.ctx);
     }
-    if (rds_sync) {
-        fmrx_rds_ext x;
-        if (fmrx_rds_blocks_flush(ctx, nullptr, 0, nullptr) == FMRX_OK && fmrx_rds_ext_get(ctx, 0, &x) == FMRX_OK) {
-            char ct[32] = "-";
-            if (x.ct_set) {
-                const int half = x.ct_offset < 0 ? -x.ct_offset : x.ct_offset;
-                std::snprintf(ct, sizeof ct, "%04d-%02d-%02dT%02d:%02d%c%02d:%02d", (int)x.ct_year, (int)x.ct_month, (int)x.ct_day,
-                              (int)x.ct_hour, (int)x.ct_minute, x.ct_offset < 0 ? '-' : '+', half / 2, half % 2 * 30);
-            }
-            std::fprintf(stderr, "rdsx pi=%04X pty=%d ps=\"%s\" ct=%s af=%d blocks=%llu+%llu groups=%llu+%llu\n", (unsigned)x.pi,
-                         (int)x.pty, x.ps, ct, (int)x.af_n, (unsigned long long)x.exact_blocks,
-                         (unsigned long long)x.corrected_blocks, (unsigned long long)x.groups,
-                         (unsigned long long)x.partial_groups);
-        }
-    }
-    if (meter) {
-        fmrx_meter_report rep;
-        fmrx_subcarriers sc{};
-        if (fmrx_meter_get(ctx, 0, &rep) == FMRX_OK && (rep.frames == 0 || fmrx_meter_detect(&rep, nullptr, &sc) == FMRX_OK))
-            std::fprintf(stderr, "meter pilot_snr=%.1f stereo=%d rds_snr=%.1f rds=%d frames=%llu\n", (double)sc.pilot_snr_db,
-                         sc.stereo, (double)sc.rds_snr_db, sc.rds, (unsigned long long)rep.frames);
-    }
-    if (afc) {
-        fmrx_afc_status st;
-        if (fmrx_afc_get(ctx, 0, &st) == FMRX_OK)
-            std::fprintf(stderr, "afc offset=%+d err=%+.0f carrier=%d retunes=%u frames=%llu\n", (int)st.offset_hz, st.last.err_hz,
-                         st.last.carrier, st.retunes, (unsigned long long)st.total.frames);
-    }
-    if (blend) {
-        fmrx_blend_report rep;
-        if (fmrx_blend_get(ctx, 0, &rep) == FMRX_OK) {
-            double sum = 0.0;
-            for (int l = 0; l <= 16; l++) sum += (double)l * (double)rep.level_frames[l];
-            std::fprintf(stderr, "blend mean=%.2f full=%llu mono=%llu frames=%llu\n", rep.frames ? sum / (16.0 * (double)rep.frames) : 0.0,
-                         (unsigned long long)rep.level_frames[16], (unsigned long long)rep.level_frames[0],
-                         (unsigned long long)rep.frames);
-        }
-    }
-    fmrx_destroy(ctx);
-    std::fprintf(stderr, "End of input stream reached!\n");
-    return 0;
+    fmrx_destroy(s.ctx);
+    if (ok && !o.scan) std::fprintf(stderr, "End of input stream reached!\n");
+    return ok ? 0 : 1;
 }

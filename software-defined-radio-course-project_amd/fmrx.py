@@ -11,6 +11,8 @@ import ctypes as C
 import os
 import re
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
+from typing import NamedTuple
 
 import numpy as np
 
@@ -674,6 +676,149 @@ PROBE_FRAMES = 16  # frames (64 ms each) decode_stations(probe=True) meters befo
 AFC_PASSES = 3     # passes over those frames decode_stations(afc=True) makes at most before it decodes
 
 
+class _Route:
+    """How decode_stations reaches a capture, chosen once from the mode, the dtype's format, capture_decim and
+    capture_rate: at the mode's own rate (scan, tune, process_shared) or through the down-converter (scan_wide,
+    tune_wide, process_wide)."""
+
+    def __init__(self, mode: int, rf_taps: int, fmt: int, capture_decim: int, capture_rate: int | None):
+        self.mode, self.rf_taps, self.fmt, self.decim, self.rate = mode, rf_taps, fmt, capture_decim, capture_rate
+        self.wide = capture_decim != 1 or capture_rate is not None
+        self.rf_fs = geometry(default_config(mode)).rf_fs
+        self.cap_fs = capture_decim * self.rf_fs if capture_rate is None else capture_rate
+
+    @contextmanager
+    def open(self, channels: int, offsets=None):
+        """A context set to the capture's format and rate; with offsets, a stream tuned to each."""
+        with Receiver(self.mode, channels, rf_taps=self.rf_taps, n_streams=len(offsets) if offsets else 1) as rx:
+            if self.fmt != IQ_U8:
+                rx.set_input_format(self.fmt)
+            if self.rate is not None:
+                rx.set_capture_rate(self.rate)
+            elif self.wide:
+                rx.set_capture_decim(self.decim)
+            if offsets:
+                (rx.tune_wide if self.wide else rx.tune)(offsets)
+            yield rx
+
+    def scan(self, rx: Receiver, iq: np.ndarray, **cfg) -> list:
+        return (rx.scan_wide if self.wide else rx.scan)(iq, **cfg)
+
+    def process(self, rx: Receiver, iq: np.ndarray) -> np.ndarray:
+        return (rx.process_wide if self.wide else rx.process_shared)(iq).reshape(rx.n_streams, -1)
+
+    def granule(self, rx: Receiver) -> int:
+        """Elements of the capture an RDS granule (whole frames) takes."""
+        blocks, pairs = rx.wide_granule if self.wide else (1, rx.geo.iq_pairs)
+        return rx.rds_granule // blocks * pairs * 2
+
+    def accepts(self, hz: int) -> bool:
+        """Whether the tuner's design takes the offset."""
+        try:
+            rate_design(self.rf_fs, self.cap_fs, hz) if self.wide else tuner_design(self.rf_fs, hz)
+            return True
+        except FmrxError:
+            return False
+
+
+class _Run(NamedTuple):
+    """What one context's run yields: the PCM, a row a stream, and a list with an entry a stream of each
+    product that was on (None: off)."""
+    pcm: np.ndarray
+    infos: list | None = None
+    levels: list | None = None
+    blends: list | None = None
+    decided: list | None = None
+
+
+def _leading_pass(route: _Route, iq: np.ndarray, offsets: list, meter: bool, measure: bool) -> _Run | None:
+    """A mono context over the capture's leading whole frames, PROBE_FRAMES at most, with the subcarrier meter
+    (levels) and/or the measure-only AFC (decided) on; None when the capture holds no whole frame."""
+    with route.open(MONO, offsets) as rx:
+        per = route.granule(rx)
+        frames = rx.rds_granule * rx.geo.if_samples // (METER_WINDOWS * (rx.geo.bp_fs // 1000))  # a granule's
+        n = min(iq.size // per, max(1, PROBE_FRAMES // frames))
+        if n == 0:
+            return None
+        if meter:
+            rx.set_meter(True)
+        if measure:
+            rx.set_afc(True, track=0)
+        pcm, streams = route.process(rx, iq[: n * per]), range(len(offsets))
+        return _Run(pcm, levels=[meter_detect(rx.meter_report(k)) for k in streams] if meter else None,
+                    decided=[afc_decide(rx.afc_status(k).total, rx.geo.bp_fs) for k in streams] if measure else None)
+
+
+def _afc_passes(route: _Route, iq: np.ndarray, stations: list, probe: bool):
+    """Up to AFC_PASSES leading passes that move every station by afc_decide's correction, within max_pull_hz
+    of where the scan found it and only to offsets the route accepts, until none moves: (the last pass, which
+    with probe carries the levels too, or None; pulls, a dict a station or None)."""
+    found, reach = [s.offset_hz for s in stations], afc_config_default().max_pull_hz
+    last = None
+    for _ in range(AFC_PASSES):
+        last = _leading_pass(route, iq, [s.offset_hz for s in stations], meter=probe, measure=True)
+        moved = False
+        for s, f, d in zip(stations, found, last.decided if last else ()):
+            to = min(f + reach, max(f - reach, s.offset_hz + d["correction_hz"]))
+            if to != s.offset_hz and route.accepts(to):
+                s.offset_hz, moved = to, True
+        if not moved:
+            break
+    if last is None:
+        return None, [None] * len(stations)
+    return last, [{"err_hz": d["err_hz"], "mean_square": d["mean_square"], "carrier": d["carrier"], "pulled_hz": s.offset_hz - f}
+                  for s, f, d in zip(stations, found, last.decided)]
+
+
+def _grouped_decode(route: _Route, iq: np.ndarray, offsets: list, channels: int, rds: bool, levels: list | None,
+                    rds_sync: bool, blend: bool, deemphasis_us: int) -> _Run:
+    """The full decode, one context a group of stations: stereo where channels asks for it, RDS where rds
+    does, and with levels each only where the station's meter found the subcarrier (mono PCM then duplicated
+    into R and L, None in infos and blends).  One group runs in the calling thread; several run side by side, a
+    thread each (a context has a stream of its own and the library's calls release the GIL), so that their
+    serial PLL chains overlap as they do inside one context."""
+    groups: dict = {}
+    for k in range(len(offsets)):
+        stereo = channels == STEREO and (levels is None or bool(levels[k]["stereo"]))
+        groups.setdefault((stereo, rds and (levels is None or bool(levels[k]["rds"]))), []).append(k)
+
+    def decode(group) -> _Run:
+        (stereo, with_rds), sel = group
+        with route.open(STEREO if stereo else MONO, [offsets[k] for k in sel]) as rx:
+            if deemphasis_us:
+                rx.set_deemphasis(deemphasis_us)
+            per = route.granule(rx) if rds or blend else 1  # rds, blend: whole RDS granules of the capture
+            if with_rds:
+                rx.set_rds(True)
+                rx.set_rds_sync(rds_sync)
+            if blend and stereo:
+                rx.set_stereo_blend(True)
+            pcm, streams = route.process(rx, iq[: iq.size // per * per]), range(len(sel))
+            if with_rds and rds_sync:
+                rx.rds_blocks_flush()
+            return _Run(pcm if stereo or channels != STEREO else np.repeat(pcm, 2, axis=1),
+                        infos=[(rx.rds_ext if rds_sync else rx.rds_info)(k).as_dict() for k in streams] if with_rds else None,
+                        blends=[rx.blend_report(k) for k in streams] if blend and stereo else None)
+
+    if len(groups) == 1:
+        runs = [decode(group) for group in groups.items()]
+    else:
+        with ThreadPoolExecutor(max_workers=len(groups)) as pool:
+            runs = list(pool.map(decode, groups.items()))
+    pcm, infos, blends = ([None] * len(offsets) for _ in range(3))
+    for sel, run in zip(groups.values(), runs):
+        for i, k in enumerate(sel):
+            pcm[k], infos[k], blends[k] = run.pcm[i], run.infos and run.infos[i], run.blends and run.blends[i]
+    return _Run(np.stack(pcm), infos, levels or [None] * len(offsets), blends)
+
+
+def _stations_result(stations: list, run: _Run, pulls: list, rds: bool, probe: bool, blend: bool, afc: bool) -> tuple:
+    """decode_stations' result, and the one place that states its order:
+    (stations, pcm[, infos if rds][, levels if probe][, blends if blend][, pulls if afc])."""
+    parts = ((True, stations), (True, run.pcm), (rds, run.infos), (probe, run.levels), (blend, run.blends), (afc, pulls))
+    return tuple(part for wanted, part in parts if wanted)
+
+
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
                     capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, probe: bool = False,
                     rds_sync: bool = False, blend: bool = False, afc: bool = False, **cfg):
@@ -710,119 +855,21 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
         raise ValueError("blend needs channels=STEREO")
     if capture_rate is not None and capture_decim != 1:
         raise ValueError("capture_rate and capture_decim exclude each other")
-    fmt = iq_format_of(iq)  # the dtype says which raw format the capture is
+    route = _Route(mode, rf_taps, iq_format_of(iq), capture_decim, capture_rate)  # the dtype says which raw format
     iq = _iq_flat(iq).reshape(-1)
-    wide = capture_decim != 1 or capture_rate is not None
-    scan, tune, process = ("scan_wide", "tune_wide", "process_wide") if wide else ("scan", "tune", "process_shared")
-
-    def configure(rx):
-        if fmt != IQ_U8:
-            rx.set_input_format(fmt)
-        if capture_rate is not None:
-            rx.set_capture_rate(capture_rate)
-        elif wide:
-            rx.set_capture_decim(capture_decim)
-
-    def run(sel, ch, want_rds, meter=False, measure=False):
-        """The stations sel in one context of ch channels: (pcm rows, infos or None, levels or None, blends or None,
-        AFC decisions or None).  meter, measure: over the leading frames alone, with the meter, the measure-only AFC."""
-        lead = meter or measure
-        data = iq
-        with Receiver(mode, ch, rf_taps=rf_taps, n_streams=len(sel)) as rx:
-            configure(rx)
-            getattr(rx, tune)([stations[k].offset_hz for k in sel])
-            if deemphasis_us and not lead:
-                rx.set_deemphasis(deemphasis_us)
-            if rds or lead or blend:
-                blocks, pairs = rx.wide_granule if wide else (1, rx.geo.iq_pairs)
-                per = rx.rds_granule // blocks * pairs * 2  # elements of the capture an RDS granule (whole frames) takes
-                n = data.size // per
-                if lead:  # the leading frames alone
-                    frames = rx.rds_granule * rx.geo.if_samples // (METER_WINDOWS * (rx.geo.bp_fs // 1000))
-                    n = min(n, max(1, PROBE_FRAMES // frames))
-                    if n == 0:
-                        return None, None, None, None, None
-                data = data[: n * per]
-            if want_rds:
-                rx.set_rds(True)
-                rx.set_rds_sync(rds_sync)
-            if meter:
-                rx.set_meter(True)
-            if measure:
-                rx.set_afc(True, track=0)
-            blended = blend and ch == STEREO and not lead
-            if blended:
-                rx.set_stereo_blend(True)
-            pcm = getattr(rx, process)(data).reshape(len(sel), -1)
-            if want_rds and rds_sync:
-                rx.rds_blocks_flush()
-                infos = [rx.rds_ext(k).as_dict() for k in range(len(sel))]
-            else:
-                infos = [rx.rds_info(k).as_dict() for k in range(len(sel))] if want_rds else None
-            levels = [meter_detect(rx.meter_report(k)) for k in range(len(sel))] if meter else None
-            blends = [rx.blend_report(k) for k in range(len(sel))] if blended else None
-            decided = [afc_decide(rx.afc_status(k).total, rx.geo.bp_fs) for k in range(len(sel))] if measure else None
-        return pcm, infos, levels, blends, decided
-
-    def accepts(hz):
-        try:
-            if wide:
-                rate_design(geo.rf_fs, cap_fs, hz)
-            else:
-                tuner_design(geo.rf_fs, hz)
-            return True
-        except FmrxError:
-            return False
-
-    with Receiver(mode, channels, rf_taps=rf_taps) as rx:
-        configure(rx)
-        stations = getattr(rx, scan)(iq, **cfg)
-        geo, cap_fs = rx.geo, rx.capture_rate[0] if wide else None
-    tail = (([],) if probe else ()) + (([],) if blend else ()) + (([],) if afc else ())
+    want = dict(rds=rds, probe=probe, blend=blend, afc=afc)
+    with route.open(channels) as rx:
+        stations = route.scan(rx, iq, **cfg)
     if not stations:
-        return (([], np.zeros((0, 0), np.int16), []) if rds else ([], np.zeros((0, 0), np.int16))) + tail
-    everyone = list(range(len(stations)))
-    levels, pulls = None, ()
+        return _stations_result([], _Run(np.zeros((0, 0), np.int16), [], [], []), [], **want)
+    lead, pulls = None, None
     if afc:
-        found, reach = [s.offset_hz for s in stations], afc_config_default().max_pull_hz
-        decided = None
-        for _ in range(AFC_PASSES):
-            levels, decided = run(everyone, MONO, False, meter=probe, measure=True)[2::2]
-            moved = False
-            for k, d in enumerate(decided or ()):
-                to = min(found[k] + reach, max(found[k] - reach, stations[k].offset_hz + d["correction_hz"]))
-                if to != stations[k].offset_hz and accepts(to):
-                    stations[k].offset_hz, moved = to, True
-            if not moved:
-                break
-        pulls = ([None if decided is None else {"err_hz": d["err_hz"], "mean_square": d["mean_square"], "carrier": d["carrier"],
-                                                "pulled_hz": stations[k].offset_hz - found[k]}
-                  for k, d in enumerate(decided or [None] * len(stations))],)
-    if not probe:
-        pcm, infos, _, blends, _ = run(everyone, channels, rds)
-        return ((stations, pcm, infos) if rds else (stations, pcm)) + ((blends,) if blend else ()) + pulls
-    if not afc:
-        levels = run(everyone, MONO, False, meter=True)[2]
-    groups: dict = {}
-    for k in everyone:
-        key = (channels == STEREO, rds) if levels is None else (bool(levels[k]["stereo"]) and channels == STEREO,
-                                                                bool(levels[k]["rds"]) and rds)
-        groups.setdefault(key, []).append(k)
-    rows, infos, blends = [None] * len(stations), [None] * len(stations), [None] * len(stations)
-    # the groups' contexts side by side, a thread each (a context has a stream of its own and the library's
-    # calls release the GIL), so that their serial PLL chains overlap as they do inside one context
-    with ThreadPoolExecutor(max_workers=len(groups)) as pool:
-        done = list(pool.map(lambda kv: run(kv[1], STEREO if kv[0][0] else MONO, kv[0][1]), groups.items()))
-    for ((stereo, with_rds), sel), (pcm, inf, _, bl, _) in zip(groups.items(), done):
-        if channels == STEREO and not stereo:
-            pcm = np.repeat(pcm, 2, axis=1)  # mono into R and L
-        for i, k in enumerate(sel):
-            rows[k] = pcm[i]
-            infos[k] = inf[i] if with_rds else None
-            blends[k] = bl[i] if bl else None
-    pcm = np.stack(rows)
-    levels = [None] * len(stations) if levels is None else levels
-    return ((stations, pcm, infos, levels) if rds else (stations, pcm, levels)) + ((blends,) if blend else ()) + pulls
+        lead, pulls = _afc_passes(route, iq, stations, probe)
+    elif probe:
+        lead = _leading_pass(route, iq, [s.offset_hz for s in stations], meter=True, measure=False)
+    run = _grouped_decode(route, iq, [s.offset_hz for s in stations], channels, rds, lead.levels if lead else None,
+                          rds_sync, blend, deemphasis_us)
+    return _stations_result(stations, run, pulls, **want)
 
 
 def synth_host(seed: int, rf_fs: int, first_pair: int, n_pairs: int) -> np.ndarray:

@@ -114,6 +114,33 @@ def landing_capture(frames: int) -> np.ndarray:
     return _cache["u8", frames]
 
 
+SCAN = [-600000, 100000, 700000]
+CAPTURE5_KW = [dict(pilot=0.05, lr=0.10, rds=0.04, audio_hz=1000.0), dict(pilot=0.05, lr=0.10, rds=0.0, audio_hz=2000.0),
+               dict(pilot=0.0, lr=0.0, rds=0.0, audio_hz=3000.0)]
+
+
+def shifted_capture5():
+    """Capture 5 of the meter's tests, 20 frames, every carrier 7 kHz up (a crystal's error)."""
+    import rds_ref as R
+
+    if "shifted" not in _cache:
+        _cache["shifted"] = R.to_u8(stations_iq(20, shift_hz=7000.0, offsets=SCAN, kws=CAPTURE5_KW), amp=38.0, noise_lsb=2.0)
+    return _cache["shifted"]
+
+
+def tracking_capture(kind):
+    """8 frames holding the first two stations, 7 and -13 kHz off their raster points: u8 at the mode's rate, at
+    twice it, or at 10 MS/s (25/6 of it)."""
+    import oracle
+    import rds_ref as R
+
+    if ("track", kind) not in _cache:
+        fs = {"narrow": None, "decim2": 2 * oracle.MODES[0][3], "rate": 10000000}[kind]
+        z = stations_iq(8, offsets=TRUE[:2], kws=STATION_KW[:2], rf_fs=fs)
+        _cache["track", kind] = R.to_u8(z, amp=55.0, noise_lsb=2.0)
+    return _cache["track", kind]
+
+
 def reference_rule(orc, iq_u8: np.ndarray, tuned, calls: int, call_frames: int, **kw) -> list:
     """The tracking rule in float64 on a shared u8 capture of mode 0: per call and stream the front end of
     meter_ref.demod_f64 (the oracle's RF taps) at the stream's current offset, afc_ref's sums and decision over

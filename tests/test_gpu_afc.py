@@ -15,6 +15,7 @@ import iqgen
 import oracle
 import meter_ref as M
 import rds_ref as R
+from afc_ref import SCAN, shifted_capture5, tracking_capture
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +30,6 @@ def _gpu():
 
 
 PI, PS = 0x4D54, "METER FM"
-RF_FS = oracle.MODES[0][3]
 _cache = {}
 
 
@@ -200,16 +200,6 @@ def test_switch_beside_meter_rds_deemphasis_and_blend(fmrx, orc):
 
 # ---- 6. tracking is a retune and nothing else -----------------------------------------------------------
 
-def tracking_capture(kind):
-    """8 frames holding the first two stations, 7 and -13 kHz off their raster points: u8 at the mode's rate, at
-    twice it, or at 10 MS/s (25/6 of it)."""
-    if ("track", kind) not in _cache:
-        fs = {"narrow": None, "decim2": 2 * RF_FS, "rate": 10000000}[kind]
-        z = A.stations_iq(8, offsets=A.TRUE[:2], kws=A.STATION_KW[:2], rf_fs=fs)
-        _cache["track", kind] = R.to_u8(z, amp=55.0, noise_lsb=2.0)
-    return _cache["track", kind]
-
-
 @pytest.mark.parametrize("kind", ["streams", "shared", "decim2", "rate"])
 def test_tracking_equals_retuning_by_hand(fmrx, kind):
     wide = kind in ("decim2", "rate")
@@ -323,18 +313,6 @@ def test_reset_restores_the_origins_and_clears_the_reports(fmrx):
 
 
 # ---- 10. decode_stations ---------------------------------------------------------------------------------
-
-SCAN = [-600000, 100000, 700000]
-CAPTURE5_KW = [dict(pilot=0.05, lr=0.10, rds=0.04, audio_hz=1000.0), dict(pilot=0.05, lr=0.10, rds=0.0, audio_hz=2000.0),
-               dict(pilot=0.0, lr=0.0, rds=0.0, audio_hz=3000.0)]
-
-
-def shifted_capture5():
-    """Capture 5 of the meter's tests, 20 frames, every carrier 7 kHz up (a crystal's error)."""
-    if "shifted" not in _cache:
-        _cache["shifted"] = R.to_u8(A.stations_iq(20, shift_hz=7000.0, offsets=SCAN, kws=CAPTURE5_KW), amp=38.0, noise_lsb=2.0)
-    return _cache["shifted"]
-
 
 def test_decode_stations_afc(fmrx):
     iq = shifted_capture5()
