@@ -568,9 +568,21 @@ int fmrx_set_afc(fmrx_ctx* ctx, const fmrx_afc_config* cfg /* NULL: defaults */,
 int fmrx_afc_get(const fmrx_ctx* ctx, int stream, fmrx_afc_status* out);
 
 /* ---- filter.h primitives on device buffers (context stream; s = per-call state) ------- */
+/* What holds for all of them: any taps, up, down >= 1 and any n >= 0, device pointers aligned to their
+ * element only (4 bytes for float, 1 for the I/Q bytes).  n = 0 is a no-op: FMRX_OK, nothing written,
+ * the carried state as it was (fmrx_pll too).  A null pointer, a negative n, or taps, up or down < 1 is
+ * FMRX_EINVAL with nothing launched.  In place: fmrx_mixer (d_out = d_a or d_b), fmrx_lr_extraction
+ * (d_left, d_right = d_mono, d_stereo in either order) and fmrx_pll (always) run in place, since an element
+ * depends on itself only.  fmrx_resample (d_out = d_in), fmrx_fm_demod and fmrx_fm_demod_arctan
+ * (d_out = d_i or d_q), fmrx_quantize (d_out = d_x) and fmrx_deemph (d_out = d_in) do not, an output
+ * lying where another thread still reads: FMRX_EINVAL.  Only equal pointers are refused; buffers that
+ * overlap in part are the caller's responsibility.                                             */
 int fmrx_impulse_response_lpf(float* h, float fs, float fc, int taps, int gain);      /* host */
 int fmrx_impulse_response_bpf(float* h, float fs, float fb, float fe, int taps);      /* host */
-/* d_state: taps-1 floats (in/out).  Returns the output count in *n_out.                    */
+/* d_state: taps-1 floats (in/out): the inputs in front of d_in[0], afterwards the last taps-1 of d_in,
+ * whatever the output count.  n_in >= taps-1 (a shorter call would have to keep part of the old state:
+ * FMRX_EINVAL).  Returns the output count n_in up / down, which may be 0, in *n_out.  Phases without a
+ * tap (taps < up) give 0.0.                                                                   */
 int fmrx_resample(fmrx_ctx* ctx, float* d_out, float* d_state, const float* d_in, int n_in,
                   const float* d_coeff, int taps, int up, int down, int* n_out);
 /* The de-emphasis kernel on one row, with the context's audio rate's taps for tau_us (50 or 75, whatever
@@ -579,7 +591,7 @@ int fmrx_resample(fmrx_ctx* ctx, float* d_out, float* d_state, const float* d_in
  * quantised form; each may be NULL; d_out must not be d_in.                                         */
 int fmrx_deemph(fmrx_ctx* ctx, const float* d_in, size_t n, int tau_us, float* d_state /* 63 floats, in/out */,
                 float* d_out /* may be NULL */, int16_t* d_pcm /* may be NULL */);
-/* d_prev: 2 floats {prev_i, prev_q} (in/out).                                              */
+/* d_prev: 2 floats {prev_i, prev_q} (in/out; n = 0 leaves them).  d_out must be neither d_i nor d_q. */
 int fmrx_fm_demod(fmrx_ctx* ctx, float* d_out, float* d_prev, const float* d_i,
                   const float* d_q, int n);
 /* d_io: PLL input, overwritten by the NCO output.  d_st: 6 floats {integrator, phaseEst,
@@ -598,7 +610,8 @@ int fmrx_lr_extraction(fmrx_ctx* ctx, float* d_left, float* d_right, const float
                        const float* d_stereo, int n);
 /* u8 interleaved I,Q -> float I and Q (n_pairs each), iofunc.cpp:67 normalisation.        */
 int fmrx_normalize_iq(fmrx_ctx* ctx, const uint8_t* d_iq, size_t n_pairs, float* d_i, float* d_q);
-/* S16 quantiser of project.cpp:185-191 (NaN -> 0, x86 truncation + 16-bit wrap).           */
+/* S16 quantiser of project.cpp:185-191 (NaN -> 0, x86 truncation + 16-bit wrap).  d_out must not be
+ * d_x: output k lies in input k / 2.                                                          */
 int fmrx_quantize(fmrx_ctx* ctx, const float* d_x, size_t n, int16_t* d_out);
 
 /* ---- RDS front half (rds_thread body, src/project.cpp:200-271) ------------------------- */
@@ -783,7 +796,8 @@ int fmrx_rds_ext_get(const fmrx_ctx* ctx, int stream, fmrx_rds_ext* out);
 /* fmDemodArctan: out[k] = atan2(Q,I) phase difference to the previous sample, wrapped into
  * [-pi, pi] as np.unwrap does; computed in double, stored as float.  d_prev_phase (one double,
  * in/out) is the phase before d_i[0]; on return the principal phase of the last sample (the
- * model returns the unwrapped one: equal mod 2 pi).  Device buffers, async.                  */
+ * model returns the unwrapped one: equal mod 2 pi).  Device buffers, async.  d_out must be neither
+ * d_i nor d_q; n = 0 leaves the phase as it was.                                               */
 int fmrx_fm_demod_arctan(fmrx_ctx* ctx, float* d_out, double* d_prev_phase, const float* d_i,
                          const float* d_q, int n);
 /* estimatePSD: Hann window, floor(n / freq_bins) segments, 10 log10(4/(Fs N) |X|^2) for the

@@ -118,12 +118,14 @@ __global__ void mixer_kernel(float* out, const float* a, const float* b, int n) 
     if (i < n) out[i] = 2.0f * (a[i] * b[i]);
 }
 
-// src/filter.cpp:186-199
+// src/filter.cpp:186-199.  Both inputs are read before either output is written: l or r may be m or s
+// (the call runs in place), and then the first store would change what the second sum reads.
 __global__ void lr_kernel(float* l, float* r, const float* m, const float* s, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        l[i] = half_of(m[i] + s[i]);
-        r[i] = half_of(m[i] - s[i]);
+        const float mi = m[i], si = s[i];
+        l[i] = half_of(mi + si);
+        r[i] = half_of(mi - si);
     }
 }
 

@@ -27,6 +27,8 @@ int fmrx_resample(fmrx_ctx* c, float* d_out, float* d_state, const float* d_in, 
     if (!c || !d_out || !d_state || !d_in || !d_coeff || taps < 1 || up < 1 || down < 1)
         return fail(FMRX_EINVAL, "bad argument");
     if (n_in < taps - 1) return fail(FMRX_EINVAL, "input shorter than the filter history");
+    // an output overwrites inputs that later outputs read
+    if (d_out == d_in) return fail(FMRX_EINVAL, "fmrx_resample does not run in place");
     int rc = set_device(c);
     if (rc) return rc;
     const int no = (int)((long long)n_in * up / down);  // filter.cpp:77
@@ -40,6 +42,8 @@ int fmrx_resample(fmrx_ctx* c, float* d_out, float* d_state, const float* d_in, 
 int fmrx_fm_demod(fmrx_ctx* c, float* d_out, float* d_prev, const float* d_i, const float* d_q, int n) {
     CtxLock lock_(c);
     if (!c || !d_out || !d_prev || !d_i || !d_q || n < 0) return fail(FMRX_EINVAL, "bad argument");
+    // sample k reads sample k - 1 of both inputs, which another thread may have overwritten
+    if (d_out == d_i || d_out == d_q) return fail(FMRX_EINVAL, "fmrx_fm_demod does not run in place");
     int rc = set_device(c);
     if (rc) return rc;
     return launch_fm_demod(d_out, d_prev, d_i, d_q, n, c->stream) ? fail(FMRX_EHIP, "launch failed") : 0;
@@ -102,6 +106,9 @@ int fmrx_normalize_iq(fmrx_ctx* c, const uint8_t* d_iq, size_t n_pairs, float* d
 int fmrx_quantize(fmrx_ctx* c, const float* d_x, size_t n, int16_t* d_out) {
     CtxLock lock_(c);
     if (!c || !d_x || !d_out) return fail(FMRX_EINVAL, "bad argument");
+    // a 16-bit output k lies in float k / 2 of the input, which another thread reads
+    if (static_cast<const void*>(d_out) == static_cast<const void*>(d_x))
+        return fail(FMRX_EINVAL, "fmrx_quantize does not run in place");
     int rc = set_device(c);
     if (rc) return rc;
     return launch_quantize(d_x, n, d_out, c->stream) ? fail(FMRX_EHIP, "launch failed") : 0;
@@ -153,6 +160,8 @@ int fmrx_fm_demod_arctan(fmrx_ctx* c, float* d_out, double* d_prev_phase, const 
                          const float* d_q, int n) {
     CtxLock lock_(c);
     if (!c || !d_out || !d_prev_phase || !d_i || !d_q || n < 0) return fail(FMRX_EINVAL, "bad argument");
+    // sample k reads sample k - 1 of both inputs, as fmrx_fm_demod
+    if (d_out == d_i || d_out == d_q) return fail(FMRX_EINVAL, "fmrx_fm_demod_arctan does not run in place");
     int rc = set_device(c);
     if (rc) return rc;
     if (launch_demod_arctan(d_out, d_prev_phase, d_i, d_q, n, c->stream)) return fail(FMRX_EHIP, "launch failed");
