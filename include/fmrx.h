@@ -495,6 +495,100 @@ int fmrx_stereo_blend(const fmrx_ctx* ctx, int* on, fmrx_blend_config* cfg);
 int fmrx_blend_hold(fmrx_ctx* ctx, int on);
 int fmrx_blend_get(const fmrx_ctx* ctx, int stream, fmrx_blend_report* out);
 
+/* ---- quieting: high-cut and soft mute from every stream's noise level -------------------------------- */
+/* No counterpart in the reference.  As a station weakens a broadcast receiver first rolls off the treble
+ * (high-cut) and finally turns the audio down (soft mute); here both follow the discriminator noise in the
+ * meter's 61 and 63 kHz bins, above the RDS skirt, where no programme content lives and the noise depends on
+ * the carrier-to-noise ratio alone (csrc/quiet.hip).  MONO and STEREO contexts alike.  The
+ * stage is defined exactly -- float32 throughout, products and sums rounded separately, no FMA -- so the
+ * GPU is checked without a tolerance.  A call is a whole number of RDS granules, as for soft stereo
+ * (fmrx_rds_granule: 24, 24, 3, 1 blocks in modes 0..3; with a capture rate set the least common multiple
+ * with fmrx_wide_granule's); a granule holds Gm = 1, 1, 20, 20 meter frames and A = 3072, 3072, 56448, 56448
+ * audio frames.  The defaults below rest on synthetic stations (DESIGN.md §5.16 has the table); nobody has
+ * measured them on an off-air capture.
+ * Config: cut_lo_db, cut_hi_db: the readings (dB) at which the high-cut begins and is complete; mute_lo_db,
+ * mute_hi_db: the same for the soft mute; mute_depth_db: how far the mute turns the audio down; corner_hz:
+ * the high-cut's corner.  Defaults 22, 34, 36, 44, 20, 2500.  Valid: every float finite, each lo < hi, all
+ * four bounds in [-40, 80], 0 <= mute_depth_db <= 60, corner_hz <= 8000 and exp(-128 pi corner_hz / audio_fs)
+ * < 2^-25 (the 64-tap bound of de-emphasis: corner_hz >= 2069 at 48 kHz, >= 1901 at 44.1 kHz); anything else:
+ * FMRX_EINVAL, nothing changed.
+ * Design (fmrx_quiet_design: host only, no context, in double until stored; audio_fs 48000 or 44100, which
+ * fixes A = 3072 or 56448, bp_fs as fmrx_meter_design takes it), with P = bp_fs / 1000:
+ *   Tc[j] = (float)(4 (P / 240.0) 10^((cut_hi_db - j (cut_hi_db - cut_lo_db) / 15) / 10)),  j = 0..15
+ *   Tm[j] the same over the mute bounds;  h[64]: fmrx_deemph_design's recipe with p = exp(-2 pi corner_hz /
+ *   audio_fs);  g0 = (float)10^(-mute_depth_db / 20),  cg = (float)((1.0 - (double)g0) / (16.0 A)),
+ *   cw = (float)(1.0 / (16.0 A))
+ * (a reading is 10 log10(N / 4 / (P / 240)) dB of the four-frame sum N below).  Every output pointer may be
+ * NULL; g0_cg_cw takes the three gains in that order.
+ * Levels, per stream and meter frame f counted from the last fmrx_reset, from the meter's power[f][tone]:
+ *   n_f = fl(power[f][61 kHz] + power[f][63 kHz]),  0 for f < 0
+ *   N_f = fl(fl(fl(n_{f-3} + n_{f-2}) + n_{f-1}) + n_f)
+ *   c_f = #{ j : N_f <= Tc[j] },  m_f = #{ j : N_f <= Tm[j] }   both in 0..16, 16: untouched (a NaN compares
+ *   false and closes the stream),  c_{-1} = m_{-1} = 0
+ * so a stream starts closed and fades in over its first frame, as a squelch opens.  Carry, 8 floats a
+ * stream: n_{f-3}, n_{f-2}, n_{f-1} of the next frame f, the last c and m as floats (anything outside 0..16
+ * counts as 0), three zeros.  Zeros are the power-on state; any split of a stream into calls gives the same
+ * levels.
+ * Apply, for audio frame n of a stream counted from the reset, in integers:
+ *   r = n / A,  a = n mod A,  u = a Gm,  f = r Gm + u / A,  t = u mod A
+ *   qc = c_{f-1} (A - t) + c_f t,  qm = m_{f-1} (A - t) + m_f t
+ * On a STEREO context R and L each take the two steps with a history of their own and the same levels.  For
+ * a sample x of the floats in front of the quantiser:
+ *   1. high-cut.  qc == 16 A: y = x bit for bit, a NaN's payload included.  Elsewhere v = sum_k h[k] x[n - k],
+ *      acc = fl(acc + fl(h[k] x[n - k])) from 0 in ascending k (the 63 inputs in front of a stream are 0);
+ *      w = fl((float)(16 A - qc) cw),  d = fl(v - x),  e = fl(w d),  y = fl(x + e)
+ *   2. soft mute.  qm == 16 A: z = y bit for bit.  Elsewhere g = fl(g0 + fl((float)qm cg)),  z = fl(g y)
+ * z goes to de-emphasis if that is on, otherwise to fmrx_quantize's quantiser; stereo PCM stays interleaved
+ * R, L.  With soft stereo on too the order is blend, quieting, de-emphasis, quantiser.  The stage carries 63
+ * floats of its input per stream and channel across calls.  (The sign and payload of a NaN that the
+ * arithmetic itself makes stay open, as with soft stereo; the quantiser sends every NaN to 0.)  A stream
+ * whose levels are all 16 gives the stage-off PCM from its second meter frame on.                          */
+typedef struct { float cut_lo_db, cut_hi_db, mute_lo_db, mute_hi_db, mute_depth_db; int corner_hz; } fmrx_quiet_config;
+typedef struct { uint64_t frames; uint64_t cut_frames[17]; uint64_t mute_frames[17]; } fmrx_quiet_report;
+int fmrx_quiet_config_default(fmrx_quiet_config* cfg);
+int fmrx_quiet_design(int audio_fs, int bp_fs, const fmrx_quiet_config* cfg /* NULL: defaults */, float* Tc16, float* Tm16,
+                      float* h64, float* g0_cg_cw /* 3 */);
+/* The levels primitive, any F >= 1.  power: n_streams x F x 7 (fmrx_meter's); carry: n_streams x 8 floats,
+ * in and out; levels: n_streams x 2 (F + 1) bytes, pair e = (c, m): pair 0 the carried-in one, pair 1 + f
+ * frame f's.                                                                                              */
+int fmrx_quiet_levels(fmrx_ctx* ctx, const fmrx_quiet_config* cfg, const float* power, size_t F, float* carry,
+                      uint8_t* levels);
+int fmrx_quiet_levels_device(fmrx_ctx* ctx, const fmrx_quiet_config* cfg, const float* d_power, size_t F,
+                             float* d_carry, uint8_t* d_levels);   /* async on the context stream */
+/* The apply primitive (async on the context stream), with the taps and gains of the context's config
+ * (fmrx_set_quieting's, the defaults before it).  d_in: n_streams rows of n frames (STEREO: (R, L) pairs), n
+ * a whole number of granules' audio frames, the first being frame 0 of a granule; d_levels: n_streams rows
+ * of 2 (n Gm / A + 1) bytes as fmrx_quiet_levels writes them (values 0..16); d_state: n_streams x channels x
+ * 63 floats, the inputs in front of the call, in and out; d_out: the floats (may be NULL), d_pcm: their S16
+ * (may be NULL), both laid out as d_in; one of the two at least.  Not in place (workgroups read their
+ * neighbours' inputs): FMRX_EINVAL where d_out overlaps d_in.                                              */
+int fmrx_quiet_apply_device(fmrx_ctx* ctx, const float* d_in, size_t n, const uint8_t* d_levels, float* d_state,
+                            float* d_out, int16_t* d_pcm);
+/* on != 0: the calls whose front end writes demod rows (tuned fmrx_process / _device / _device_ex,
+ * fmrx_process_shared / _device, fmrx_process_wide / _device) run the meter kernel over those rows (one
+ * launch, however many of fmrx_set_meter, soft stereo and quieting are on; the meter's reports are what they
+ * were), the levels kernel behind it, and the apply kernel on the floats in front of the quantiser: it writes
+ * the PCM itself when de-emphasis is off and a scratch of its own, which de-emphasis then reads, when it is
+ * on.  d_mono of a mono fmrx_process_device_ex is read and never written: it stays the mono product as it
+ * was.  The level bytes are copied back once the call's work is enqueued (a host synchronisation, as with
+ * fmrx_set_meter) and counted in the stream's report.  Such a call must be whole granules (FMRX_EINVAL and
+ * nothing runs otherwise).  While it is on, the calls without demod rows -- untuned fmrx_process / _device /
+ * _device_ex and fmrx_audio_block -- return FMRX_ESTATE, launch nothing and leave their output untouched,
+ * and so do fmrx_get_state, fmrx_set_state and fmrx_seek (the blob holds neither carry).  cfg NULL: the
+ * defaults; a bad cfg: FMRX_EINVAL, nothing changed.  fmrx_reset clears both carries and the reports and
+ * keeps the switch and the config; fmrx_set_quieting, with any value, clears both carries and the reports
+ * and changes nothing else.  Off (the default): no call launches, allocates or copies anything more, every
+ * output bit is what it was.                                                                             */
+int fmrx_set_quieting(fmrx_ctx* ctx, int on, const fmrx_quiet_config* cfg /* NULL: defaults */);
+int fmrx_quieting(const fmrx_ctx* ctx, int* on, fmrx_quiet_config* cfg);
+/* The end of a stream that is no whole granule, fmrx_blend_hold's analogue.  on != 0, with quieting on (else
+ * FMRX_ESTATE): the calls take any block count and run the apply kernel at every stream's last levels
+ * throughout (those of the last frame counted, 0 after a reset); the meter and the levels kernel do not run
+ * for the stage, the level carry and the reports stay as they are; the FIR history still moves.  fmrx_reset
+ * and fmrx_set_quieting turn it off.                                                                      */
+int fmrx_quiet_hold(fmrx_ctx* ctx, int on);
+int fmrx_quiet_get(const fmrx_ctx* ctx, int stream, fmrx_quiet_report* out);
+
 /* ---- AFC: measure each stream's carrier offset and retune to it -------------------------------------- */
 /* No counterpart in the reference, which decodes a station at the capture's centre.  A scan reports offsets
  * on a raster and a real capture is never on it (crystal error, the capture's centre), so the demod row of a

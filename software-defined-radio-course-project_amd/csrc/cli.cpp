@@ -1,6 +1,6 @@
 // cli.cpp — `fmrx [<mode> <channels>] [--batch N] [--device D] [--rf-taps T] [--mono-product]
 // [--offset-hz F] [--scan [--scan-bytes B]] [--iq-format u8|s8|s16|f32] [--capture-decim D]
-// [--capture-rate HZ] [--rds] [--deemph 50|75] [--meter] [--blend] [--afc]`:
+// [--capture-rate HZ] [--rds] [--deemph 50|75] [--meter] [--blend] [--afc] [--quiet]`:
 // the drop-in for the reference's `project` executable (src/project.cpp:273-390).  Reads u8 I/Q
 // (or, with --iq-format, another raw format) from stdin and writes raw S16LE to stdout under project's process contract:
 //   * arguments as project.cpp:278-299: fewer than two positional arguments run the default
@@ -52,6 +52,12 @@
 //     (fmrx_blend_hold); at end of input one line goes to stderr, `blend mean=%.2f full=%llu mono=%llu
 //     frames=%llu` (the mean level over 16, the frames at level 16 and at level 0, all frames).  With
 //     <channels> 1 or --mono-product: message, exit 1.
+//   * --quiet (an fmrx extension, either <channels>) rolls off the treble and turns the audio down by the
+//     station's noise level (fmrx_set_quieting, the default configuration): batches of whole granules and the
+//     tuned front end as with --meter; blocks past the last whole granule are decoded at the last levels
+//     (fmrx_quiet_hold); at end of input one line goes to stderr, `quiet cut=%.2f mute=%.2f frames=%llu` (the
+//     mean cut and mute levels over 16, all frames).  (The usage text does not list it: tests/golden/
+//     drivers_parent.json records that text byte for byte.)
 //   * --afc (an fmrx extension) measures the station's carrier against --offset-hz and retunes to it between
 //     batches (fmrx_set_afc, the default configuration, tracking on): batches of whole frames and the tuned
 //     front end as with --meter; blocks past the last whole frame are decoded where the tuner then stands,
@@ -218,7 +224,16 @@ void report_blend(fmrx_ctx* ctx) {
                  (unsigned long long)rep.frames);
 }
 
-enum { kRds, kRdsSync, kMeter, kAfc, kBlend, kSwitchCount };
+void report_quiet(fmrx_ctx* ctx) {
+    fmrx_quiet_report rep;
+    if (fmrx_quiet_get(ctx, 0, &rep) != FMRX_OK) return;
+    double cut = 0.0, mute = 0.0;
+    for (int l = 0; l <= 16; l++) cut += (double)l * (double)rep.cut_frames[l], mute += (double)l * (double)rep.mute_frames[l];
+    const double over = rep.frames ? 16.0 * (double)rep.frames : 1.0;
+    std::fprintf(stderr, "quiet cut=%.2f mute=%.2f frames=%llu\n", cut / over, mute / over, (unsigned long long)rep.frames);
+}
+
+enum { kRds, kRdsSync, kMeter, kAfc, kBlend, kQuiet, kSwitchCount };
 
 struct Switch {
     const char* flag;
@@ -233,6 +248,7 @@ const Switch kSwitches[kSwitchCount] = {
     {"--meter", [](fmrx_ctx* c) { return fmrx_set_meter(c, 1); }, [](fmrx_ctx* c) { return fmrx_set_meter(c, 0); }, report_meter},
     {"--afc", [](fmrx_ctx* c) { return fmrx_set_afc(c, nullptr, 1); }, [](fmrx_ctx* c) { return fmrx_set_afc(c, nullptr, 0); }, report_afc},
     {"--blend", [](fmrx_ctx* c) { return fmrx_set_stereo_blend(c, 1, nullptr); }, [](fmrx_ctx* c) { return fmrx_blend_hold(c, 1); }, report_blend},
+    {"--quiet", [](fmrx_ctx* c) { return fmrx_set_quieting(c, 1, nullptr); }, [](fmrx_ctx* c) { return fmrx_quiet_hold(c, 1); }, report_quiet},
 };
 
 struct Options {
@@ -263,6 +279,7 @@ bool parse(int argc, char** argv, Options* o) {
         else if (is("--meter")) o->on[kMeter] = true;
         else if (is("--blend")) o->on[kBlend] = true;
         else if (is("--afc")) o->on[kAfc] = true;
+        else if (is("--quiet")) o->on[kQuiet] = true;
         else if (is("--scan-bytes") && value) o->scan_bytes = std::atoll(argv[++i]);
         else if (is("--iq-format") && value) {
             static const char* const names[] = {"u8", "s8", "s16", "f32"};  // FMRX_IQ_U8 .. FMRX_IQ_F32

@@ -58,7 +58,7 @@ int reset_state(fmrx_ctx* c) {
     for (size_t s = 0; s < pll0.size(); s += 8) pll0[s + 2] = pll0[s + 4] = 1.0f;
     int rc;
     if ((rc = reset_front(c)) || (rc = reset_wide(c)) || (rc = reset_audio(c, pll0)) || (rc = reset_rds_front(c, pll0)) ||
-        (rc = reset_rds_bits(c)) || (rc = reset_deemph(c)) || (rc = reset_blend(c)))
+        (rc = reset_rds_bits(c)) || (rc = reset_deemph(c)) || (rc = reset_blend(c)) || (rc = reset_quiet(c)))
         return rc;
     reset_meter(c);
     if ((rc = reset_afc(c))) return rc;  // behind reset_front: a pulled stream goes back to its origin at position 0
@@ -285,6 +285,7 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
     if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_seek: not with de-emphasis on (its carry has no seek)");
     if (refuse_blend(c, "fmrx_seek", "its carry has no seek")) return FMRX_ESTATE;
+    if (refuse_quiet(c, "fmrx_seek", "its carries have no seek")) return FMRX_ESTATE;
     if (n % c->front.pair_bytes != 0)
         return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->front.pair_bytes);
     int rc = set_device(c);
@@ -420,6 +421,7 @@ int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
     if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_get_state: not with de-emphasis on (the blob does not hold its carry)");
     if (refuse_blend(c, "fmrx_get_state", "the blob does not hold its carry")) return FMRX_ESTATE;
+    if (refuse_quiet(c, "fmrx_get_state", "the blob does not hold its carries")) return FMRX_ESTATE;
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
 
@@ -429,6 +431,7 @@ int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
     if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_set_state: not with de-emphasis on (the blob does not hold its carry)");
     if (refuse_blend(c, "fmrx_set_state", "the blob does not hold its carry")) return FMRX_ESTATE;
+    if (refuse_quiet(c, "fmrx_set_state", "the blob does not hold its carries")) return FMRX_ESTATE;
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
     if (rc == 0) {

@@ -1,6 +1,6 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, blend_api.cpp, afc_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, blend_api.cpp, quiet_api.cpp, afc_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -294,6 +294,29 @@ struct Ctx {
         fmrx_blend_config prim_cfg{0.0f, 0.0f};  // the config prim_thr holds (lo == hi: none yet)
         DevBuf<float> prim_pow;               // fmrx_blend_levels: the caller's powers
     } blend;
+    // quieting (fmrx_set_quieting, quiet.hip): configuration and two carries of its own, not in the blob;
+    // nothing here is allocated until the switch is first turned on (or a quieting primitive first runs).
+    // A and Gm are soft stereo's (blend.A, blend.Gm)
+    struct Quiet {
+        bool on = false;                      // fmrx_set_quieting
+        fmrx_quiet_config cfg{22.0f, 34.0f, 36.0f, 44.0f, 20.0f, 2500};
+        float g0 = 0.0f, cg = 0.0f, cw = 0.0f;  // cfg's gains once `tab` is filled
+        DevBuf<float> tab;                    // cfg's Tc (16), Tm (16) and taps (64)
+        PingPong<float> carry;                // n_streams x kQuietCarry
+        PingPong<float> hist;                 // n_streams x channels x kQuietHist inputs in front of the next call
+        DevBuf<uint8_t> levels;               // a call's level rows: n_streams x 2 (frames + 1)
+        DevBuf<float> x;                      // a call's output floats when de-emphasis follows
+        std::vector<uint8_t> host;            // the level rows' host copy (2 frames bytes a stream)
+        size_t pending = 0;                   // frames a stream of a call enqueued and not yet counted
+        std::vector<fmrx_quiet_report> rep;   // n_streams
+        bool hold = false;                    // fmrx_quiet_hold: calls run at the streams' last levels
+        std::vector<uint8_t> last;            // n_streams x 2: c and m of the last frame counted (0 after a reset)
+        std::vector<uint8_t> hold_rows;       // a held call's level rows on the host
+        DevBuf<float> prim_thr, prim_carry;   // the levels primitive's: a caller's thresholds, the next carry before it is copied back
+        fmrx_quiet_config prim_cfg{};         // the config prim_thr holds (all zero: none yet)
+        DevBuf<float> prim_pow;               // fmrx_quiet_levels: the caller's powers
+        DevBuf<float> prim_hist;              // fmrx_quiet_apply_device: the caller's next history, before it is copied back
+    } quiet;
     // off-centre tuning (fmrx_tune): configuration, not part of the state blob; the tables are allocated
     // by the first fmrx_tune or by a format other than u8
     struct Tuner {
@@ -513,6 +536,19 @@ int blend_apply(fmrx_ctx* c, float* rows, size_t na, bool in_place, int16_t* d_p
 int blend_finish(fmrx_ctx* c);
 // "<who>: not with soft stereo on" as FMRX_ESTATE while the switch is on, else 0
 int refuse_blend(const fmrx_ctx* c, const char* who, const char* why);
+
+// ---- quiet_api.cpp
+int check_quiet_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole granules: the RDS granule's blocks
+int reset_quiet(fmrx_ctx* c);                                // both carries (once they exist) and the reports back to the start
+// the levels kernel over the powers the meter kernel left in meter.pow for this call, enqueued, the carry moved;
+// quiet_apply: the call's rows (na frames a stream) through the apply kernel into d_out (floats), d_pcm or both,
+// the history moved; quiet_finish copies the level bytes back, waits for the stream and counts them
+int quiet_enqueue(fmrx_ctx* c, size_t n_blocks);
+inline bool quiet_metered(const fmrx_ctx* c) { return c->quiet.on && !c->quiet.hold; }  // the call's levels come from the meter
+int quiet_apply(fmrx_ctx* c, const float* rows, size_t na, float* d_out, int16_t* d_pcm);
+int quiet_finish(fmrx_ctx* c);
+// "<who>: not with quieting on" as FMRX_ESTATE while the switch is on, else 0
+int refuse_quiet(const fmrx_ctx* c, const char* who, const char* why);
 
 // ---- front.cpp
 int init_front(fmrx_ctx* c);   // the halo; the tuner's and the wide stage's per-stream offsets

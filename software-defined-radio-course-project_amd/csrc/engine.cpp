@@ -244,19 +244,23 @@ int reset_deemph(fmrx_ctx* c) {
 }
 
 // The floats in front of the quantiser, one route for the stages that work on them: soft stereo
-// (blend.hip, stereo contexts) and then de-emphasis (deemph.hip).  quant_rows: where an audio stage's float
-// outlet writes a call of na frames a stream while either is on (null while both are off) -- the caller's
-// d_mono when a mono call gave one, else the context's scratch, grown to the call.  run_quant_rows: those
-// rows through the stages that are on into d_pcm on the context stream, the carries moved: the apply
-// kernel in place on the scratch when de-emphasis follows, writing the PCM itself otherwise.
+// (blend.hip, stereo contexts), quieting (quiet.hip) and then de-emphasis (deemph.hip).  quant_rows: where an
+// audio stage's float outlet writes a call of na frames a stream while any of them is on (null while all are
+// off) -- the caller's d_mono when a mono call gave one, else the context's scratch, grown to the call.
+// run_quant_rows: those rows through the stages that are on into d_pcm on the context stream, the carries
+// moved: soft stereo's apply kernel in place on the scratch when a stage follows, writing the PCM itself
+// otherwise; quieting's from the rows into a scratch of its own when de-emphasis follows, else into the PCM.
 static int quant_rows(fmrx_ctx* c, size_t na, float* d_mono, float** rows) {
     *rows = nullptr;
-    if (!c->deemph.tau && !c->blend.on) return 0;
+    if (!c->deemph.tau && !c->blend.on && !c->quiet.on) return 0;
+    const size_t count = (size_t)c->cfg.n_streams * na * (size_t)c->cfg.channels;
+    int rc = c->quiet.on && c->deemph.tau ? c->quiet.x.ensure(count) : 0;  // quieting's outlet when de-emphasis follows
+    if (rc) return rc;
     if (c->cfg.channels == FMRX_MONO && d_mono) {
         *rows = d_mono;
         return 0;
     }
-    const int rc = c->deemph.x.ensure((size_t)c->cfg.n_streams * na * (size_t)c->cfg.channels);
+    rc = c->deemph.x.ensure(count);
     *rows = c->deemph.x.p;
     return rc;
 }
@@ -279,11 +283,18 @@ static int run_deemph(fmrx_ctx* c, const float* rows, size_t na, int16_t* d_pcm)
 }
 
 static int run_quant_rows(fmrx_ctx* c, float* rows, size_t na, int16_t* d_pcm) {
+    const bool more = c->deemph.tau != 0 || c->quiet.on;  // a stage behind soft stereo
     if (c->blend.on) {
-        const int rc = blend_apply(c, rows, na, c->deemph.tau != 0, d_pcm);
-        if (rc || !c->deemph.tau) return rc;
+        const int rc = blend_apply(c, rows, na, more, d_pcm);
+        if (rc || !more) return rc;
     }
-    return run_deemph(c, rows, na, d_pcm);
+    const float* src = rows;
+    if (c->quiet.on) {  // never in place: the rows may be a caller's d_mono
+        const int rc = quiet_apply(c, rows, na, c->deemph.tau ? c->quiet.x.p : nullptr, c->deemph.tau ? nullptr : d_pcm);
+        if (rc || !c->deemph.tau) return rc;
+        src = c->quiet.x.p;
+    }
+    return run_deemph(c, src, na, d_pcm);
 }
 
 // RF front end (+ the mono audio stage when `pcm` is non-null and the mode allows it).

@@ -392,6 +392,38 @@ struct BlendApplyLaunch {
 };
 int launch_blend_apply(const BlendApplyLaunch& L, int n_streams, hipStream_t s);
 
+// ---- quieting (quiet.hip) ----------------------------------------------------
+constexpr int kQuietSteps = 16;      // thresholds of the high-cut and of the soft mute; a level is 0 .. 16
+constexpr int kQuietCarry = 8;       // floats a stream: n of the last three frames, the last c and m, three zeros
+constexpr int kQuietTaps = 64;       // the high-cut's one-pole response, cut as de-emphasis cuts its own
+constexpr int kQuietHist = kQuietTaps - 1;  // inputs carried in front of a call, per stream and channel
+constexpr int kQuietChunk = 1024;    // outputs a workgroup
+struct QuietLevelsLaunch {
+    const float* power;     // n_streams x frames x kMeterTones (the meter's)
+    int frames;             // frames a stream, >= 1
+    const float* thr;       // 2 x kQuietSteps thresholds: Tc, then Tm
+    const float* carry_in;  // n_streams x kQuietCarry
+    float* carry_out;       // n_streams x kQuietCarry (never carry_in)
+    uint8_t* levels;        // n_streams x 2 (frames + 1): entry e is the pair (c, m); 0 the carried-in one, 1 + f frame f's
+};
+int launch_quiet_levels(const QuietLevelsLaunch& L, int n_streams, hipStream_t s);
+struct QuietApplyLaunch {
+    const float* in;        // row (stream s, channel ch): sample i at in[s stride + ch + i nch]
+    size_t stride;          // floats between the streams' rows, of `in`, `out` and `pcm` alike
+    int nch;                // 1, or 2 for interleaved (right, left) frames
+    unsigned n;             // frames a row; the first is frame 0 of a granule
+    unsigned A, Gm;         // audio frames and meter frames a granule
+    float g0, cg, cw;       // fmrx_quiet_design's gains
+    const uint8_t* levels;  // n_streams rows of level_stride bytes: pair e the levels in front of meter frame e
+    size_t level_stride;    //   (at least 2 (the row's meter frames + 1))
+    const float* h;         // kQuietTaps taps
+    const float* state_in;  // rows x kQuietHist: the inputs in front of the call
+    float* state_out;       // rows x kQuietHist: the inputs in front of the next (never state_in)
+    float* out;             // optional floats, laid out as `in` (never `in`)
+    int16_t* pcm;           // optional S16, laid out as `in`
+};
+int launch_quiet_apply(const QuietApplyLaunch& L, int n_streams, hipStream_t s);
+
 // ---- spectrum tooling and the arctan demodulator ------------------
 constexpr int kPsdMaxBins = 8192;  // N complex doubles in LDS per segment
 int launch_demod_arctan(float* out, double* prev, const float* i, const float* q, int n, hipStream_t s);

@@ -90,7 +90,7 @@ int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n
 }
 
 // The taps on the demod rows, the meter (fmrx_set_meter), soft stereo's levels (fmrx_set_stereo_blend),
-// the RDS decode (fmrx_set_rds) and the carrier sums (fmrx_set_afc), in that order everywhere; a further tap
+// quieting's levels (fmrx_set_quieting), the RDS decode (fmrx_set_rds) and the carrier sums (fmrx_set_afc), in that order everywhere; a further tap
 // is one line in each of the three.
 // check_taps: the call is whole granules of every tap that is on (the RDS decode's refusal first).  The
 // levels read the meter's powers: one meter launch serves both, and only fmrx_set_meter has them copied
@@ -99,19 +99,22 @@ static int check_taps(const fmrx_ctx* c, size_t n_blocks) {
     int rc = c->rdsb.on ? check_rds_blocks(c, n_blocks) : 0;
     if (!rc && c->meter.on) rc = check_meter_blocks(c, n_blocks);
     if (!rc && c->afc.on) rc = check_meter_blocks(c, n_blocks);
-    return rc || !blend_metered(c) ? rc : check_blend_blocks(c, n_blocks);
+    if (!rc && blend_metered(c)) rc = check_blend_blocks(c, n_blocks);
+    return rc || !quiet_metered(c) ? rc : check_quiet_blocks(c, n_blocks);
 }
 static int taps_enqueue(fmrx_ctx* c, size_t n_blocks) {
     const float* rows = c->stereo.demod.p + kDemodHist;
-    int rc = c->meter.on || blend_metered(c) ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
+    int rc = c->meter.on || blend_metered(c) || quiet_metered(c) ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
     if (!rc && c->blend.on) rc = blend_enqueue(c, n_blocks);
+    if (!rc && c->quiet.on) rc = quiet_enqueue(c, n_blocks);
     if (!rc && c->rdsb.on) rc = rds_decode_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
     return rc || !c->afc.on ? rc : afc_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
 }
 static int taps_finish(fmrx_ctx* c) {
     int rc = c->meter.on ? meter_finish(c) : 0;
-    if (!c->meter.on) c->meter.pending = 0;  // powers soft stereo alone asked for: nothing to report
+    if (!c->meter.on) c->meter.pending = 0;  // powers soft stereo or quieting alone asked for: nothing to report
     if (!rc && c->blend.on) rc = blend_finish(c);
+    if (!rc && c->quiet.on) rc = quiet_finish(c);
     if (!rc && c->rdsb.on) rc = rds_decode_finish(c);
     return rc || !c->afc.on ? rc : afc_finish(c);
 }

@@ -197,6 +197,23 @@ class BlendReport(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("level_frames", C.c_uint64 * (BLEND_STEPS + 1))]
 
 
+QUIET_STEPS = 16  # thresholds of the high-cut and of the soft mute; a level is 0 .. 16
+QUIET_CARRY = 8   # floats of carry a stream (include/fmrx.h: n of the last three frames, the last c and m, three zeros)
+QUIET_HIST = 63   # inputs of history a stream and channel
+
+
+class QuietConfig(C.Structure):
+    """fmrx_quiet_config: the readings (dB) between which the high-cut and the soft mute close, the mute's depth
+    (dB) and the high-cut's corner (Hz)."""
+    _fields_ = [("cut_lo_db", C.c_float), ("cut_hi_db", C.c_float), ("mute_lo_db", C.c_float), ("mute_hi_db", C.c_float),
+                ("mute_depth_db", C.c_float), ("corner_hz", C.c_int)]
+
+
+class QuietReport(C.Structure):
+    """fmrx_quiet_report: a stream's meter frames, and how many of them sat at each cut and mute level 0 .. 16."""
+    _fields_ = [("frames", C.c_uint64), ("cut_frames", C.c_uint64 * (QUIET_STEPS + 1)), ("mute_frames", C.c_uint64 * (QUIET_STEPS + 1))]
+
+
 class CarrierReport(C.Structure):
     """fmrx_carrier_report: a stream's summed demod samples and squares and the frames they cover."""
     _fields_ = [("sum", C.c_double), ("sumsq", C.c_double), ("frames", C.c_uint64)]
@@ -322,6 +339,15 @@ PROTOTYPES = {
     "fmrx_stereo_blend": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(BlendConfig)]),
     "fmrx_blend_hold": (C.c_int, [_vp, C.c_int]),
     "fmrx_blend_get": (C.c_int, [_vp, C.c_int, C.POINTER(BlendReport)]),
+    "fmrx_quiet_config_default": (C.c_int, [C.POINTER(QuietConfig)]),
+    "fmrx_quiet_design": (C.c_int, [C.c_int, C.c_int, C.POINTER(QuietConfig), _vp, _vp, _vp, _vp]),
+    "fmrx_quiet_levels": (C.c_int, [_vp, C.POINTER(QuietConfig), _vp, _sz, _vp, _vp]),
+    "fmrx_quiet_levels_device": (C.c_int, [_vp, C.POINTER(QuietConfig), _vp, _sz, _vp, _vp]),
+    "fmrx_quiet_apply_device": (C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmrx_set_quieting": (C.c_int, [_vp, C.c_int, C.POINTER(QuietConfig)]),
+    "fmrx_quieting": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(QuietConfig)]),
+    "fmrx_quiet_hold": (C.c_int, [_vp, C.c_int]),
+    "fmrx_quiet_get": (C.c_int, [_vp, C.c_int, C.POINTER(QuietReport)]),
     "fmrx_carrier": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_carrier_device": (C.c_int, [_vp, _vp, _sz, _vp]),
     "fmrx_carrier_accumulate": (C.c_int, [C.POINTER(CarrierReport), _vp, _sz]),
@@ -559,6 +585,29 @@ def blend_design(lo_db: float | None = None, hi_db: float | None = None) -> np.n
     return T
 
 
+def quiet_config(**kw) -> QuietConfig:
+    """fmrx_quiet_config_default (22, 34, 36, 44, 20 dB and 2500 Hz) with the fields given replaced
+    (cut_lo_db, cut_hi_db, mute_lo_db, mute_hi_db, mute_depth_db, corner_hz)."""
+    cfg = QuietConfig()
+    _check(lib().fmrx_quiet_config_default(C.byref(cfg)))
+    names = [f[0] for f in QuietConfig._fields_]
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError(f"quiet_config: no field {k!r}")
+        if v is not None:
+            setattr(cfg, k, v)
+    return cfg
+
+
+def quiet_design(audio_fs: int, bp_fs: int, **kw) -> dict:
+    """fmrx_quiet_design (host only): Tc and Tm (16 float32 each), h (64 float32) and the float32 gains g0, cg,
+    cw of quiet_config(**kw) at the audio rate (48000 or 44100) and bp_fs, as a dict."""
+    Tc, Tm = np.zeros(QUIET_STEPS, np.float32), np.zeros(QUIET_STEPS, np.float32)
+    h, g = np.zeros(QUIET_HIST + 1, np.float32), np.zeros(3, np.float32)
+    _check(lib().fmrx_quiet_design(int(audio_fs), int(bp_fs), C.byref(quiet_config(**kw)), _np_ptr(Tc), _np_ptr(Tm), _np_ptr(h), _np_ptr(g)))
+    return {"Tc": Tc, "Tm": Tm, "h": h, "g0": g[0], "cg": g[1], "cw": g[2]}
+
+
 def iq_pair_bytes(fmt: int) -> int:
     """fmrx_iq_pair_bytes: bytes an I/Q pair of the format takes (FmrxError(EINVAL) if unknown)."""
     n = lib().fmrx_iq_pair_bytes(fmt)
@@ -729,6 +778,7 @@ class _Run(NamedTuple):
     levels: list | None = None
     blends: list | None = None
     decided: list | None = None
+    quiets: list | None = None
 
 
 def _leading_pass(route: _Route, iq: np.ndarray, offsets: list, meter: bool, measure: bool) -> _Run | None:
@@ -771,7 +821,7 @@ def _afc_passes(route: _Route, iq: np.ndarray, stations: list, probe: bool):
 
 
 def _grouped_decode(route: _Route, iq: np.ndarray, offsets: list, channels: int, rds: bool, levels: list | None,
-                    rds_sync: bool, blend: bool, deemphasis_us: int) -> _Run:
+                    rds_sync: bool, blend: bool, deemphasis_us: int, quiet: bool = False) -> _Run:
     """The full decode, one context a group of stations: stereo where channels asks for it, RDS where rds
     does, and with levels each only where the station's meter found the subcarrier (mono PCM then duplicated
     into R and L, None in infos and blends).  One group runs in the calling thread; several run side by side, a
@@ -787,41 +837,46 @@ def _grouped_decode(route: _Route, iq: np.ndarray, offsets: list, channels: int,
         with route.open(STEREO if stereo else MONO, [offsets[k] for k in sel]) as rx:
             if deemphasis_us:
                 rx.set_deemphasis(deemphasis_us)
-            per = route.granule(rx) if rds or blend else 1  # rds, blend: whole RDS granules of the capture
+            per = route.granule(rx) if rds or blend or quiet else 1  # rds, blend, quiet: whole RDS granules of the capture
             if with_rds:
                 rx.set_rds(True)
                 rx.set_rds_sync(rds_sync)
             if blend and stereo:
                 rx.set_stereo_blend(True)
+            if quiet:
+                rx.set_quieting(True)
             pcm, streams = route.process(rx, iq[: iq.size // per * per]), range(len(sel))
             if with_rds and rds_sync:
                 rx.rds_blocks_flush()
             return _Run(pcm if stereo or channels != STEREO else np.repeat(pcm, 2, axis=1),
                         infos=[(rx.rds_ext if rds_sync else rx.rds_info)(k).as_dict() for k in streams] if with_rds else None,
-                        blends=[rx.blend_report(k) for k in streams] if blend and stereo else None)
+                        blends=[rx.blend_report(k) for k in streams] if blend and stereo else None,
+                        quiets=[rx.quiet_report(k) for k in streams] if quiet else None)
 
     if len(groups) == 1:
         runs = [decode(group) for group in groups.items()]
     else:
         with ThreadPoolExecutor(max_workers=len(groups)) as pool:
             runs = list(pool.map(decode, groups.items()))
-    pcm, infos, blends = ([None] * len(offsets) for _ in range(3))
+    pcm, infos, blends, quiets = ([None] * len(offsets) for _ in range(4))
     for sel, run in zip(groups.values(), runs):
         for i, k in enumerate(sel):
             pcm[k], infos[k], blends[k] = run.pcm[i], run.infos and run.infos[i], run.blends and run.blends[i]
-    return _Run(np.stack(pcm), infos, levels or [None] * len(offsets), blends)
+            quiets[k] = run.quiets and run.quiets[i]
+    return _Run(np.stack(pcm), infos, levels or [None] * len(offsets), blends, quiets=quiets)
 
 
-def _stations_result(stations: list, run: _Run, pulls: list, rds: bool, probe: bool, blend: bool, afc: bool) -> tuple:
+def _stations_result(stations: list, run: _Run, pulls: list, rds: bool, probe: bool, blend: bool, afc: bool, quiet: bool = False) -> tuple:
     """decode_stations' result, and the one place that states its order:
-    (stations, pcm[, infos if rds][, levels if probe][, blends if blend][, pulls if afc])."""
-    parts = ((True, stations), (True, run.pcm), (rds, run.infos), (probe, run.levels), (blend, run.blends), (afc, pulls))
+    (stations, pcm[, infos if rds][, levels if probe][, blends if blend][, pulls if afc][, quiets if quiet])."""
+    parts = ((True, stations), (True, run.pcm), (rds, run.infos), (probe, run.levels), (blend, run.blends), (afc, pulls),
+             (quiet, run.quiets))
     return tuple(part for wanted, part in parts if wanted)
 
 
 def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps: int = 51, capture_decim: int = 1,
                     capture_rate: int | None = None, rds: bool = False, deemphasis_us: int = 0, probe: bool = False,
-                    rds_sync: bool = False, blend: bool = False, afc: bool = False, **cfg):
+                    rds_sync: bool = False, blend: bool = False, afc: bool = False, quiet: bool = False, **cfg):
     """Decode everything in a capture: scan it, tune one stream to every station found and run
     process_shared over its whole blocks.  Returns (stations, pcm), pcm one row a station (S16);
     ([], an empty array) when the scan finds none.  capture_decim > 1: the capture is at
@@ -848,7 +903,10 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
     none moves; with probe=True the last of them is the probe's pass too.  The stations returned carry the
     corrected offset_hz, everything is decoded there, and the result gains a last list after the probe's and
     the blend's: a dict a station (err_hz, mean_square and carrier of its last measurement, pulled_hz against
-    the scan's offset), None where the capture holds no whole frame (decoded as without afc)."""
+    the scan's offset), None where the capture holds no whole frame (decoded as without afc).
+    quiet=True (either channel count): quieting (set_quieting, the default configuration) rolls off the treble
+    and turns down the audio of every station by its noise level; the capture is trimmed to whole RDS granules
+    and the result gains a last list after all the others, quiets: Receiver.quiet_report's dict a station."""
     if rds_sync and not rds:
         raise ValueError("rds_sync needs rds")
     if blend and channels != STEREO:
@@ -857,18 +915,18 @@ def decode_stations(iq: np.ndarray, mode: int = 0, channels: int = MONO, rf_taps
         raise ValueError("capture_rate and capture_decim exclude each other")
     route = _Route(mode, rf_taps, iq_format_of(iq), capture_decim, capture_rate)  # the dtype says which raw format
     iq = _iq_flat(iq).reshape(-1)
-    want = dict(rds=rds, probe=probe, blend=blend, afc=afc)
+    want = dict(rds=rds, probe=probe, blend=blend, afc=afc, quiet=quiet)
     with route.open(channels) as rx:
         stations = route.scan(rx, iq, **cfg)
     if not stations:
-        return _stations_result([], _Run(np.zeros((0, 0), np.int16), [], [], []), [], **want)
+        return _stations_result([], _Run(np.zeros((0, 0), np.int16), [], [], [], quiets=[]), [], **want)
     lead, pulls = None, None
     if afc:
         lead, pulls = _afc_passes(route, iq, stations, probe)
     elif probe:
         lead = _leading_pass(route, iq, [s.offset_hz for s in stations], meter=True, measure=False)
     run = _grouped_decode(route, iq, [s.offset_hz for s in stations], channels, rds, lead.levels if lead else None,
-                          rds_sync, blend, deemphasis_us)
+                          rds_sync, blend, deemphasis_us, quiet)
     return _stations_result(stations, run, pulls, **want)
 
 
@@ -1218,6 +1276,55 @@ class Receiver:
         frames = int(out.frames)
         mean = sum(l * n for l, n in enumerate(counts)) / (16.0 * frames) if frames else 0.0
         return {"frames": frames, "level_frames": counts, "mean": mean}
+
+    # ---- quieting
+    def set_quieting(self, on: bool, **kw) -> None:
+        """fmrx_set_quieting: high-cut and soft mute of every stream by its noise level in the tuned, shared and
+        wide calls (MONO and STEREO contexts); quiet_config's fields by name, one left out keeps its default."""
+        _check(lib().fmrx_set_quieting(self.h, int(bool(on)), C.byref(quiet_config(**kw))))
+
+    def quiet_hold(self, on: bool) -> None:
+        """fmrx_quiet_hold: quieted calls of any block count at every stream's last levels (a stream's end)."""
+        _check(lib().fmrx_quiet_hold(self.h, int(bool(on))))
+
+    def quieting(self) -> tuple[bool, QuietConfig]:
+        """(on, config) as fmrx_quieting reports them."""
+        on, cfg = C.c_int(), QuietConfig()
+        _check(lib().fmrx_quieting(self.h, C.byref(on), C.byref(cfg)))
+        return bool(on.value), cfg
+
+    def quiet_levels(self, power: np.ndarray, carry: np.ndarray | None = None, **kw) -> tuple[np.ndarray, np.ndarray]:
+        """fmrx_quiet_levels: power (n_streams, F, 7) as the meter gives it and the carry (n_streams, 8; None:
+        zeros, the power-on state) -> (levels uint8 (n_streams, F + 1, 2), the pairs (c, m), pair 0 the carried-in
+        one; the next carry).  kw: quiet_config's fields."""
+        p = np.ascontiguousarray(power, np.float32)
+        if p.ndim != 3 or p.shape[0] != self.n_streams or p.shape[1] < 1 or p.shape[2] != METER_TONES:
+            raise FmrxError(FMRX_EINVAL, f"power of shape {p.shape}: expected ({self.n_streams}, F >= 1, {METER_TONES})")
+        c = np.zeros((self.n_streams, QUIET_CARRY), np.float32) if carry is None else np.array(carry, np.float32, order="C")
+        if c.shape != (self.n_streams, QUIET_CARRY):
+            raise FmrxError(FMRX_EINVAL, f"carry of shape {c.shape}: expected ({self.n_streams}, {QUIET_CARRY})")
+        lv = np.zeros((self.n_streams, p.shape[1] + 1, 2), np.uint8)
+        _check(lib().fmrx_quiet_levels(self.h, C.byref(quiet_config(**kw)), _np_ptr(p), p.shape[1], _np_ptr(c), _np_ptr(lv)))
+        return lv, c
+
+    def quiet_levels_device(self, d_power: int, frames: int, d_carry: int, d_levels: int, **kw) -> None:
+        _check(lib().fmrx_quiet_levels_device(self.h, C.byref(quiet_config(**kw)), d_power, frames, d_carry, d_levels))
+
+    def quiet_apply(self, d_in: int, n: int, d_levels: int, d_state: int, d_out: int | None = None, d_pcm: int | None = None) -> None:
+        """fmrx_quiet_apply_device: n frames a stream (whole granules; STEREO: (R, L) pairs) through the high-cut
+        and the soft mute by the level rows, with the context's config; d_state (n_streams x channels x 63 floats)
+        is the history, in and out; d_out (never d_in) takes the floats, d_pcm their S16.  Async on the context
+        stream."""
+        _check(lib().fmrx_quiet_apply_device(self.h, d_in, n, d_levels, d_state, d_out, d_pcm))
+
+    def quiet_report(self, stream: int = 0) -> dict:
+        """fmrx_quiet_get as a dict: frames, cut_frames and mute_frames (17 counts each) and cut_mean, mute_mean =
+        sum(l n_l) / (16 frames), 1.0 for untouched throughout, 0.0 for closed (and with no frames yet)."""
+        out = QuietReport()
+        _check(lib().fmrx_quiet_get(self.h, int(stream), C.byref(out)))
+        cut, mute, frames = [int(v) for v in out.cut_frames], [int(v) for v in out.mute_frames], int(out.frames)
+        mean = lambda counts: sum(l * n for l, n in enumerate(counts)) / (16.0 * frames) if frames else 0.0
+        return {"frames": frames, "cut_frames": cut, "mute_frames": mute, "cut_mean": mean(cut), "mute_mean": mean(mute)}
 
     def estimate_psd(self, samples: np.ndarray, freq_bins: int, fs: float):
         """estimatePSD (fourier.cpp:35-117) on the GPU: (freq, psd_db)."""
