@@ -9,15 +9,11 @@ using namespace fmrx;
 
 namespace {
 
-inline size_t carrier_frames(const fmrx_ctx* c, size_t n_blocks) {
-    return n_blocks * c->geo.if_samples / ((size_t)kMeterWindows * (size_t)(c->geo.bp_fs / 1000));
-}
-
 // the kernel over the rows at d_demod (whole frames) into d_sums, enqueued
 int run_carrier(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks, float* d_sums) {
     int P = 0;
     if (!meter_design(c->geo.bp_fs, &P, nullptr)) return fail(FMRX_EINVAL, "no frame at bp_fs %d", c->geo.bp_fs);
-    const size_t frames = carrier_frames(c, n_blocks);
+    const size_t frames = meter_frames(c, n_blocks);
     if (frames > 0x7FFFFFFFull) return fail(FMRX_EINVAL, "%zu blocks: too many frames for one carrier call", n_blocks);
     CarrierLaunch L{};
     L.demod = d_demod;
@@ -26,8 +22,7 @@ int run_carrier(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n
     L.frames = (int)frames;
     L.sums = d_sums;
     const int rc = launch_carrier(L, c->cfg.n_streams, c->stream);
-    if (rc) return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "carrier launch failed (%d)%s", rc, rc == -1 ? ": rows 16-byte aligned?" : "");
-    return 0;
+    return rc ? launch_failed(rc, "carrier", ": rows 16-byte aligned?") : 0;
 }
 
 bool config_ok(const fmrx_afc_config& k) {
@@ -130,7 +125,7 @@ void afc_caller_tuned(fmrx_ctx* c) {
 }
 
 int afc_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks) {
-    const size_t ns = c->cfg.n_streams, frames = carrier_frames(c, n_blocks);
+    const size_t ns = c->cfg.n_streams, frames = meter_frames(c, n_blocks);
     c->afc.pending = 0;
     int rc;
     if ((rc = c->afc.sums.ensure(ns * frames * 2))) return rc;
@@ -162,7 +157,7 @@ extern "C" {
 int fmrx_carrier_device(fmrx_ctx* c, const float* d_demod, size_t n_blocks, float* d_sums) {
     CtxLock lock_(c);
     if (!c || !d_demod || !d_sums) return fail(FMRX_EINVAL, "null argument");
-    int rc = check_meter_blocks(c, n_blocks);
+    int rc = check_frame_blocks(c, n_blocks, "a carrier call");
     if (rc || n_blocks == 0) return rc;
     if ((rc = set_device(c))) return rc;
     return run_carrier(c, d_demod, n_blocks * c->geo.if_samples, n_blocks, d_sums);
@@ -171,11 +166,11 @@ int fmrx_carrier_device(fmrx_ctx* c, const float* d_demod, size_t n_blocks, floa
 int fmrx_carrier(fmrx_ctx* c, const float* demod, size_t n_blocks, float* sums) {
     CtxLock lock_(c);
     if (!c || !demod || !sums) return fail(FMRX_EINVAL, "null argument");
-    int rc = check_meter_blocks(c, n_blocks);
+    int rc = check_frame_blocks(c, n_blocks, "a carrier call");
     if (rc || n_blocks == 0) return rc;
     if ((rc = set_device(c))) return rc;
     const size_t ns = c->cfg.n_streams, n_if = n_blocks * c->geo.if_samples;
-    const size_t n_sums = ns * carrier_frames(c, n_blocks) * 2;
+    const size_t n_sums = ns * meter_frames(c, n_blocks) * 2;
     if ((rc = c->io.f32.ensure(ns * n_if)) || (rc = c->afc.sums.ensure(n_sums))) return rc;
     HIPCHK(hipMemcpyAsync(c->io.f32.p, demod, sizeof(float) * ns * n_if, hipMemcpyHostToDevice, c->stream));
     if ((rc = run_carrier(c, c->io.f32.p, n_if, n_blocks, c->afc.sums.p))) return rc;

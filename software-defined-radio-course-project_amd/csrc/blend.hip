@@ -32,7 +32,7 @@ constexpr int kThreads = 256;
 constexpr int kA = 1, kG17 = 0, kG21 = 2;  // the tones of a frame's seven that the levels read
 static_assert(kBlendPer == 4, "a lane's frames are two float4 and its PCM one uint4");
 
-__global__ void __launch_bounds__(kThreads) blend_levels_kernel(BlendLevelsLaunch L, const float* __restrict__ thr, int n_streams) {
+__global__ void __launch_bounds__(kThreads) blend_levels_kernel(LevelsLaunch L, const float* __restrict__ thr, int n_streams) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= (long long)n_streams * L.frames) return;
     const int s = (int)(i / L.frames), f = (int)(i - (long long)s * L.frames);
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(kThreads) blend_apply_kernel(BlendApplyLaunch 
 
 }  // namespace
 
-int launch_blend_levels(const BlendLevelsLaunch& L, int n_streams, hipStream_t s) {
+int launch_blend_levels(const LevelsLaunch& L, int n_streams, hipStream_t s) {
     if (n_streams <= 0) return 0;
     if (L.frames < 1 || L.carry_in == L.carry_out) return -1;
     const long long lanes = (long long)n_streams * L.frames;

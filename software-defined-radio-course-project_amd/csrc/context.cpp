@@ -245,6 +245,7 @@ int fmrx_create(const fmrx_config* cfg, fmrx_ctx** out) {
     if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
         hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi) != hipSuccess)
         return failed(fail(FMRX_EHIP, "hipStreamCreate failed"));
+    init_frames(c);
     init_blend(c);
     if ((rc = init_front(c)) || (rc = init_audio(c)) || (rc = init_rds_front(c)) || (rc = init_rds_bits(c)) ||
         (rc = reset_state(c)))
@@ -284,8 +285,7 @@ int fmrx_seek(fmrx_ctx* c, const uint8_t* prev, size_t n, int prev_on_device) {
     if (c->cfg.channels != FMRX_MONO) return fail(FMRX_ESTATE, "fmrx_seek: mono product only (the PLL is serial)");
     if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_seek: not with a capture decimation (the wide stage has no seek)");
     if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_seek: not with de-emphasis on (its carry has no seek)");
-    if (refuse_blend(c, "fmrx_seek", "its carry has no seek")) return FMRX_ESTATE;
-    if (refuse_quiet(c, "fmrx_seek", "its carries have no seek")) return FMRX_ESTATE;
+    if (refuse_row_stages(c, "fmrx_seek", "its carry has no seek", "its carries have no seek")) return FMRX_ESTATE;
     if (n % c->front.pair_bytes != 0)
         return fail(FMRX_EINVAL, "fmrx_seek: %zu bytes are no whole number of %zu-byte I/Q pairs", n, c->front.pair_bytes);
     int rc = set_device(c);
@@ -420,8 +420,7 @@ int fmrx_get_state(fmrx_ctx* c, void* buf, size_t bytes) {
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
     if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_get_state: not with a capture decimation (no checkpoint of the wide stage)");
     if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_get_state: not with de-emphasis on (the blob does not hold its carry)");
-    if (refuse_blend(c, "fmrx_get_state", "the blob does not hold its carry")) return FMRX_ESTATE;
-    if (refuse_quiet(c, "fmrx_get_state", "the blob does not hold its carries")) return FMRX_ESTATE;
+    if (refuse_row_stages(c, "fmrx_get_state", "the blob does not hold its carry", "the blob does not hold its carries")) return FMRX_ESTATE;
     return state_io(c, static_cast<uint8_t*>(buf), bytes, false);
 }
 
@@ -430,8 +429,7 @@ int fmrx_set_state(fmrx_ctx* c, const void* buf, size_t bytes) {
     if (!c || !buf) return fail(FMRX_EINVAL, "null argument");
     if (c->wide.ratio.on()) return fail(FMRX_ESTATE, "fmrx_set_state: not with a capture decimation (no checkpoint of the wide stage)");
     if (c->deemph.tau) return fail(FMRX_ESTATE, "fmrx_set_state: not with de-emphasis on (the blob does not hold its carry)");
-    if (refuse_blend(c, "fmrx_set_state", "the blob does not hold its carry")) return FMRX_ESTATE;
-    if (refuse_quiet(c, "fmrx_set_state", "the blob does not hold its carries")) return FMRX_ESTATE;
+    if (refuse_row_stages(c, "fmrx_set_state", "the blob does not hold its carry", "the blob does not hold its carries")) return FMRX_ESTATE;
     const uint8_t* p = static_cast<const uint8_t*>(buf);
     const int rc = state_io(c, const_cast<uint8_t*>(p), bytes, true);
     if (rc == 0) {

@@ -1,12 +1,13 @@
 // ctx.h — what the host runtime's files share: the context, its buffers, the error text and the
 // functions that cross files.  Private to the host sources (context.cpp, engine.cpp, front.cpp,
-// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, blend_api.cpp, quiet_api.cpp, afc_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
+// process.cpp, rds_api.cpp, rds_sync_api.cpp, meter_api.cpp, levels.cpp, blend_api.cpp, quiet_api.cpp, afc_api.cpp, scan_api.cpp, prims_api.cpp); no .hip file includes it.  No CPU compute path exists:
 // every numeric result comes from a GPU kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -107,6 +108,17 @@ int upload(DevBuf<T>& d, const T* src, size_t count, const char* what) {
     if (rc) return rc;
     return hipMemcpy(d.p, src, sizeof(T) * count, hipMemcpyHostToDevice) == hipSuccess ? 0 : fail(FMRX_EHIP, "%s failed", what);
 }
+
+// a launch function's code as the entry point's: "<what> launch failed (rc)", FMRX_EINVAL for -1 (then with `hint`)
+inline int launch_failed(int rc, const char* what, const char* hint = "") {
+    return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "%s launch failed (%d)%s", what, rc, rc == -1 ? hint : "");
+}
+
+}  // namespace fmrx
+
+#include "levels.h"  // the level follower (it needs the buffer types above)
+
+namespace fmrx {
 
 using TimingPair = std::pair<hipEvent_t, hipEvent_t>;
 
@@ -237,6 +249,11 @@ struct Ctx {
         size_t cap = 0, bits = 0;             //   its list rows and its bits a stream
         std::vector<fmrx_rds_ext> ext;        // n_streams
     } rdss;
+    // the frame geometry of the mode (set at creation): a granule without a capture rate is the fewest
+    // blocks that are whole meter frames
+    struct Frames {
+        unsigned A = 0, Gm = 0;               // audio frames and meter frames a granule
+    } frames;
     // subcarrier meter (fmrx_set_meter, meter.hip): no signal state; nothing here is allocated until the
     // switch is first turned on (or fmrx_meter first runs)
     struct Meter {
@@ -274,47 +291,31 @@ struct Ctx {
         DevBuf<float> x;                      // a call's floats in front of the quantiser (4 B a sample and channel)
         DevBuf<float> tmp;                    // fmrx_deemph: the caller's next state, before it is copied back
     } deemph;
-    // soft stereo (fmrx_set_stereo_blend, blend.hip): configuration and a carry of its own, not in the blob;
-    // nothing here is allocated until the switch is first turned on (or a blend primitive first runs)
+    // soft stereo (fmrx_set_stereo_blend, blend.hip): configuration and a level follower of its own (levels.h),
+    // not in the blob; nothing here is allocated until the switch is first turned on (or a blend primitive
+    // first runs)
     struct Blend {
         bool on = false;                      // fmrx_set_stereo_blend
         fmrx_blend_config cfg{10.0f, 22.0f};
-        unsigned A = 0, Gm = 0;               // audio frames and meter frames a granule (set at creation)
-        float c = 0.0f;                       // (float)(1.0 / (32.0 A))
+        float c = 0.0f;                       // (float)(1.0 / (32.0 frames.A))
         DevBuf<float> thr;                    // the 16 thresholds of cfg
-        PingPong<float> carry;                // n_streams x kBlendCarry
-        DevBuf<uint8_t> levels;               // a call's level rows: n_streams x (frames + 1)
-        std::vector<uint8_t> host;            // their host copy (frames a stream)
-        size_t pending = 0;                   // frames a stream of a call enqueued and not yet counted
+        LevelFollower f{1, launch_blend_levels, "blend levels"};  // fmrx_blend_hold sets its hold
         std::vector<fmrx_blend_report> rep;   // n_streams
-        bool hold = false;                    // fmrx_blend_hold: calls run at the streams' last levels
-        std::vector<uint8_t> last;            // n_streams: the level of the last frame counted (0 after a reset)
-        std::vector<uint8_t> hold_rows;       // a held call's level rows on the host
-        DevBuf<float> prim_thr, prim_carry;   // the primitives': a caller's thresholds, the next carry before it is copied back
-        fmrx_blend_config prim_cfg{0.0f, 0.0f};  // the config prim_thr holds (lo == hi: none yet)
-        DevBuf<float> prim_pow;               // fmrx_blend_levels: the caller's powers
+        fmrx_blend_config prim_cfg{0.0f, 0.0f};  // the config f.prim_thr holds (lo == hi: none yet)
     } blend;
-    // quieting (fmrx_set_quieting, quiet.hip): configuration and two carries of its own, not in the blob;
-    // nothing here is allocated until the switch is first turned on (or a quieting primitive first runs).
-    // A and Gm are soft stereo's (blend.A, blend.Gm)
+    // quieting (fmrx_set_quieting, quiet.hip): configuration, a level follower (levels.h) and a history of its
+    // own, not in the blob; nothing here is allocated until the switch is first turned on (or a quieting
+    // primitive first runs)
     struct Quiet {
         bool on = false;                      // fmrx_set_quieting
         fmrx_quiet_config cfg{22.0f, 34.0f, 36.0f, 44.0f, 20.0f, 2500};
         float g0 = 0.0f, cg = 0.0f, cw = 0.0f;  // cfg's gains once `tab` is filled
         DevBuf<float> tab;                    // cfg's Tc (16), Tm (16) and taps (64)
-        PingPong<float> carry;                // n_streams x kQuietCarry
+        LevelFollower f{2, launch_quiet_levels, "quieting levels"};  // a frame's pair (c, m); fmrx_quiet_hold sets its hold
         PingPong<float> hist;                 // n_streams x channels x kQuietHist inputs in front of the next call
-        DevBuf<uint8_t> levels;               // a call's level rows: n_streams x 2 (frames + 1)
         DevBuf<float> x;                      // a call's output floats when de-emphasis follows
-        std::vector<uint8_t> host;            // the level rows' host copy (2 frames bytes a stream)
-        size_t pending = 0;                   // frames a stream of a call enqueued and not yet counted
         std::vector<fmrx_quiet_report> rep;   // n_streams
-        bool hold = false;                    // fmrx_quiet_hold: calls run at the streams' last levels
-        std::vector<uint8_t> last;            // n_streams x 2: c and m of the last frame counted (0 after a reset)
-        std::vector<uint8_t> hold_rows;       // a held call's level rows on the host
-        DevBuf<float> prim_thr, prim_carry;   // the levels primitive's: a caller's thresholds, the next carry before it is copied back
-        fmrx_quiet_config prim_cfg{};         // the config prim_thr holds (all zero: none yet)
-        DevBuf<float> prim_pow;               // fmrx_quiet_levels: the caller's powers
+        fmrx_quiet_config prim_cfg{};         // the config f.prim_thr holds (all zero: none yet)
         DevBuf<float> prim_hist;              // fmrx_quiet_apply_device: the caller's next history, before it is copied back
     } quiet;
     // off-centre tuning (fmrx_tune): configuration, not part of the state blob; the tables are allocated
@@ -452,6 +453,19 @@ inline int set_device(const fmrx_ctx* c) {
     HIPCHK(hipSetDevice(c->cfg.device));
     return 0;
 }
+// `count` floats at src into d, grown to hold them; the stream is drained first (a launch in flight may
+// still read the old ones)
+inline int upload_floats(fmrx_ctx* c, const float* src, size_t count, DevBuf<float>& d) {
+    const int rc = d.ensure(count);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(d.p, src, sizeof(float) * count, hipMemcpyHostToDevice));
+    return 0;
+}
+// meter frames of n_blocks blocks (whole granules): the frames of the meter, the carrier sums and the levels
+inline size_t meter_frames(const fmrx_ctx* c, size_t n_blocks) {
+    return n_blocks * c->geo.if_samples / ((size_t)kMeterWindows * (size_t)(c->geo.bp_fs / 1000));
+}
 
 // Every stage that keeps signal state has an init_ (creation: its tables designed and uploaded, its
 // creation-time buffers allocated) and a reset_ (its start state, enqueued on the context stream) beside
@@ -507,8 +521,13 @@ int rds_sync_enqueue(fmrx_ctx* c, const uint8_t* d_bits, size_t n_bits);
 int rds_sync_finish(fmrx_ctx* c);
 
 // ---- meter_api.cpp
-int check_meter_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole frames: the RDS granule's blocks
+void init_frames(fmrx_ctx* c);                               // the mode's frames.A and frames.Gm; nothing allocated
+// whole frames: the RDS granule's blocks, or FMRX_EINVAL "<who> takes whole frames, granules of ..."
+int check_frame_blocks(const fmrx_ctx* c, size_t n_blocks, const char* who);
 void reset_meter(fmrx_ctx* c);                               // the reports back to zero
+// the meter's tables on the device by fmrx_set_meter's own path, its switch put back as it was (the stages
+// that read its powers call this when they are turned on)
+int meter_tables_ready(fmrx_ctx* c);
 // the meter over the rows at d_demod (whole frames) and the copy of its powers to the host, enqueued;
 // meter_finish waits for the stream and adds them to the streams' reports
 int meter_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
@@ -523,32 +542,27 @@ void afc_caller_tuned(fmrx_ctx* c);                          // fmrx_tune / fmrx
 int afc_enqueue(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks);
 int afc_finish(fmrx_ctx* c);
 
-// ---- blend_api.cpp
-void init_blend(fmrx_ctx* c);                                // the mode's A, Gm and c; nothing allocated
-int check_blend_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole granules: the RDS granule's blocks
-int reset_blend(fmrx_ctx* c);                                // the carry (once it exists) and the reports back to the start
-// the levels kernel over the powers the meter kernel left in meter.pow for this call, enqueued, the carry moved;
-// blend_apply: the call's (right, left) rows through the apply kernel (out and pcm as BlendApplyLaunch's);
-// blend_finish copies the level bytes back, waits for the stream and counts them in the streams' reports
-int blend_enqueue(fmrx_ctx* c, size_t n_blocks);
-inline bool blend_metered(const fmrx_ctx* c) { return c->blend.on && !c->blend.hold; }  // the call's levels come from the meter
+// ---- blend_api.cpp, quiet_api.cpp: the two stages on a level follower.  A tuned call enqueues the follower
+// over the powers the meter kernel left in meter.pow (front.cpp taps_enqueue: levels_enqueue, or
+// levels_enqueue_held under hold), runs the stage's apply kernel by the rows (engine.cpp quant_rows), and
+// has the stage's finish count the level bytes into its reports
+void init_blend(fmrx_ctx* c);                                // soft stereo's c of frames.A; nothing allocated
+int reset_blend(fmrx_ctx* c);                                // the follower and the reports back to the start
+int reset_quiet(fmrx_ctx* c);                                // that, and the history (once it exists)
+inline bool blend_metered(const fmrx_ctx* c) { return c->blend.on && !c->blend.f.hold; }  // the call's levels come from the meter
+inline bool quiet_metered(const fmrx_ctx* c) { return c->quiet.on && !c->quiet.f.hold; }
+// the call's (right, left) rows through the apply kernel (out and pcm as BlendApplyLaunch's)
 int blend_apply(fmrx_ctx* c, float* rows, size_t na, bool in_place, int16_t* d_pcm);
-int blend_finish(fmrx_ctx* c);
-// "<who>: not with soft stereo on" as FMRX_ESTATE while the switch is on, else 0
-int refuse_blend(const fmrx_ctx* c, const char* who, const char* why);
-
-// ---- quiet_api.cpp
-int check_quiet_blocks(const fmrx_ctx* c, size_t n_blocks);  // whole granules: the RDS granule's blocks
-int reset_quiet(fmrx_ctx* c);                                // both carries (once they exist) and the reports back to the start
-// the levels kernel over the powers the meter kernel left in meter.pow for this call, enqueued, the carry moved;
-// quiet_apply: the call's rows (na frames a stream) through the apply kernel into d_out (floats), d_pcm or both,
-// the history moved; quiet_finish copies the level bytes back, waits for the stream and counts them
-int quiet_enqueue(fmrx_ctx* c, size_t n_blocks);
-inline bool quiet_metered(const fmrx_ctx* c) { return c->quiet.on && !c->quiet.hold; }  // the call's levels come from the meter
+// the call's rows (na frames a stream) through the apply kernel into d_out (floats), d_pcm or both, the history moved
 int quiet_apply(fmrx_ctx* c, const float* rows, size_t na, float* d_out, int16_t* d_pcm);
+int blend_finish(fmrx_ctx* c);
 int quiet_finish(fmrx_ctx* c);
-// "<who>: not with quieting on" as FMRX_ESTATE while the switch is on, else 0
-int refuse_quiet(const fmrx_ctx* c, const char* who, const char* why);
+// "<who>: not with soft stereo on (<why>)", then "... quieting on (<why_quiet>, or <why>)", as FMRX_ESTATE
+// while that switch is on, else 0
+inline int refuse_row_stages(const fmrx_ctx* c, const char* who, const char* why, const char* why_quiet = nullptr) {
+    if (c->blend.on) return fail(FMRX_ESTATE, "%s: not with soft stereo on (%s)", who, why);
+    return c->quiet.on ? fail(FMRX_ESTATE, "%s: not with quieting on (%s)", who, why_quiet ? why_quiet : why) : 0;
+}
 
 // ---- front.cpp
 int init_front(fmrx_ctx* c);   // the halo; the tuner's and the wide stage's per-stream offsets

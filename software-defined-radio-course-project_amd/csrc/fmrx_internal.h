@@ -371,15 +371,16 @@ constexpr int kBlendPer = 4;         // consecutive (right, left) frames a lane 
 // the 16 thresholds of fmrx_blend_design (host only, in double until stored); false, nothing written:
 // a bound that is not finite, outside [-20, 60], or lo_db >= hi_db
 bool blend_design(float lo_db, float hi_db, float* T16);
-struct BlendLevelsLaunch {
+// a levels kernel's launch, soft stereo's (K = 1 level byte a frame) and quieting's (K = 2: the pair (c, m))
+struct LevelsLaunch {
     const float* power;     // n_streams x frames x kMeterTones (the meter's)
     int frames;             // frames a stream, >= 1
-    const float* thr;       // kBlendSteps thresholds
-    const float* carry_in;  // n_streams x kBlendCarry
-    float* carry_out;       // n_streams x kBlendCarry (never carry_in)
-    uint8_t* levels;        // n_streams x (frames + 1): entry 0 the carried-in level, entry 1 + f frame f's
+    const float* thr;       // the stage's thresholds: kBlendSteps, or 2 x kQuietSteps (Tc, then Tm)
+    const float* carry_in;  // n_streams x 8 (kBlendCarry, kQuietCarry)
+    float* carry_out;       // n_streams x 8 (never carry_in)
+    uint8_t* levels;        // n_streams x K (frames + 1): entry 0 the carried-in level(s), entry 1 + f frame f's
 };
-int launch_blend_levels(const BlendLevelsLaunch& L, int n_streams, hipStream_t s);
+int launch_blend_levels(const LevelsLaunch& L, int n_streams, hipStream_t s);
 struct BlendApplyLaunch {
     const float2* in;       // n_streams rows of n (right, left) frames, 16-byte aligned, n even
     unsigned n;             // frames a row; the first is frame 0 of a granule
@@ -398,15 +399,7 @@ constexpr int kQuietCarry = 8;       // floats a stream: n of the last three fra
 constexpr int kQuietTaps = 64;       // the high-cut's one-pole response, cut as de-emphasis cuts its own
 constexpr int kQuietHist = kQuietTaps - 1;  // inputs carried in front of a call, per stream and channel
 constexpr int kQuietChunk = 1024;    // outputs a workgroup
-struct QuietLevelsLaunch {
-    const float* power;     // n_streams x frames x kMeterTones (the meter's)
-    int frames;             // frames a stream, >= 1
-    const float* thr;       // 2 x kQuietSteps thresholds: Tc, then Tm
-    const float* carry_in;  // n_streams x kQuietCarry
-    float* carry_out;       // n_streams x kQuietCarry (never carry_in)
-    uint8_t* levels;        // n_streams x 2 (frames + 1): entry e is the pair (c, m); 0 the carried-in one, 1 + f frame f's
-};
-int launch_quiet_levels(const QuietLevelsLaunch& L, int n_streams, hipStream_t s);
+int launch_quiet_levels(const LevelsLaunch& L, int n_streams, hipStream_t s);
 struct QuietApplyLaunch {
     const float* in;        // row (stream s, channel ch): sample i at in[s stride + ch + i nch]
     size_t stride;          // floats between the streams' rows, of `in`, `out` and `pcm` alike

@@ -97,16 +97,25 @@ int run_tuned_front(fmrx_ctx* c, const uint8_t* d_iq, size_t iq_stride, size_t n
 // back and added to its reports.  The carrier sums' finish comes last: with tracking it may retune.
 static int check_taps(const fmrx_ctx* c, size_t n_blocks) {
     int rc = c->rdsb.on ? check_rds_blocks(c, n_blocks) : 0;
-    if (!rc && c->meter.on) rc = check_meter_blocks(c, n_blocks);
-    if (!rc && c->afc.on) rc = check_meter_blocks(c, n_blocks);
-    if (!rc && blend_metered(c)) rc = check_blend_blocks(c, n_blocks);
-    return rc || !quiet_metered(c) ? rc : check_quiet_blocks(c, n_blocks);
+    if (!rc && c->meter.on) rc = check_frame_blocks(c, n_blocks, "a meter call");
+    if (!rc && c->afc.on) rc = check_frame_blocks(c, n_blocks, "a carrier call");
+    if (!rc && blend_metered(c)) rc = check_frame_blocks(c, n_blocks, "a call with soft stereo on");
+    return rc || !quiet_metered(c) ? rc : check_frame_blocks(c, n_blocks, "a call with quieting on");
+}
+// a stage's level follower over the call's frames: from the powers the meter kernel leaves in meter.pow for
+// this call, or under hold the streams' last levels over the meter frames the call's audio frames reach
+static int levels_of_call(fmrx_ctx* c, LevelFollower& F, const float* d_thr, size_t n_blocks) {
+    const size_t ns = c->cfg.n_streams, frames = meter_frames(c, n_blocks), na = n_blocks * c->geo.audio_frames;
+    if (F.hold) return levels_enqueue_held(F, c->stream, ns, (na * c->frames.Gm + c->frames.A - 1) / c->frames.A);
+    F.pending = 0;
+    if (frames < 1 || frames > 0x7FFFFFFFull / kMeterTones) return fail(FMRX_EINVAL, "%zu blocks: too many frames for one call", n_blocks);
+    return levels_enqueue(F, c->stream, ns, c->meter.pow.p, d_thr, frames);
 }
 static int taps_enqueue(fmrx_ctx* c, size_t n_blocks) {
     const float* rows = c->stereo.demod.p + kDemodHist;
     int rc = c->meter.on || blend_metered(c) || quiet_metered(c) ? meter_enqueue(c, rows, c->stereo.demod_stride, n_blocks) : 0;
-    if (!rc && c->blend.on) rc = blend_enqueue(c, n_blocks);
-    if (!rc && c->quiet.on) rc = quiet_enqueue(c, n_blocks);
+    if (!rc && c->blend.on) rc = levels_of_call(c, c->blend.f, c->blend.thr.p, n_blocks);
+    if (!rc && c->quiet.on) rc = levels_of_call(c, c->quiet.f, c->quiet.tab.p, n_blocks);
     if (!rc && c->rdsb.on) rc = rds_decode_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
     return rc || !c->afc.on ? rc : afc_enqueue(c, rows, c->stereo.demod_stride, n_blocks);
 }

@@ -2,6 +2,7 @@
 // demod rows (meter.hip), the host-side report and decision, and the switch that runs the meter inside
 // the calls whose front end writes demod rows.
 #include <cmath>
+#include <numeric>
 
 #include "ctx.h"
 
@@ -26,10 +27,6 @@ int ensure_meter_tables(fmrx_ctx* c) {
     return 0;
 }
 
-inline size_t meter_frames(const fmrx_ctx* c, size_t n_blocks) {
-    return n_blocks * c->geo.if_samples / ((size_t)kMeterWindows * (size_t)(c->geo.bp_fs / 1000));
-}
-
 // the kernel over the rows at d_demod (whole frames) into d_power, enqueued
 int run_meter(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_blocks, float* d_power) {
     int rc = ensure_meter_tables(c);
@@ -43,9 +40,7 @@ int run_meter(fmrx_ctx* c, const float* d_demod, size_t demod_stride, size_t n_b
     L.P = c->meter.p;
     L.frames = (int)frames;
     L.power = d_power;
-    if ((rc = launch_meter(L, c->cfg.n_streams, c->stream)))
-        return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "meter launch failed (%d)", rc);
-    return 0;
+    return (rc = launch_meter(L, c->cfg.n_streams, c->stream)) ? launch_failed(rc, "meter") : 0;
 }
 
 inline double db10(double x) { return 10.0 * std::log10(x); }
@@ -70,11 +65,26 @@ bool meter_design(int bp_fs, int* P, float* tables) {
     return true;
 }
 
-int check_meter_blocks(const fmrx_ctx* c, size_t n_blocks) {
+void init_frames(fmrx_ctx* c) {
+    // a granule without a capture rate: the fewest blocks that are whole meter frames
+    const size_t frame = (size_t)kMeterWindows * (size_t)(c->geo.bp_fs / 1000);
+    const size_t blocks = std::lcm((size_t)c->geo.if_samples, frame) / (size_t)c->geo.if_samples;
+    c->frames.Gm = (unsigned)(blocks * c->geo.if_samples / frame);
+    c->frames.A = (unsigned)(blocks * c->geo.audio_frames);
+}
+
+int check_frame_blocks(const fmrx_ctx* c, size_t n_blocks, const char* who) {
     const size_t g = rds_granule_blocks(c);  // a frame is the RDS window: 64 ms
     if (n_blocks % g != 0)
-        return fail(FMRX_EINVAL, "%zu blocks: a meter call takes whole frames, granules of %zu blocks", n_blocks, g);
+        return fail(FMRX_EINVAL, "%zu blocks: %s takes whole frames, granules of %zu blocks", n_blocks, who, g);
     return 0;
+}
+
+int meter_tables_ready(fmrx_ctx* c) {
+    const bool on = c->meter.on;
+    const int rc = fmrx_set_meter(c, 1);
+    c->meter.on = on;
+    return rc;
 }
 
 void reset_meter(fmrx_ctx* c) {
@@ -119,7 +129,7 @@ int fmrx_meter_design(int bp_fs, int* P, float* tables) {
 int fmrx_meter_device(fmrx_ctx* c, const float* d_demod, size_t n_blocks, float* d_power) {
     CtxLock lock_(c);
     if (!c || !d_demod || !d_power) return fail(FMRX_EINVAL, "null argument");
-    int rc = check_meter_blocks(c, n_blocks);
+    int rc = check_frame_blocks(c, n_blocks, "a meter call");
     if (rc || n_blocks == 0) return rc;
     if ((rc = set_device(c))) return rc;
     return run_meter(c, d_demod, n_blocks * c->geo.if_samples, n_blocks, d_power);
@@ -128,7 +138,7 @@ int fmrx_meter_device(fmrx_ctx* c, const float* d_demod, size_t n_blocks, float*
 int fmrx_meter(fmrx_ctx* c, const float* demod, size_t n_blocks, float* power) {
     CtxLock lock_(c);
     if (!c || !demod || !power) return fail(FMRX_EINVAL, "null argument");
-    int rc = check_meter_blocks(c, n_blocks);
+    int rc = check_frame_blocks(c, n_blocks, "a meter call");
     if (rc || n_blocks == 0) return rc;
     if ((rc = set_device(c))) return rc;
     const size_t ns = c->cfg.n_streams, n_if = n_blocks * c->geo.if_samples;

@@ -76,8 +76,7 @@ int process_host(fmrx_ctx* c, const uint8_t* iq, size_t n_blocks, int16_t* pcm, 
     if (!c || !iq || !pcm) return fail(FMRX_EINVAL, "null argument");
     if (shared && !c->tune.on) return fail(FMRX_ESTATE, "fmrx_process_shared: tuning is off (fmrx_tune first)");
     if (n_blocks == 0) return FMRX_OK;
-    int rc = front_tuned(c) ? 0 : refuse_blend(c, "an untuned call", "the fused path writes no demod rows; fmrx_tune with zero offsets first");
-    if (!rc && !front_tuned(c)) rc = refuse_quiet(c, "an untuned call", "the fused path writes no demod rows; fmrx_tune with zero offsets first");
+    int rc = front_tuned(c) ? 0 : refuse_row_stages(c, "an untuned call", "the fused path writes no demod rows; fmrx_tune with zero offsets first");
     if (rc || (rc = set_device(c))) return rc;
     if ((rc = check_call_size(c, n_blocks))) return rc;
     const size_t ns = c->cfg.n_streams;
@@ -105,8 +104,7 @@ int fmrx_process_device_ex(fmrx_ctx* c, const uint8_t* d_iq, size_t n_blocks, in
         if ((rc = check_call_size(c, n_blocks))) return rc;
         return run_tuned(c, d_iq, n_blocks * iq_block_bytes(c), n_blocks, d_pcm, d_mono);
     }
-    if ((rc = refuse_blend(c, "an untuned call", "the fused path writes no demod rows; fmrx_tune with zero offsets first"))) return rc;
-    if ((rc = refuse_quiet(c, "an untuned call", "the fused path writes no demod rows; fmrx_tune with zero offsets first"))) return rc;
+    if ((rc = refuse_row_stages(c, "an untuned call", "the fused path writes no demod rows; fmrx_tune with zero offsets first"))) return rc;
     const size_t n_if = n_blocks * c->geo.if_samples;
     if (c->cfg.channels == FMRX_MONO)  // every mode: RF + demod + audio resampler in one launch
         return run_fused(c, d_iq, n_blocks, d_pcm, d_mono, nullptr, 0, 0, true);
@@ -197,8 +195,7 @@ int fmrx_audio_block(fmrx_ctx* c, const float* demod, size_t n_blocks, int16_t* 
     CtxLock lock_(c);
     if (!c || !demod || !pcm) return fail(FMRX_EINVAL, "null argument");
     if (n_blocks == 0) return FMRX_OK;
-    int rc = refuse_blend(c, "fmrx_audio_block", "the stage runs in the tuned calls");
-    if (!rc) rc = refuse_quiet(c, "fmrx_audio_block", "the stage runs in the tuned calls");
+    int rc = refuse_row_stages(c, "fmrx_audio_block", "the stage runs in the tuned calls");
     if (rc || (rc = set_device(c))) return rc;
     const size_t ns = c->cfg.n_streams;
     const size_t n_if = n_blocks * c->geo.if_samples;

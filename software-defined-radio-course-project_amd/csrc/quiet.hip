@@ -45,7 +45,7 @@ constexpr int kImage = kQuietChunk + kQuietTaps;     // floats staged: 63 of his
 static_assert(kPer == 4, "a lane's outputs start on a float4 of the LDS image");
 static_assert(kQuietTaps % 4 == 0, "whole float4 reads");
 
-__global__ void __launch_bounds__(kThreads) quiet_levels_kernel(QuietLevelsLaunch L, const float* __restrict__ thr, int n_streams) {
+__global__ void __launch_bounds__(kThreads) quiet_levels_kernel(LevelsLaunch L, const float* __restrict__ thr, int n_streams) {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= (long long)n_streams * L.frames) return;
     const int s = (int)(i / L.frames), f = (int)(i - (long long)s * L.frames);
@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(kThreads) quiet_apply_kernel(QuietApplyLaunch 
 
 }  // namespace
 
-int launch_quiet_levels(const QuietLevelsLaunch& L, int n_streams, hipStream_t s) {
+int launch_quiet_levels(const LevelsLaunch& L, int n_streams, hipStream_t s) {
     if (n_streams <= 0) return 0;
     if (L.frames < 1 || L.carry_in == L.carry_out) return -1;
     const long long lanes = (long long)n_streams * L.frames;

@@ -61,22 +61,7 @@ bool quiet_design(int audio_fs, int bp_fs, const fmrx_quiet_config& k, Design* d
 }
 
 inline bool ctx_design(const fmrx_ctx* c, const fmrx_quiet_config& k, Design* d) {
-    return quiet_design(deemph_audio_fs(c), c->geo.bp_fs, k, d) && granule_frames(deemph_audio_fs(c)) == c->blend.A;
-}
-
-// meter frames of n_blocks blocks (whole granules)
-inline size_t quiet_frames(const fmrx_ctx* c, size_t n_blocks) {
-    return n_blocks * c->geo.if_samples / ((size_t)kMeterWindows * (size_t)(c->geo.bp_fs / 1000));
-}
-
-// `count` floats at src into d, grown to hold them; the stream is drained first (a launch in flight may
-// still read the old ones)
-int upload_floats(fmrx_ctx* c, const float* src, size_t count, DevBuf<float>& d) {
-    int rc = d.ensure(count);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(d.p, src, sizeof(float) * count, hipMemcpyHostToDevice));
-    return 0;
+    return quiet_design(deemph_audio_fs(c), c->geo.bp_fs, k, d) && granule_frames(deemph_audio_fs(c)) == c->frames.A;
 }
 
 // the context's thresholds, taps and gains on the device, once a config
@@ -90,37 +75,26 @@ int ensure_tab(fmrx_ctx* c) {
     return rc;
 }
 
-// the levels primitive's thresholds: prim_thr holds those of the last config it was given
+// the levels primitive's thresholds: f.prim_thr holds those of the last config it was given
 int prim_thresholds(fmrx_ctx* c, const fmrx_quiet_config* cfg) {
     auto& Q = c->quiet;
     const fmrx_quiet_config& k = cfg ? *cfg : kDefault;
-    if (Q.prim_thr.p && same_cfg(k, Q.prim_cfg)) return 0;
+    if (Q.f.prim_thr.p && same_cfg(k, Q.prim_cfg)) return 0;
     Design d;
     if (!ctx_design(c, k, &d)) return fail(FMRX_EINVAL, "%s", kBadCfg);
-    const int rc = upload_floats(c, d.tab, 2 * kQuietSteps, Q.prim_thr);
+    const int rc = upload_floats(c, d.tab, 2 * kQuietSteps, Q.f.prim_thr);
     if (!rc) Q.prim_cfg = k;
     return rc;
 }
 
-inline int launch_failed(int rc, const char* what) { return fail(rc == -1 ? FMRX_EINVAL : FMRX_EHIP, "quieting %s launch failed (%d)", what, rc); }
-
-// the levels kernel over d_power with a caller's carry (in and out) on the context stream
-int run_levels_prim(fmrx_ctx* c, const fmrx_quiet_config* cfg, const float* d_power, size_t F, float* d_carry, uint8_t* d_levels) {
-    auto& Q = c->quiet;
-    const size_t ns = c->cfg.n_streams;
-    if (F < 1 || F > 0x7FFFFFFFull / kMeterTones) return fail(FMRX_EINVAL, "%zu frames: a levels call takes 1 .. %d", F, 0x7FFFFFFF / kMeterTones);
-    int rc = prim_thresholds(c, cfg);
-    if (rc || (rc = Q.prim_carry.ensure(ns * kQuietCarry))) return rc;
-    QuietLevelsLaunch L{};
-    L.power = d_power;
-    L.frames = (int)F;
-    L.thr = Q.prim_thr.p;
-    L.carry_in = d_carry;
-    L.carry_out = Q.prim_carry.p;  // a first lane may still read d_carry when a last one is done
-    L.levels = d_levels;
-    if ((rc = launch_quiet_levels(L, (int)ns, c->stream))) return launch_failed(rc, "levels");
-    HIPCHK(hipMemcpyAsync(d_carry, Q.prim_carry.p, sizeof(float) * ns * kQuietCarry, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+// one stream's level pairs (c, m) of a call into its report (levels_finish's count)
+void count_row(void* reports, size_t stream, const uint8_t* row, size_t frames) {
+    fmrx_quiet_report& r = static_cast<fmrx_quiet_report*>(reports)[stream];
+    for (size_t f = 0; f < frames; f++) {
+        r.cut_frames[row[2 * f]]++;
+        r.mute_frames[row[2 * f + 1]]++;
+    }
+    r.frames += frames;
 }
 
 // the launch of na frames a stream with the context's taps and gains; levels, history and outlets are the caller's
@@ -131,8 +105,8 @@ QuietApplyLaunch apply_launch(const fmrx_ctx* c, const float* rows, size_t na) {
     L.nch = c->cfg.channels == FMRX_MONO ? 1 : 2;
     L.stride = na * (size_t)L.nch;
     L.n = (unsigned)na;
-    L.A = c->blend.A;
-    L.Gm = c->blend.Gm;
+    L.A = c->frames.A;
+    L.Gm = c->frames.Gm;
     L.g0 = Q.g0;
     L.cg = Q.cg;
     L.cw = Q.cw;
@@ -144,102 +118,33 @@ QuietApplyLaunch apply_launch(const fmrx_ctx* c, const float* rows, size_t na) {
 
 namespace fmrx {
 
-int check_quiet_blocks(const fmrx_ctx* c, size_t n_blocks) {
-    const size_t g = rds_granule_blocks(c);
-    if (n_blocks % g != 0)
-        return fail(FMRX_EINVAL, "%zu blocks: a call with quieting on takes whole granules of %zu blocks", n_blocks, g);
-    return 0;
-}
-
 int reset_quiet(fmrx_ctx* c) {
     auto& Q = c->quiet;
     Q.rep.assign((size_t)c->cfg.n_streams, fmrx_quiet_report{});  // sized here: creation resets
-    Q.last.assign(2 * (size_t)c->cfg.n_streams, 0);
-    Q.pending = 0;
-    Q.hold = false;
-    Q.carry.rewind();
     Q.hist.rewind();
-    if (Q.carry.cur()) HIPCHK(hipMemsetAsync(Q.carry.cur(), 0, sizeof(float) * Q.carry.buf[0].n, c->stream));
-    if (Q.hist.cur()) HIPCHK(hipMemsetAsync(Q.hist.cur(), 0, sizeof(float) * Q.hist.buf[0].n, c->stream));
-    return 0;
-}
-
-int refuse_quiet(const fmrx_ctx* c, const char* who, const char* why) {
-    return c->quiet.on ? fail(FMRX_ESTATE, "%s: not with quieting on (%s)", who, why) : 0;
-}
-
-int quiet_enqueue(fmrx_ctx* c, size_t n_blocks) {
-    auto& Q = c->quiet;
-    const size_t ns = c->cfg.n_streams, frames = quiet_frames(c, n_blocks);
-    Q.pending = 0;
-    if (Q.hold) {  // every pair of a stream's row its last levels; the rows go up by a blocking copy
-        const size_t na = n_blocks * c->geo.audio_frames, held = (na * c->blend.Gm + c->blend.A - 1) / c->blend.A;
-        int rc = Q.levels.ensure(ns * 2 * (held + 1));
-        if (rc) return rc;
-        Q.hold_rows.resize(ns * 2 * (held + 1));
-        for (size_t s = 0; s < ns; s++)
-            for (size_t e = 0; e <= held; e++) {
-                Q.hold_rows[(s * (held + 1) + e) * 2] = Q.last[2 * s];
-                Q.hold_rows[(s * (held + 1) + e) * 2 + 1] = Q.last[2 * s + 1];
-            }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(Q.levels.p, Q.hold_rows.data(), Q.hold_rows.size(), hipMemcpyHostToDevice));
-        Q.pending = held;
-        return 0;
-    }
-    if (frames < 1 || frames > 0x7FFFFFFFull / kMeterTones) return fail(FMRX_EINVAL, "%zu blocks: too many frames for one call", n_blocks);
-    int rc = Q.levels.ensure(ns * 2 * (frames + 1));
-    if (rc) return rc;
-    QuietLevelsLaunch L{};
-    L.power = c->meter.pow.p;
-    L.frames = (int)frames;
-    L.thr = Q.tab.p;
-    L.carry_in = Q.carry.cur();
-    L.carry_out = Q.carry.next();
-    L.levels = Q.levels.p;
-    if ((rc = launch_quiet_levels(L, (int)ns, c->stream))) return launch_failed(rc, "levels");
-    Q.carry.flip();
-    Q.pending = frames;
-    return 0;
+    const int rc = levels_reset(Q.f, c->stream, (size_t)c->cfg.n_streams);
+    if (!rc && Q.hist.cur()) HIPCHK(hipMemsetAsync(Q.hist.cur(), 0, sizeof(float) * Q.hist.buf[0].n, c->stream));
+    return rc;
 }
 
 int quiet_apply(fmrx_ctx* c, const float* rows, size_t na, float* d_out, int16_t* d_pcm) {
     auto& Q = c->quiet;
     if (na > 0x7FFFFFF0ull) return fail(FMRX_EINVAL, "%zu audio frames a stream: too many for one call", na);
     QuietApplyLaunch L = apply_launch(c, rows, na);
-    L.levels = Q.levels.p;
-    L.level_stride = 2 * (Q.pending + 1);
+    L.levels = Q.f.levels.p;
+    L.level_stride = Q.f.stride();
     L.state_in = Q.hist.cur();
     L.state_out = Q.hist.next();
     L.out = d_out;
     L.pcm = d_pcm;
     const int rc = launch_quiet_apply(L, c->cfg.n_streams, c->stream);
-    if (rc) return launch_failed(rc, "apply");
+    if (rc) return launch_failed(rc, "quieting apply");
     Q.hist.flip();
     return 0;
 }
 
 int quiet_finish(fmrx_ctx* c) {
-    auto& Q = c->quiet;
-    const size_t ns = c->cfg.n_streams, frames = Q.pending;
-    if (frames == 0) return 0;
-    Q.pending = 0;
-    if (Q.hold) return 0;  // nothing measured, nothing counted
-    Q.host.resize(ns * 2 * frames);
-    HIPCHK(hipMemcpy2DAsync(Q.host.data(), 2 * frames, Q.levels.p + 2, 2 * (frames + 1), 2 * frames, ns, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t s = 0; s < ns; s++) {
-        fmrx_quiet_report& r = Q.rep[s];
-        const uint8_t* row = Q.host.data() + s * 2 * frames;
-        for (size_t f = 0; f < frames; f++) {
-            r.cut_frames[std::min<unsigned>(row[2 * f], kQuietSteps)]++;
-            r.mute_frames[std::min<unsigned>(row[2 * f + 1], kQuietSteps)]++;
-        }
-        r.frames += frames;
-        Q.last[2 * s] = (uint8_t)std::min<unsigned>(row[2 * frames - 2], kQuietSteps);
-        Q.last[2 * s + 1] = (uint8_t)std::min<unsigned>(row[2 * frames - 1], kQuietSteps);
-    }
-    return 0;
+    return levels_finish(c->quiet.f, c->stream, (size_t)c->cfg.n_streams, count_row, c->quiet.rep.data());
 }
 
 }  // namespace fmrx
@@ -268,34 +173,22 @@ int fmrx_quiet_levels_device(fmrx_ctx* c, const fmrx_quiet_config* cfg, const fl
     CtxLock lock_(c);
     if (!c || !d_power || !d_carry || !d_levels) return fail(FMRX_EINVAL, "null argument");
     const int rc = set_device(c);
-    return rc ? rc : run_levels_prim(c, cfg, d_power, F, d_carry, d_levels);
+    return rc ? rc : levels_prim_device(c->quiet.f, c->stream, (size_t)c->cfg.n_streams, [&] { return prim_thresholds(c, cfg); }, d_power, F, d_carry, d_levels);
 }
 
 int fmrx_quiet_levels(fmrx_ctx* c, const fmrx_quiet_config* cfg, const float* power, size_t F, float* carry, uint8_t* levels) {
     CtxLock lock_(c);
     if (!c || !power || !carry || !levels) return fail(FMRX_EINVAL, "null argument");
-    if (F < 1 || F > 0x7FFFFFFFull / kMeterTones) return fail(FMRX_EINVAL, "%zu frames: a levels call takes 1 .. %d", F, 0x7FFFFFFF / kMeterTones);
-    int rc = set_device(c);
-    if (rc) return rc;
-    auto& Q = c->quiet;
-    const size_t ns = c->cfg.n_streams, n_pow = ns * F * kMeterTones, n_lv = ns * 2 * (F + 1);
-    // the powers, then the carry, in one buffer of floats; the level rows in the context's
-    if ((rc = Q.prim_pow.ensure(n_pow + ns * kQuietCarry)) || (rc = Q.levels.ensure(n_lv))) return rc;
-    float* d_carry = Q.prim_pow.p + n_pow;
-    HIPCHK(hipMemcpyAsync(Q.prim_pow.p, power, sizeof(float) * n_pow, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_carry, carry, sizeof(float) * ns * kQuietCarry, hipMemcpyHostToDevice, c->stream));
-    if ((rc = run_levels_prim(c, cfg, Q.prim_pow.p, F, d_carry, Q.levels.p))) return rc;
-    HIPCHK(hipMemcpyAsync(levels, Q.levels.p, n_lv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(carry, d_carry, sizeof(float) * ns * kQuietCarry, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return FMRX_OK;
+    int rc = levels_check_frames(F);
+    if (rc || (rc = set_device(c))) return rc;
+    return levels_prim_host(c->quiet.f, c->stream, (size_t)c->cfg.n_streams, [&] { return prim_thresholds(c, cfg); }, power, F, carry, levels);
 }
 
 int fmrx_quiet_apply_device(fmrx_ctx* c, const float* d_in, size_t n, const uint8_t* d_levels, float* d_state, float* d_out,
                             int16_t* d_pcm) {
     CtxLock lock_(c);
     if (!c || !d_in || !d_levels || !d_state || (!d_out && !d_pcm)) return fail(FMRX_EINVAL, "null argument");
-    const unsigned A = c->blend.A, Gm = c->blend.Gm;
+    const unsigned A = c->frames.A, Gm = c->frames.Gm;
     if (n % A != 0 || n > 0x7FFFFFF0ull)
         return fail(FMRX_EINVAL, "%zu audio frames: a quieting call takes whole granules of %u (at most 2^31 - 16 frames)", n, A);
     const size_t ns = c->cfg.n_streams, nch = c->cfg.channels == FMRX_MONO ? 1 : 2, total = ns * n * nch;
@@ -308,12 +201,12 @@ int fmrx_quiet_apply_device(fmrx_ctx* c, const float* d_in, size_t n, const uint
     if (rc || (rc = ensure_tab(c)) || (rc = c->quiet.prim_hist.ensure(ns * nch * kQuietHist))) return rc;
     QuietApplyLaunch L = apply_launch(c, d_in, n);
     L.levels = d_levels;
-    L.level_stride = 2 * (n / A * Gm + 1);
+    L.level_stride = level_row_bytes(2, n / A * Gm);
     L.state_in = d_state;
     L.state_out = c->quiet.prim_hist.p;  // a first workgroup may still read d_state when a last one is done
     L.out = d_out;
     L.pcm = d_pcm;
-    if ((rc = launch_quiet_apply(L, (int)ns, c->stream))) return launch_failed(rc, "apply");
+    if ((rc = launch_quiet_apply(L, (int)ns, c->stream))) return launch_failed(rc, "quieting apply");
     HIPCHK(hipMemcpyAsync(d_state, c->quiet.prim_hist.p, sizeof(float) * ns * nch * kQuietHist, hipMemcpyDeviceToDevice, c->stream));
     return FMRX_OK;
 }
@@ -330,11 +223,7 @@ int fmrx_set_quieting(fmrx_ctx* c, int on, const fmrx_quiet_config* cfg) {
     auto& Q = c->quiet;
     const size_t ns = c->cfg.n_streams, rows = ns * (size_t)c->cfg.channels;
     if (on) {  // everything but a call's rows now, so that a quieted call allocates nothing else
-        if ((rc = Q.carry.ensure(ns * kQuietCarry)) || (rc = Q.hist.ensure(rows * kQuietHist))) return rc;
-        // the meter's tables too: fmrx_set_meter's own path (its switch is put back as it was)
-        const bool meter_on = c->meter.on;
-        if ((rc = fmrx_set_meter(c, 1))) return rc;
-        c->meter.on = meter_on;
+        if ((rc = Q.f.carry.ensure(ns * kLevelCarry)) || (rc = Q.hist.ensure(rows * kQuietHist)) || (rc = meter_tables_ready(c))) return rc;
     }
     if ((on || Q.tab.p) && (rc = upload_floats(c, d.tab, kTabFloats, Q.tab))) return rc;  // (else: at a primitive's first run)
     Q.g0 = d.g0, Q.cg = d.cg, Q.cw = d.cw;
@@ -349,7 +238,7 @@ int fmrx_quiet_hold(fmrx_ctx* c, int on) {
     CtxLock lock_(c);
     if (!c) return fail(FMRX_EINVAL, "null context");
     if (on && !c->quiet.on) return fail(FMRX_ESTATE, "fmrx_quiet_hold: quieting is off (fmrx_set_quieting first)");
-    c->quiet.hold = on != 0;
+    c->quiet.f.hold = on != 0;
     return FMRX_OK;
 }
 

@@ -2,6 +2,7 @@
 """Soft stereo on one GPU.
 
     python tools/bench_blend.py off [--tree DIR] [--repeats 5]          one JSON line
+    python tools/bench_blend.py switch [--tree DIR] [--repeats 5]       one JSON line: `on`'s switch leg alone, in DIR's build
     python tools/bench_blend.py on [--repeats 5] [--ab-dir DIR] [--out profiles/blend]
 
 off: a tuned stereo fmrx_process_device call, mode 0, 16 streams x 3.072 s, with the stage off (wall clock, the
@@ -158,7 +159,7 @@ def ab(ab_dir):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("leg", choices=["off", "on"])
+    ap.add_argument("leg", choices=["off", "switch", "on"])
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--streams", type=int, default=256)
@@ -168,6 +169,11 @@ def main():
     args = ap.parse_args()
     if args.leg == "off":
         print(json.dumps(leg_off(args.tree, args.repeats)))
+        return
+    if args.leg == "switch":  # the switch leg alone in the build of --tree (tools/bench_quiet.py ab sums the alternating runs up)
+        torch, iqgen, fm = load(args.tree)
+        res = leg_switch(torch, fm, iqgen, args.repeats)
+        print(json.dumps({"leg": "switch", "tree": os.path.relpath(os.path.abspath(args.tree), REPO), **res}))
         return
     torch, iqgen, fm = load(REPO)
     prop = torch.cuda.get_device_properties(0)

@@ -2,6 +2,8 @@
 """Quieting on one GPU.
 
     python tools/bench_quiet.py off [--channels 0|1|2] [--tree DIR] [--repeats 5]    one JSON line a channel count (0: both)
+    python tools/bench_quiet.py switch [--channels 0|1|2] [--tree DIR] [--repeats 5] one JSON line a channel count
+    python tools/bench_quiet.py ab --ab-dir DIR                                      the alternating runs' lines summed up (no GPU)
     python tools/bench_quiet.py on [--repeats 5] [--ab-dir DIR] [--out profiles/quiet]
     python tools/bench_quiet.py kernel-mono [--repeats 5] [--out profiles/quiet]
 
@@ -13,8 +15,9 @@ fmrx_set_quieting off and on, alone and beside soft stereo (stereo) and de-empha
 apply kernel alone (fmrx_quiet_apply_device, HIP events on the context's stream, a warm-up and `repeats` runs)
 over 256 streams x 9.984 s of (R, L) rows with levels uniform in 0..16 and with all 16, writing PCM and
 writing floats, and in the same run on the same rows fmrx_deemph, fmrx_blend_apply_device and a
-device-to-device copy.  --ab-dir: the lines of the alternating runs, parent_*.json and this_*.json (`off`
-lines and bench.py result lines).  Writes bench_quiet.json and bench_quiet.md under --out; every number in
+device-to-device copy.  switch: those switch legs alone in the build of DIR, for alternating runs against
+the parent commit's build of a change to the host code that runs once a call.  --ab-dir: the lines of the alternating runs, parent_*.json and this_*.json (`off`
+lines, `switch` lines of this tool and of bench_blend.py, and bench.py result lines).  Writes bench_quiet.json and bench_quiet.md under --out; every number in
 them was measured by this run (the alternating lines by the runs that wrote --ab-dir).  kernel-mono: the apply
 kernel over the same bytes as rows of a MONO context (contiguous rows; a stereo context's workgroups take one
 channel each and read and write every other float), into bench_quiet_kernel_mono.json and .md.
@@ -213,7 +216,11 @@ def ab(ab_dir):
                     row = json.loads(line)
                 except ValueError:
                     continue
-                if row.get("leg") == "off":
+                if row.get("leg") == "switch":  # this tool's lines hold `runs`, bench_blend.py's `median_ms`
+                    name = "blend_tool_stereo" if "median_ms" in row else "stereo" if row["channels"] == 2 else "mono"
+                    for k, v in (row.get("median_ms") or {k: r["median"] for k, r in row["runs"].items()}).items():
+                        out.setdefault(f"switch_{name}_{k}_ms", {}).setdefault(who, []).append(v)
+                elif row.get("leg") == "off":
                     out.setdefault(f"off_{'stereo' if row['channels'] == 2 else 'mono'}_ms", {}).setdefault(who, []).append(row["ms_median"])
                 elif "value" in row and "metric" in row:
                     out.setdefault(f"bench_py_{row.get('unit', 'value')}", {}).setdefault(who, []).append(row["value"])
@@ -228,7 +235,7 @@ def ab(ab_dir):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("leg", choices=["off", "on", "kernel-mono"])
+    ap.add_argument("leg", choices=["off", "switch", "ab", "on", "kernel-mono"])
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--channels", type=int, default=0, choices=[0, 1, 2])
     ap.add_argument("--repeats", type=int, default=5)
@@ -241,6 +248,15 @@ def main():
         loaded = load(args.tree)
         for channels in ((1, 2) if args.channels == 0 else (args.channels,)):
             print(json.dumps(leg_off(*loaded, args.tree, channels, args.repeats)), flush=True)
+        return
+    if args.leg == "switch":
+        torch, iqgen, fm = load(args.tree)
+        for channels in ((1, 2) if args.channels == 0 else (args.channels,)):
+            res = leg_switch(torch, fm, iqgen, channels, args.repeats)
+            print(json.dumps({"leg": "switch", "channels": channels, "tree": os.path.relpath(os.path.abspath(args.tree), REPO), **res}), flush=True)
+        return
+    if args.leg == "ab":
+        print(json.dumps(ab(args.ab_dir), indent=1))
         return
     torch, iqgen, fm = load(REPO)
     prop = torch.cuda.get_device_properties(0)
